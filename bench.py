@@ -2,7 +2,16 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--model gru|transformer]
                     [--mode clip|window] [--batch 32] [--precision winograd|exact|x3]
-                    [--no-cpu-baseline] [--no-side]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-side]]
+
+A plain run sets up, warms up, times the K steps and prints the headline
+(metric / value / unit / ms_per_step / dtype, the timed region's per-stage
+times and the roofline they give).  --dump-outputs DIR then also writes what
+the last timed step returned to its caller as DIR/<name>.npy (float32; the
+inputs and weights are seeded, so two builds can be compared output for
+output).  Everything else below (latencies, isolated per-stage passes, the
+other precisions and configurations, the CPU baseline and its parity) takes
+runs of its own and is measured only with --full.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment (a plain
 ``python bench.py --gpus 8``) the process launches N ranks itself before it
@@ -23,7 +32,7 @@ N > 1 (one process per GPU) every rank runs its own shard of clips (weak
 scaling) and the framewise outputs are gathered to rank 0 over RCCL inside
 each step — the path's only collective.  Rank 0 prints ONE JSON line.
 
-At N = 1 the line also carries, each with its own roofline:
+With --full at N = 1 the line also carries, each with its own roofline:
   value_exact         the same workload with the direct fp32 conv everywhere
                       (the reference's operation order; sedx_set_precision EXACT)
   value_x3            the same workload with the opt-in 3xbf16-split MFMA
@@ -593,19 +602,26 @@ def roofline(stage_ms, B, precision, T=1001, iso_ms=None, summary=None):
 # ---------------------------------------------------------------------------
 # legs
 # ---------------------------------------------------------------------------
-def clip_leg(model, wave, args, world, rank, dev, precision, isolated=False):
-    """Throughput + per-stage timed-region times + device p50/p99; with
-    ``isolated`` also the per-stage times one batch at a time (the roofline's
-    launch time)."""
+def clip_leg(model, wave, args, world, rank, dev, precision, isolated=False, latencies=True, keep=None):
+    """Throughput + per-stage timed-region times + (``latencies``) device
+    p50/p99; with ``isolated`` also the per-stage times one batch at a time
+    (the roofline's launch time).  ``keep`` (a dict, --dump-outputs) receives
+    what the last step returned: the model's outputs at N = 1, the gathered
+    framewise + clipwise on rank 0 at N > 1."""
     model.set_precision(precision)
     B = wave.shape[0]
 
     def step():
         with torch.no_grad():
-            gather_outputs(model(wave), world, rank)
+            out = model(wave)
+            fw, cw = gather_outputs(out, world, rank)
+        if keep is not None:
+            keep['out'] = out if world == 1 else {'framewise_output': fw, 'clipwise_output': cw}
 
     value, elapsed, stage_ms = measure(step, args, world, dev, model, B)
-    p50, p99 = latency(step, B, max(5, min(args.steps, 20)), dev)
+    if keep is not None:
+        keep['last'] = keep.pop('out')      # the last timed step's, not a later latency pass's
+    p50, p99 = latency(step, B, max(5, min(args.steps, 20)), dev) if latencies else (None, None)
     iso = stage_times_isolated(model, wave, dev, max(3, min(args.steps, 10))) if isolated else None
     return value, elapsed, stage_ms, p50, p99, iso
 
@@ -619,11 +635,12 @@ def gamma_profile(B):
     return traffic, rocprof_ms
 
 
-def gamma_leg(args, dev, precision):
+def gamma_leg(args, dev, precision, keep=None):
     """BASELINE config 4: Cnn_9layers_Gru_FrameAtt gammatone 32k, B=32.  A
     step = float64 gammatone features of 32 x 10 s @ 32 kHz clips (the
     reference computes them on the CPU at HDF5-pack time, utils/features.py:
-    361-370) + the gamma-branch forward (models.py:636-688)."""
+    361-370) + the gamma-branch forward (models.py:636-688).  ``keep`` as in
+    clip_leg."""
     name = MODEL_NAMES['gru']
     m = build_model(name, dev, (32000, 1024, 320, 64, 50, 14000), 'gamma').set_precision(precision)
     if getattr(args, 'gamma_spec', None) is not None:
@@ -633,9 +650,13 @@ def gamma_leg(args, dev, precision):
 
     def step():
         with torch.no_grad():
-            m(inference.gamma_features(m, audio))
+            out = m(inference.gamma_features(m, audio))
+        if keep is not None:
+            keep['out'] = out
 
     value, elapsed, stage_ms = measure(step, args, 1, dev, m, B)
+    if keep is not None:
+        keep['last'] = keep.pop('out')
     with torch.no_grad():
         feats = inference.gamma_features(m, audio)
     iso = stage_times_isolated(m, feats, dev, max(3, min(args.steps, 10)))
@@ -674,15 +695,19 @@ def gamma_leg(args, dev, precision):
                                        '+ 64 x 1025 ERB product per frame; bytes: audio in + features out'}}
 
 
-def window_leg(model, wave, args, dev, precision):
+def window_leg(model, wave, args, dev, precision, keep=None):
     model.set_precision(precision)
     B = wave.shape[0]
 
     def step():
         with torch.no_grad():
-            inference.predict_windows(model, wave, 5, 1)
+            merged = inference.predict_windows(model, wave, 5, 1)
+        if keep is not None:
+            keep['out'] = {'framewise_output': merged}
 
     value, elapsed, _ = measure(step, args, 1, dev, None, B)
+    if keep is not None:
+        keep['last'] = keep.pop('out')
     p50, p99 = latency(step, B, max(5, min(args.steps, 20)), dev)
     # the dominant launch of one windowed call: B' = 6 B windows of T = 501
     # frames (5 s at hop 160) through the model as one batch
@@ -750,6 +775,33 @@ def events_side(model, wave):
     for _ in range(reps):
         n_ev = len(inference.event_pairs(fw, params))
     return {'events_ms_per_batch': round((time.perf_counter() - t0) / reps * 1e3, 4), 'events_per_batch': n_ev}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out, directory, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: every tensor of ``out`` (what the last timed step
+    returned) as directory/<name>.npy in float32 (float64 stays float64).
+    Past ``max_bytes`` in all, each array keeps its share of the budget as a
+    fixed sample: the elements at seeded, sorted flat indices (the same ones
+    in every run of the same shapes), saved 1-D."""
+    arrays = {}
+    for k, v in out.items():
+        if not torch.is_tensor(v):
+            continue
+        a = v.detach().cpu().numpy()
+        arrays[k] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(directory, exist_ok=True)
+    for k, a in sorted(arrays.items()):
+        if total > max_bytes:
+            n = max(1, int(max_bytes * (a.nbytes / total)) // a.itemsize)
+            if n < a.size:
+                idx = np.sort(np.random.RandomState(0).choice(a.size, n, replace=False))
+                a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, k + '.npy'), a)
+    return sorted(arrays)
 
 
 # ---------------------------------------------------------------------------
@@ -835,8 +887,8 @@ def rank0_cpu_baseline(args, world, rank, run):
     other ranks go on to the closing barrier and wait there while rank 0
     times the oracle (so the N > 1 line carries cpu_baseline too; its sample
     is the same bounded B = 32 oracle run as at N = 1, on rank 0's host
-    threads)."""
-    if rank != 0 or args.no_cpu_baseline:
+    threads).  A --full measurement."""
+    if rank != 0 or args.no_cpu_baseline or not args.full:
         return None
     return run()
 
@@ -864,9 +916,14 @@ def stub_main(args, world, rank):
         sys.exit(3)
     B = args.batch
     wave = torch.from_numpy(synth.make_waveforms(B, 0.1, 16000, seed=1234 + rank))
-    value, elapsed, _, p50, _, _ = clip_leg(StubModel(), wave, args, world, rank, dev, args.precision)
-    # the config-5 leg of the N > 1 run (a second model, the same measurement path)
-    c5 = config5_leg(StubModel(), wave, args, world, rank, dev, args.precision, isolated=False)
+    keep = {} if args.dump_outputs else None
+    value, elapsed, _, p50, _, _ = clip_leg(StubModel(), wave, args, world, rank, dev, args.precision,
+                                            latencies=args.full, keep=keep)
+    if keep is not None and rank == 0:
+        dump_outputs(keep['last'], args.dump_outputs)
+    # --full: the config-5 leg of the N > 1 run (a second model, the same measurement path)
+    c5 = (config5_leg(StubModel(), wave, args, world, rank, dev, args.precision, isolated=False)
+          if args.full else None)
     env = {k: os.environ.get(k) for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR')}
     envs = [None] * world if rank == 0 else None
     if world > 1:
@@ -891,6 +948,13 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch', type=int, default=32, help='clips per GPU per step')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline also measure everything else: latencies (device, host to host, one '
+                         'clip), isolated per-stage times, the other precisions, configs 3 / 4 / 5, window mode, '
+                         'the CPU baseline and its parity (--no-side / --no-cpu-baseline trim it)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last one returned (framewise_output, '
+                         'clipwise_output, embedding) as DIR/<name>.npy, float32')
     ap.add_argument('--streams', type=int, default=2,
                     help='batches in flight per GPU (HIP streams the steps rotate over)')
     ap.add_argument('--no-pipeline', action='store_true',
@@ -939,6 +1003,8 @@ def main():
                     help='winograd precision: block 1 as Winograd with conv1 inside the launch (2), fed by a '
                          'separate conv1 launch (1), or as the direct fused kernel (0); default: WINO_BLOCK1')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # a plain `python bench.py --gpus N`: start the N ranks here, before
@@ -973,42 +1039,55 @@ def main():
     B = args.batch
     wave = torch.from_numpy(synth.make_waveforms(B, 10.0, 16000, seed=1234 + rank)).to(dev)
 
-    side = world == 1 and rank == 0 and not args.no_side and args.mode == 'clip'
+    # a plain run measures the headline only; --full adds the side legs
+    side = args.full and world == 1 and rank == 0 and not args.no_side and args.mode == 'clip'
+    keep = {} if args.dump_outputs else None
     iso_ms = None
     if rank == 0:
         progress('headline leg (%s, %s mode, B=%d, %d steps)' % (args.precision, args.mode, B, args.steps))
     if args.mode == 'gamma':
-        res = gamma_leg(args, dev, args.precision)
+        res = gamma_leg(args, dev, args.precision, keep=keep)
         if rank == 0:
+            if keep is not None:
+                res['outputs_dumped'] = dump_outputs(keep['last'], args.dump_outputs)
             print(json.dumps(res))
         return
     if args.mode == 'clip':
         # per-stage times one batch at a time (the roofline's launch time) on
         # every rank at N > 1 too (no collective inside; rank 0's are reported)
-        value, elapsed, stage_ms, p50_dev, p99_dev, iso_ms = clip_leg(model, wave, args, world, rank, dev,
-                                                                     args.precision, isolated=side or world > 1)
+        value, elapsed, stage_ms, p50_dev, p99_dev, iso_ms = clip_leg(
+            model, wave, args, world, rank, dev, args.precision,
+            isolated=side or (args.full and world > 1), latencies=args.full, keep=keep)
         roof = roofline(stage_ms, B, args.precision, iso_ms=iso_ms)
     else:
         model.set_precision(args.precision)
-        wl = window_leg(model, wave, args, dev, args.precision)
+        wl = window_leg(model, wave, args, dev, args.precision, keep=keep)
         value, elapsed, stage_ms, roof = wl['value'], wl['ms_per_step'] * args.steps / 1e3, None, None
         p50_dev = p99_dev = None
-    # p50 from host-visible input (pinned) to the framewise output on the host
-    host_wave = wave.cpu().pin_memory()
-    host_out = torch.empty((B * world, 1000, 25), dtype=torch.float32).pin_memory() if rank == 0 else None
+    dumped = None
+    if keep is not None and rank == 0:
+        dumped = dump_outputs(keep['last'], args.dump_outputs)
+        progress('outputs of the last timed step (%s) written' % ', '.join(dumped))
+    keep = None
     # BASELINE config 5 at N > 1: the Transformer model through the same
     # sharded step (the driver's `bench.py --gpus N` measures both models)
     c5 = None
-    if world > 1 and args.mode == 'clip' and args.model == 'gru' and not args.no_side:
+    if args.full and world > 1 and args.mode == 'clip' and args.model == 'gru' and not args.no_side:
         if rank == 0:
             progress('config5 (Transformer, %d ranks) leg' % world)
         trf = build_model(MODEL_NAMES['transformer'], dev)
         c5 = config5_leg(trf, wave, args, world, rank, dev, args.precision)
         del trf
-    h2h = host_to_host_step(model, host_wave, host_out, dev, world, rank)
-    for _ in range(3):
-        h2h()
-    p50, p99 = latency(h2h, B, max(5, min(args.steps, 20))) if args.mode == 'clip' else (None, None)
+    # p50 from host-visible input (pinned) to the framewise output on the host
+    p50 = p99 = None
+    if args.full:
+        host_wave = wave.cpu().pin_memory()
+        host_out = torch.empty((B * world, 1000, 25), dtype=torch.float32).pin_memory() if rank == 0 else None
+        h2h = host_to_host_step(model, host_wave, host_out, dev, world, rank)
+        for _ in range(3):
+            h2h()
+        if args.mode == 'clip':
+            p50, p99 = latency(h2h, B, max(5, min(args.steps, 20)))
     # the same from int16 host input: the reference's batched clip driver
     # reads HDF5 int16 waveforms (utils/data_generator.py:20-49); the model
     # takes them as they are and dequantises on the device (half the PCIe bytes)
@@ -1096,7 +1175,7 @@ def main():
     if rank == 0:
         line = {
             'metric': METRICS[args.model], 'value': round(value, 2), 'unit': 'clips/s', 'n_gpus': world,
-            'steps': args.steps, 'warmup': args.warmup,
+            'steps': args.steps, 'warmup': args.warmup, 'full': args.full,
             'ms_per_step': round(elapsed / args.steps * 1e3, 4),
             'ms_per_clip_p50': round(p50, 4) if p50 is not None else None,
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
@@ -1126,6 +1205,8 @@ def main():
             'library': os.path.relpath(_lib.LIB_PATH, REPO), 'library_version': _lib.lib().sedx_version().decode(),
         }
         line.update(extra)
+        if dumped is not None:
+            line['outputs_dumped'] = dumped
         if c5 is not None:
             line.setdefault('configs', {})['config5'] = c5
         if cpu:

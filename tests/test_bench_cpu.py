@@ -167,8 +167,8 @@ def test_bench_launches_n_ranks(n):
     elapsed time; gloo and a CPU stand-in model here), and exactly one JSON
     line comes back, with n_gpus = N."""
     B, steps = 4, 3
-    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', str(n), '--stub', '--steps',
-                        str(steps), '--warmup', '1', '--batch', str(B), '--streams', '1'],
+    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', str(n), '--stub', '--full',
+                        '--steps', str(steps), '--warmup', '1', '--batch', str(B), '--streams', '1'],
                        capture_output=True, text=True, timeout=600, cwd=REPO, env=_bench_env())
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -194,6 +194,57 @@ def test_bench_launches_n_ranks(n):
     assert cpu is not None and cpu['value'] > 0 and cpu['unit'] == 'clips/s' and cpu['kind'] == 'port'
     assert cpu['cores'] >= 1 and cpu['sample']
     assert d['config']['world_size'] == n
+
+
+def _stub_run(extra, steps=3, B=4):
+    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--stub', '--steps', str(steps),
+                        '--warmup', '1', '--batch', str(B), '--streams', '1'] + extra,
+                       capture_output=True, text=True, timeout=300, cwd=REPO, env=_bench_env())
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+def test_plain_run_measures_the_headline_only(tmp_path):
+    """Without --full the run times its steps and prints the headline: no CPU
+    baseline, no config-5 leg.  --dump-outputs writes what the last timed step
+    returned, float32, identical from run to run (seeded inputs) and whatever
+    the number of steps."""
+    import numpy as np
+    a, b = str(tmp_path / 'a'), str(tmp_path / 'b')
+    d = _stub_run(['--dump-outputs', a], steps=3)
+    assert d['steps'] == 3 and d['ms_per_step'] > 0 and d['value'] > 0
+    assert d['cpu_baseline'] is None and d['configs']['config5'] is None
+    _stub_run(['--dump-outputs', b], steps=2)
+    assert sorted(os.listdir(a)) == ['clipwise_output.npy', 'framewise_output.npy']
+    for f in os.listdir(a):
+        x, y = np.load(os.path.join(a, f)), np.load(os.path.join(b, f))
+        assert x.dtype == np.float32 and np.array_equal(x, y)
+    assert np.load(os.path.join(a, 'framewise_output.npy')).shape == (4, 1000, 25)
+
+
+def test_dump_outputs_samples_past_the_budget(bench, tmp_path):
+    """Past the byte budget every array keeps its share as the elements at
+    fixed (seeded, sorted) flat indices: the same ones in every run."""
+    import numpy as np
+    import torch
+    out = {'big': torch.arange(3000, dtype=torch.float32).reshape(30, 100),
+           'small': torch.arange(1000, dtype=torch.float64), 'note': 'not a tensor'}
+    names = bench.dump_outputs(out, str(tmp_path / 'full'))
+    assert names == ['big', 'small']
+    big = np.load(str(tmp_path / 'full' / 'big.npy'))
+    assert big.shape == (30, 100) and big.dtype == np.float32
+    assert np.load(str(tmp_path / 'full' / 'small.npy')).dtype == np.float64
+    for d in ('s1', 's2'):
+        bench.dump_outputs(out, str(tmp_path / d), max_bytes=4000)
+    s1 = {k: np.load(str(tmp_path / 's1' / (k + '.npy'))) for k in names}
+    s2 = {k: np.load(str(tmp_path / 's2' / (k + '.npy'))) for k in names}
+    assert sum(v.nbytes for v in s1.values()) <= 4000
+    for k in names:
+        assert s1[k].ndim == 1 and 0 < s1[k].size < out[k].numel() and np.array_equal(s1[k], s2[k])
+        assert np.all(np.diff(s1[k]) > 0)          # values = their own flat indices, sorted
+        assert np.isin(s1[k], out[k].numpy().reshape(-1)).all()
 
 
 def test_bench_launcher_fails_when_a_rank_fails():

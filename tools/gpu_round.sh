@@ -15,4 +15,4 @@ run() {  # name timeout cmd...
 }
 run smoke 300 python -c "import __graft_entry__ as g; g.build(); g.smoke()"
 run pytest_gpu 900 python -m pytest tests -m gpu -x -q -s
-run bench 600 python bench.py --steps ${BENCH_STEPS:-10} --warmup 3 ${BENCH_ARGS}
+run bench 600 python bench.py --full --steps ${BENCH_STEPS:-10} --warmup 3 ${BENCH_ARGS}

@@ -8,7 +8,7 @@
 #   tests          pytest -m gpu (all GPU tests)
 #   tests=EXPR     pytest -m gpu -k EXPR  (',' in EXPR reads as ' ')
 #   testsp=EXPR    the same with -s (the tests' printed errors in the log)
-#   bench          python bench.py (default command)
+#   bench          python bench.py --full (every leg)
 #   bench=ARGS     python bench.py ARGS   (',' in ARGS reads as ' ')
 #   w43=B          tools/run/w43_bench B 20 (build first: tools/build_w43.sh)
 #   w43v=NAME:B    tools/run/w43_bench_NAME B 20 (a VARIANTS build)
@@ -16,7 +16,7 @@
 #   w43s=B         tools/run/w43_bench B 20 with W43_SCHED=0 (static item order, no claims)
 #   prof           tools/profile_round.sh (rocprof kernel trace + PMC passes; env as there)
 #   ab=SETS        tools/ab_headline.sh: headline-leg A/B of '|'-separated bench argument sets (',' = ' ')
-#   rank2          python bench.py --gpus 2 --backend gloo (the N > 1 path, both ranks on GPU 0)
+#   rank2          python bench.py --full --gpus 2 --backend gloo (the N > 1 path, both ranks on GPU 0)
 #   sq             three rocprofv3 --pmc SQ passes of the headline (one stream) into gpurun_out/TAG/sq{1,2,3}
 #                  (tools/sq_summary.py input)
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -43,7 +43,7 @@ for s in "$@"; do
     tests) step pytest 1100 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread ;;
     testsp=*) step pytest 1100 python -u -m pytest tests -m gpu -x -v -s --timeout 300 --timeout-method thread -k "$arg" ;;
     tests=*) step pytest 1100 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread -k "$arg" ;;
-    bench) step bench 600 python -u bench.py ;;
+    bench) step bench 600 python -u bench.py --full ;;
     bench=*) step bench 600 python -u bench.py $arg ;;
     w43=*) step w43_b$arg 200 tools/run/w43_bench $arg 20 ;;
     w43v=*) v=${arg%%:*}; b=${arg#*:}; step w43_${v}_b$b 200 tools/run/w43_bench_$v $b 20 ;;
@@ -51,7 +51,7 @@ for s in "$@"; do
     w43s=*) step w43_static_b$arg 200 env W43_SCHED=0 tools/run/w43_bench $arg 20 ;;
     prof) step prof 1100 tools/profile_round.sh ;;
     ab=*) step ab 900 tools/ab_headline.sh "$TAG/ab$n" "${s#*=}" ${AB_ROUNDS:-2} ;;
-    rank2) step rank2 600 python -u bench.py --gpus 2 --backend gloo ;;
+    rank2) step rank2 600 python -u bench.py --full --gpus 2 --backend gloo ;;
     sq)
       A="--no-cpu-baseline --no-side --streams 1 --steps 3 --warmup 1"
       step sq1 150 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY \

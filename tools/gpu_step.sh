@@ -26,5 +26,5 @@ if [ -z "$NOTEST" ]; then
   fi
 fi
 if [ -z "$NOBENCH" ]; then
-  step bench 900 python bench.py --steps ${BENCH_STEPS:-20} --warmup 3 ${BENCH_ARGS} || exit $?
+  step bench 900 python bench.py --full --steps ${BENCH_STEPS:-20} --warmup 3 ${BENCH_ARGS} || exit $?
 fi

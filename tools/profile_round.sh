@@ -18,7 +18,7 @@ step() {
   echo "== $name rc=$rc"; tail -n 3 "$OUT/$name.log" | cut -c1-300
   if [ $rc -ne 0 ]; then echo "stopping"; exit $rc; fi
 }
-[ -n "$NO_FULL" ] || step bench_full 600 python bench.py --steps 20 --warmup 3
+[ -n "$NO_FULL" ] || step bench_full 600 python bench.py --full --steps 20 --warmup 3
 # LEGS: extra profiled legs beside the precisions: config3 (Transformer),
 # config4 (gammatone 32k frontend + forward) and window (predict.py windows:
 # 192 x 5 s windows per call), headline arithmetic
