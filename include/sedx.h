@@ -78,7 +78,7 @@ const char* sedx_last_error(const sedx_handle* h);
  * entry point's signature or a struct layout changes incompatibly; a caller
  * built against this header checks sedx_abi_version() == SEDX_ABI_VERSION
  * at load time ("ABI history"). */
-#define SEDX_ABI_VERSION 5
+#define SEDX_ABI_VERSION 6
 const char* sedx_version(void);
 int32_t sedx_abi_version(void);
 
@@ -464,6 +464,35 @@ sedx_status sedx_events_device(const float* d_x, int64_t n_clips, int64_t T, int
                                int32_t mode, double overlap_value, int32_t sample_duration,
                                int32_t* d_events, int64_t capacity, int64_t* d_info,
                                void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* Threshold calibration (utils/optimize_thresholds.py optimize_sed_thresholds):
+ * segment-based true / false positive and false negative counts of
+ * activity_detection (mode 0 above, always with the low threshold) for V
+ * threshold variants at once, without materialising event lists.  Every event
+ * (bgn, fin) of a (clip, class) series sets segments [bgn / segment_frames,
+ * ceil(fin / segment_frames)); the set is compared with the series' target
+ * mask: tp = |est & ref|, fp = |est & ~ref|, fn = |ref & ~est|, summed over
+ * clips.  `bad` counts the series where the reference raises IndexError (see
+ * the events entry points); such a series adds nothing to tp / fp / fn.
+ *   S = ceil(T / segment_frames) <= 64, segment_frames >= 1, 1 <= V <= 64;
+ *   anything else returns SEDX_EINVAL and sedx_last_error(NULL) names the
+ *   reason (a per-thread message of these handle-free entry points).
+ *   target  uint64 [n_clips][C]: bit s = class active in segment s
+ *   high / low  float64 [V][C] (host), rounded to float32 for the compares
+ *   counts  int64 [V][C][4] = (tp, fp, fn, bad), overwritten
+ * The device version is asynchronous on `stream` (the device that owns d_x
+ * must be current), zeroes d_counts itself and needs
+ * sedx_segment_counts_workspace_size bytes of workspace. */
+sedx_status sedx_segment_counts(const float* h_x, int64_t n_clips, int64_t T, int64_t C,
+                                const uint64_t* h_target, int64_t segment_frames, int64_t V,
+                                const double* high, const double* low,
+                                const int64_t* n_smooth, const int64_t* n_salt, int64_t* h_counts);
+sedx_status sedx_segment_counts_workspace_size(int64_t n_clips, int64_t T, int64_t C, int64_t V, size_t* bytes);
+sedx_status sedx_segment_counts_device(const float* d_x, int64_t n_clips, int64_t T, int64_t C,
+                                       const uint64_t* d_target, int64_t segment_frames, int64_t V,
+                                       const double* high, const double* low,
+                                       const int64_t* n_smooth, const int64_t* n_salt,
+                                       int64_t* d_counts, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * Input side: librosa.core.load(path, sr, mono=True) as

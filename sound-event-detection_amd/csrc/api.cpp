@@ -657,7 +657,7 @@ T* carve(char*& p, size_t n) {
 extern "C" {
 
 const char* sedx_version(void) {
-  return "sedx 0.5 (abi 5; gfx950: fp32 MFMA exact direct conv | fp32 Winograd F(4x4,3x3) + F(2x2,3x3) | "
+  return "sedx 0.6 (abi 6; gfx950: fp32 MFMA exact direct conv | fp32 Winograd F(4x4,3x3) + F(2x2,3x3) | "
          "3xbf16-split MFMA)";
 }
 
@@ -671,7 +671,11 @@ sedx_status sedx_set_precision(sedx_handle* h, int32_t mode) {
   return SEDX_OK;
 }
 
-const char* sedx_last_error(const sedx_handle* h) { return h ? h->err.c_str() : "null handle"; }
+const char* sedx_last_error(const sedx_handle* h) {
+  if (h) return h->err.c_str();
+  const char* seg = segment_error();                // handle-free segment-count entry points
+  return seg ? seg : "null handle";
+}
 
 sedx_status sedx_set_capture(sedx_handle* h, int32_t stage, float* d_buf, size_t bytes) {
   if (!h) return SEDX_EINVAL;
@@ -1614,6 +1618,47 @@ sedx_status sedx_events_device(const float* d_x, int64_t n_clips, int64_t T, int
               step, (int64_t)sample_duration, counts, slots, events_slot_cap(T), d_info, d_events,
               capacity};
   launch_events(a, mode, s);
+  if (take_launch_error() != hipSuccess) return SEDX_EHIP;
+  return hipGetLastError() == hipSuccess ? SEDX_OK : SEDX_EHIP;
+}
+
+sedx_status sedx_segment_counts_workspace_size(int64_t n_clips, int64_t T, int64_t C, int64_t V, size_t* bytes) {
+  if (!bytes || n_clips < 0 || T < 0 || C <= 0 || V < 1 || V > 64) return SEDX_EINVAL;
+  *bytes = calib_workspace_bytes(C, V);
+  return SEDX_OK;
+}
+
+sedx_status sedx_segment_counts_device(const float* d_x, int64_t n_clips, int64_t T, int64_t C,
+                                       const uint64_t* d_target, int64_t segment_frames, int64_t V,
+                                       const double* high, const double* low, const int64_t* n_smooth,
+                                       const int64_t* n_salt, int64_t* d_counts, void* d_workspace,
+                                       size_t workspace_bytes, void* stream) {
+  const sedx_status chk = segment_counts_check(n_clips, T, C, segment_frames, V);
+  if (chk != SEDX_OK) return chk;
+  if (!high || !low || !n_smooth || !n_salt || !d_counts || (n_clips > 0 && (!d_x || !d_target)))
+    return segment_fail("segment counts: null argument");
+  if (T > calib_max_frames())                       // a series' two bitmaps live in LDS
+    return segment_fail("segment counts: T = %lld frames, the device path holds at most %lld", (long long)T,
+                        (long long)calib_max_frames());
+  if (n_clips * C >= (int64_t(1) << 31)) return segment_fail("segment counts: too many series for one launch");
+  const size_t need = calib_workspace_bytes(C, V);
+  if (!d_workspace || workspace_bytes < need)
+    return segment_fail("segment counts: workspace too small: %zu < %zu bytes", workspace_bytes, need);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // thresholds and per-class parameters -> one packed block in the workspace, one copy
+  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+  const size_t o_hi = 0, o_lo = al(V * C * 8), o_ns = 2 * al(V * C * 8), o_salt = o_ns + al(C * 8);
+  std::vector<char> blob(o_salt + C * 8, 0);
+  std::memcpy(blob.data() + o_hi, high, V * C * 8);
+  std::memcpy(blob.data() + o_lo, low, V * C * 8);
+  std::memcpy(blob.data() + o_ns, n_smooth, C * 8);
+  std::memcpy(blob.data() + o_salt, n_salt, C * 8);
+  char* p = static_cast<char*>(d_workspace);
+  if (hipMemcpyAsync(p, blob.data(), blob.size(), hipMemcpyHostToDevice, s) != hipSuccess) return SEDX_EHIP;
+  CalibArgs a{d_x, n_clips, T, C, d_target, segment_frames, V,
+              reinterpret_cast<const double*>(p + o_hi), reinterpret_cast<const double*>(p + o_lo),
+              reinterpret_cast<const int64_t*>(p + o_ns), reinterpret_cast<const int64_t*>(p + o_salt), d_counts};
+  launch_segment_counts(a, s);
   if (take_launch_error() != hipSuccess) return SEDX_EHIP;
   return hipGetLastError() == hipSuccess ? SEDX_OK : SEDX_EHIP;
 }

@@ -391,4 +391,26 @@ int64_t events_max_frames();
 size_t events_workspace_bytes(int64_t n_series, int64_t T, int64_t C);
 void launch_events(const EventArgs& a, int mode, hipStream_t s);
 
+// ---- threshold calibration: segment-based tp / fp / fn counts (calib.hip) ----
+struct CalibArgs {
+  const float* x;            // [N][T][C] framewise probabilities
+  int64_t N, T, C;
+  const uint64_t* target;    // [N][C] reference segment masks (bit s = class active in segment s)
+  int64_t seg;               // frames per segment; ceil(T / seg) <= 64
+  int64_t V;                 // threshold variants, 1..64
+  const double* hi;          // [V][C] (rounded to float32 for the compare)
+  const double* lo;          // [V][C]
+  const int64_t* n_smooth;   // [C]
+  const int64_t* n_salt;     // [C]
+  int64_t* counts;           // [V][C][4] = (tp, fp, fn, bad)
+};
+size_t calib_workspace_bytes(int64_t C, int64_t V);
+int64_t calib_max_frames();
+void launch_segment_counts(const CalibArgs& a, hipStream_t s);
+// segments.cpp: the shape limits of the segment-count entry points and their
+// per-thread message (they take no handle)
+sedx_status segment_counts_check(int64_t n_clips, int64_t T, int64_t C, int64_t segment_frames, int64_t V);
+sedx_status segment_fail(const char* fmt, ...);
+const char* segment_error();
+
 }  // namespace sedx

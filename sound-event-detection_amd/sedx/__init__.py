@@ -3,7 +3,19 @@
 Public surface (mirrors the reference's hot-path API):
   sedx.models      Cnn_9layers_Gru_FrameAtt, Cnn_9layers_Transformer_FrameAtt (+ helpers)
   sedx.inference   predict_windows, inference_prob, gamma_features, events_from_framewise
+  sedx.calibrate   optimize_sed_thresholds, segment_counts, segment_metrics, segment_targets
   sedx.distributed clip sharding + framewise gather over RCCL
   sedx.synth       seeded synthetic weights / waveforms (bench, tests)
 """
 __version__ = '0.1.0'
+
+_CALIBRATE = ('optimize_sed_thresholds', 'segment_counts', 'segment_metrics', 'segment_targets')
+
+
+def __getattr__(name):
+    # the calibration entry points, importable from the package itself
+    # (resolved on first use: importing sedx stays free of torch)
+    if name in _CALIBRATE:
+        from . import calibrate
+        return getattr(calibrate, name)
+    raise AttributeError('module %r has no attribute %r' % (__name__, name))

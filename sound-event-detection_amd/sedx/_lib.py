@@ -21,6 +21,7 @@ EXPORTS = ['sedx_create', 'sedx_destroy', 'sedx_last_error', 'sedx_version', 'se
            'sedx_window_geometry', 'sedx_forward_windows', 'sedx_window_workspace_size',
            'sedx_events', 'sedx_set_profiling', 'sedx_stage_times', 'sedx_set_precision', 'sedx_set_pipelined',
            'sedx_forward_windows_vote', 'sedx_events_workspace_size', 'sedx_events_device',
+           'sedx_segment_counts', 'sedx_segment_counts_workspace_size', 'sedx_segment_counts_device',
            'sedx_forward_i16', 'sedx_wav_parse', 'sedx_wav_decode_mono', 'sedx_resample_size',
            'sedx_resample_workspace_size', 'sedx_resample', 'sedx_gamma_workspace_size',
            'sedx_set_tuning', 'sedx_set_capture', 'sedx_window_starts', 'sedx_merge_host', 'sedx_check_error',
@@ -43,7 +44,7 @@ RESAMPLE = {'kaiser_best': 0, 'kaiser_fast': 1}
 
 DRIVER = {'predict': 0, 'main_strong': 1}
 
-ABI_VERSION = 5   # include/sedx.h SEDX_ABI_VERSION
+ABI_VERSION = 6   # include/sedx.h SEDX_ABI_VERSION
 
 
 class SedxWindowSpec(ctypes.Structure):
@@ -123,6 +124,9 @@ def lib():
         'sedx_events_workspace_size': ([I64, I64, I64, PSZ], I32),
         'sedx_events_device': ([P, I64, I64, I64, P, P, I32, P, P, I32, F64, I32, P, I64, P, P, SZ, P],
                                I32),
+        'sedx_segment_counts': ([P, I64, I64, I64, P, I64, I64, P, P, P, P, P], I32),
+        'sedx_segment_counts_workspace_size': ([I64, I64, I64, I64, PSZ], I32),
+        'sedx_segment_counts_device': ([P, I64, I64, I64, P, I64, I64, P, P, P, P, P, P, SZ, P], I32),
         'sedx_set_profiling': ([P, I32], I32),
         'sedx_set_precision': ([P, I32], I32),
         'sedx_set_pipelined': ([P, I32], I32),

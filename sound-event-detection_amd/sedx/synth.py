@@ -94,3 +94,43 @@ def make_waveforms(batch, seconds=10.0, sample_rate=16000, seed=1234):
             x += amp * gate * np.sin(2 * np.pi * f * t + rng.uniform(0, 2 * np.pi))
         out[b] = x.astype(np.float32)
     return out
+
+
+def make_calibration_set(n_clips=8, frames=1000, classes=25, seed=0, segment_frames=100):
+    """Seeded framewise scores with a known ground truth for threshold
+    calibration (sedx.calibrate).  Every (clip, class) is active with
+    probability 0.35 with 1-2 events of 30-400 frames;
+    x = clip(0.12 + 0.45 truth + 0.9 movavg41(N(0,1)) + 0.03 N(0,1), 0, 1)
+    quantised to (floor(4096 x) + 0.5) / 4096 in float32 (no sample within 1e-4
+    of a multiple of 1/4096), and the last frame copies the one before (a run
+    that begins at the last frame is the reference's IndexError).
+
+    Returns {'framewise' float32 [N, T, C], 'truth' uint8 [N, T, C],
+    'targets' uint8 [N, S, C] (segment s active where a truth frame falls in
+    it), 'events' [(clip, class, bgn, fin)] truth events in frames}."""
+    rng = np.random.default_rng(seed)
+    N, T, C = n_clips, frames, classes
+    truth = np.zeros((N, T, C), np.uint8)
+    events = []
+    for n in range(N):
+        for k in range(C):
+            if rng.uniform() >= 0.35:
+                continue
+            for _ in range(int(rng.integers(1, 3))):
+                length = min(int(rng.integers(30, 401)), T)
+                b = int(rng.integers(0, T - length + 1))
+                truth[n, b:b + length, k] = 1
+                events.append((n, k, b, b + length))
+    slow = rng.standard_normal((N, T + 40, C))
+    cs = np.concatenate([np.zeros((N, 1, C)), np.cumsum(slow, axis=1)], axis=1)   # sequential sums: same on every host
+    mov = (cs[:, 41:] - cs[:, :-41]) / 41.0
+    x = np.clip(0.12 + 0.45 * truth + 0.9 * mov + 0.03 * rng.standard_normal((N, T, C)), 0.0, 1.0)
+    x = ((np.floor(4096.0 * x) + 0.5) / 4096.0).astype(np.float32)
+    if T > 1:
+        x[:, -1] = x[:, -2]
+    S = (T + segment_frames - 1) // segment_frames
+    pad = np.zeros((N, S * segment_frames, C), np.uint8)
+    pad[:, :T] = truth
+    targets = pad.reshape(N, S, segment_frames, C).max(axis=2)
+    return {'framewise': np.ascontiguousarray(x), 'truth': truth, 'targets': np.ascontiguousarray(targets),
+            'events': events}
