@@ -48,7 +48,15 @@ typedef enum {
 
 typedef enum {
   SEDX_MODEL_GRU_FRAMEATT = 0,          /* Cnn_9layers_Gru_FrameAtt   pytorch/models.py:564 */
-  SEDX_MODEL_TRANSFORMER_FRAMEATT = 1   /* Cnn_9layers_Transformer_FrameAtt  :981       */
+  SEDX_MODEL_TRANSFORMER_FRAMEATT = 1,  /* Cnn_9layers_Transformer_FrameAtt  :981       */
+  /* the other models on the same 9-layer CNN trunk.  "fc" heads: sigmoid(fc(x))
+   * per frame, x8 repeat, clipwise = max / mean over the frames */
+  SEDX_MODEL_CNN_FRAMEMAX = 2,          /* Cnn_9layers_FrameMax  :213-295: trunk, fc, max      */
+  SEDX_MODEL_CNN_FRAMEAVG = 3,          /* Cnn_9layers_FrameAvg  :298-380: trunk, fc, mean     */
+  SEDX_MODEL_CNN_FRAMEATT = 4,          /* Cnn_9layers_FrameAtt  :383-461: trunk, AttBlock     */
+  SEDX_MODEL_GRU_FRAMEAVG = 5,          /* Cnn_9layers_Gru_FrameAvg  :466-561: bi-GRU, fc, mean
+                                           (no padding to a multiple of 100, :551)            */
+  SEDX_MODEL_TRANSFORMER_FRAMEAVG = 6   /* Cnn_9layers_Transformer_FrameAvg  :880-978: MultiHead, fc, mean */
 } sedx_model;
 
 typedef enum { SEDX_FEATURE_LOGMEL = 0, SEDX_FEATURE_GAMMA = 1 } sedx_feature;
@@ -70,7 +78,10 @@ typedef struct {
 
 typedef struct sedx_handle sedx_handle;
 
-/* Model construction: replaces Model(...) (pytorch/models.py:565-623 / :982-1024). */
+/* Model construction: replaces Model(...) (pytorch/models.py:565-623 / :982-1024
+ * and the constructors of the other sedx_model values).  feature_type GAMMA is
+ * Cnn_9layers_Gru_FrameAtt's alone (Cnn_9layers_Gru_FrameAvg takes the argument
+ * and ignores it, :512-518); any other model_type with it is SEDX_EINVAL. */
 sedx_status sedx_create(const sedx_config* cfg, int device, sedx_handle** out);
 void sedx_destroy(sedx_handle* h);
 const char* sedx_last_error(const sedx_handle* h);
@@ -85,7 +96,10 @@ int32_t sedx_abi_version(void);
 /* One state_dict entry (host fp32; int64 scalars such as num_batches_tracked
  * are skipped by the caller).  Keys/shapes exactly as the reference
  * state_dict; unused keys (att_block.bn_att.*,
- * multihead.layer_norm.*) are accepted and ignored.  Replaces
+ * multihead.layer_norm.*) are accepted and ignored.  The key set is the
+ * model's own: the fc models take fc.weight [C, 512] / fc.bias [C] and no
+ * att_block.*, the CNN-only models no gru.* / multihead.*; a key of another
+ * family is SEDX_EKEY.  Replaces
  * model.load_state_dict(checkpoint['model']) (pytorch/predict.py:232-233). */
 sedx_status sedx_load_param(sedx_handle* h, const char* key, const float* h_data,
                             const int64_t* shape, int32_t ndim);
@@ -95,8 +109,9 @@ sedx_status sedx_finalize_weights(sedx_handle* h);
 
 /* Output geometry for a batch of waveforms of L samples (logmel) or of
  * feature matrices with T frames (gamma): frames of framewise_output
- * (after x8 interpolation and, GRU only, padding to a multiple of 100:
- * models.py:62-95, :678-681) and the sequence length after the CNN. */
+ * (after x8 interpolation and, Cnn_9layers_Gru_FrameAtt only, padding to a
+ * multiple of 100: models.py:62-95, :678-681) and the sequence length after
+ * the CNN. */
 sedx_status sedx_output_geometry(const sedx_handle* h, int64_t L_or_T, int64_t* out_frames,
                                  int64_t* seq_len);
 /* Bytes of device workspace sedx_forward* needs for (B, L). */
@@ -107,7 +122,10 @@ sedx_status sedx_workspace_size(const sedx_handle* h, int64_t B, int64_t L_or_T,
  *   d_wave       [B, L]                         (logmel models)
  *   d_framewise  [B, out_frames, classes_num]
  *   d_clipwise   [B, classes_num]
- *   d_embedding  GRU: [B, classes_num, seq_len]; Transformer: [B, 512, seq_len]
+ *   d_embedding  GRU_FRAMEATT, CNN_FRAMEATT: [B, classes_num, seq_len] (cla);
+ *                every other model: [B, 512, seq_len], the head's input
+ *                transposed (the GRU / MHA output; CNN_FRAMEMAX / CNN_FRAMEAVG:
+ *                block 4's frequency mean)
  *                (may be NULL)
  *   d_workspace  NULL = handle-owned cache, else >= sedx_workspace_size bytes. */
 sedx_status sedx_forward(sedx_handle* h, const float* d_wave, int64_t B, int64_t L,
@@ -403,7 +421,8 @@ sedx_status sedx_set_pipelined(sedx_handle* h, int32_t on);
  * on its stream at the stage boundaries; sedx_stage_times waits for them and
  * returns milliseconds for: 0 frontend, 1 conv1 of block 1, 2..8 the seven
  * implicit-GEMM convs (b1c2, b2c1, b2c2, b3c1, b3c2, b4c1, b4c2), 9 GRU / MHA
- * incl. projections, 10 AttBlock head, 11 pipeline wait: with
+ * incl. projections (~0 for the CNN-only models), 10 AttBlock / fc head,
+ * 11 pipeline wait: with
  * sedx_set_pipelined on, the stream's wait for the previous forward's conv
  * stack (between the frontend and block 1; ~0 otherwise), so stage 0 times
  * the frontend's own work.  on = 1: the last forward's times;
@@ -420,6 +439,7 @@ sedx_status sedx_set_pipelined(sedx_handle* h, int32_t on);
  *   3,5,7  conv1 of block 2..4        [items][T'][F'][C]
  *   8  block 4 + freq mean            [items][T/8][512]
  *   9  GRU / MHA output               [items][T/8][512]
+ *      (the head's input; CNN-only models: the same contents as stage 8)
  * stage < 0 or d_buf == NULL switches capture off. */
 sedx_status sedx_set_capture(sedx_handle* h, int32_t stage, float* d_buf, size_t bytes);
 sedx_status sedx_set_profiling(sedx_handle* h, int32_t on);

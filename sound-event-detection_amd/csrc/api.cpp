@@ -22,6 +22,10 @@ using namespace sedx;
 
 namespace {
 
+// a model = the CNN trunk, then a sequence layer, then a head
+enum SeqKind { SEQ_NONE = 0, SEQ_GRU = 1, SEQ_MHA = 2 };
+enum HeadKind { HEAD_ATT = 0, HEAD_FC_AVG = 1, HEAD_FC_MAX = 2 };
+
 struct Tensor {
   std::vector<int64_t> shape;
   std::vector<float> data;
@@ -84,7 +88,13 @@ struct sedx_handle {
   void* blob = nullptr;      // single device allocation for all packed weights
   size_t blob_bytes = 0;
   DevWeights w;
-  int nac = 64;              // rows of the att|cla projection (2C rounded up to 64)
+  // the model as a pair (sedx_create, model_parts): what follows the CNN
+  // trunk, and the head that reads its output
+  int seq = SEQ_GRU;
+  int head = HEAD_ATT;
+  bool pad100 = false;       // framewise padded to a multiple of 100 (Cnn_9layers_Gru_FrameAtt, models.py:678-681)
+  bool emb_cla = false;      // d_embedding is cla [B][C][T3] (models.py:683-686, :459), else the head's input transposed
+  int nac = 64;              // rows of the head projection: att|cla (2C) or fc (C), rounded up to 64
   int g_nfft = 0, g_nwin = 0, g_hop = 0;
   void* ws = nullptr;        // cached workspace
   size_t ws_bytes = 0;
@@ -254,7 +264,19 @@ struct DeviceGuard {
   }
 };
 
-bool is_gru(const sedx_handle* h) { return h->cfg.model_type == SEDX_MODEL_GRU_FRAMEATT; }
+// sedx_model -> (seq, head); false for an unknown model_type
+bool model_parts(int32_t model_type, int* seq, int* head) {
+  switch (model_type) {
+    case SEDX_MODEL_GRU_FRAMEATT: *seq = SEQ_GRU, *head = HEAD_ATT; return true;
+    case SEDX_MODEL_TRANSFORMER_FRAMEATT: *seq = SEQ_MHA, *head = HEAD_ATT; return true;
+    case SEDX_MODEL_CNN_FRAMEMAX: *seq = SEQ_NONE, *head = HEAD_FC_MAX; return true;
+    case SEDX_MODEL_CNN_FRAMEAVG: *seq = SEQ_NONE, *head = HEAD_FC_AVG; return true;
+    case SEDX_MODEL_CNN_FRAMEATT: *seq = SEQ_NONE, *head = HEAD_ATT; return true;
+    case SEDX_MODEL_GRU_FRAMEAVG: *seq = SEQ_GRU, *head = HEAD_FC_AVG; return true;
+    case SEDX_MODEL_TRANSFORMER_FRAMEAVG: *seq = SEQ_MHA, *head = HEAD_FC_AVG; return true;
+    default: return false;
+  }
+}
 
 void add_bn(std::map<std::string, std::vector<int64_t>>& e, const std::string& p, int64_t n) {
   for (const char* s : {".weight", ".bias", ".running_mean", ".running_var"}) e[p + s] = {n};
@@ -276,19 +298,24 @@ void build_expected(sedx_handle* h) {
     add_bn(e, p + ".bn2", ch[k]);
   }
   const int64_t C = h->cfg.classes_num;
-  e["att_block.att.weight"] = {C, 512, 1};
-  e["att_block.att.bias"] = {C};
-  e["att_block.cla.weight"] = {C, 512, 1};
-  e["att_block.cla.bias"] = {C};
-  add_bn(e, "att_block.bn_att", C);   // unused in forward (models.py:161-169)
-  if (is_gru(h)) {
+  if (h->head == HEAD_ATT) {
+    e["att_block.att.weight"] = {C, 512, 1};
+    e["att_block.att.bias"] = {C};
+    e["att_block.cla.weight"] = {C, 512, 1};
+    e["att_block.cla.bias"] = {C};
+    add_bn(e, "att_block.bn_att", C);   // unused in forward (models.py:161-169)
+  } else {
+    e["fc.weight"] = {C, 512};          // nn.Linear(512, classes_num) (models.py:247, :332, :503, :921)
+    e["fc.bias"] = {C};
+  }
+  if (h->seq == SEQ_GRU) {
     for (const char* s : {"", "_reverse"}) {
       e[std::string("gru.weight_ih_l0") + s] = {768, 512};
       e[std::string("gru.weight_hh_l0") + s] = {768, 256};
       e[std::string("gru.bias_ih_l0") + s] = {768};
       e[std::string("gru.bias_hh_l0") + s] = {768};
     }
-  } else {
+  } else if (h->seq == SEQ_MHA) {
     for (const char* n : {"w_qs", "w_ks", "w_vs", "fc"}) {
       e[std::string("multihead.") + n + ".weight"] = {512, 512};
       e[std::string("multihead.") + n + ".bias"] = {512};
@@ -312,7 +339,9 @@ Geometry geometry_from_T(const sedx_handle* h, int64_t T) {
   g.T3 = g.T2 / 2;
   g.fw_len = 8 * g.T3;
   g.out_frames = g.fw_len;
-  if (is_gru(h) && g.fw_len != 1000)   // pad_framewise_output(roundup) models.py:678-681
+  // pad_framewise_output(roundup) models.py:678-681: Cnn_9layers_Gru_FrameAtt
+  // alone (Cnn_9layers_Gru_FrameAvg returns the 8 T3 frames, :551)
+  if (h->pad100 && g.fw_len != 1000)
     g.out_frames = (g.fw_len % 100 == 0) ? g.fw_len : g.fw_len + 100 - g.fw_len % 100;
   return g;
 }
@@ -492,7 +521,10 @@ sedx_status run_body(sedx_handle* h, int64_t B, const Geometry& g, float* ws, co
     else
       launch_linear(a, M, 512, wf, n, bias, c, act, s);
   };
-  if (is_gru(h)) {
+  // the head's input [M][512]: the sequence layer's output, or (no sequence
+  // layer: no projection, no recurrence / MHA launch) the stage-8 buffer itself
+  const float* HI = h->seq == SEQ_NONE ? S : Hs;
+  if (h->seq == SEQ_GRU) {
     linear(S, w.w_ih, w.w_ih_x3, 1536, 128, w.b_ih, G, 0);
     if (h->gru_kernel == SEDX_GRU_KERNEL_SIMPLE)
       launch_gru(G, iB, (int)g.T3, w.whhT, w.bhh, Hs, s);
@@ -517,17 +549,21 @@ sedx_status run_body(sedx_handle* h, int64_t B, const Geometry& g, float* ws, co
                       // vs 0.51 ms in the timed region, profiles/r05t_*)
                       h->gru_handoff == SEDX_GRU_HANDOFF_SPREAD ||
                           (h->gru_handoff == SEDX_GRU_HANDOFF_AUTO && h->pipelined));
-  } else {
+  } else if (h->seq == SEQ_MHA) {
     linear(S, w.wqkv, w.wqkv_x3, 1536, 128, w.bqkv, G, 0);
     launch_mha(G, iB, (int)g.T3, O, s);
     linear(O, w.wfc, w.wfc_x3, 512, 128, w.bfc, Hs, 1);
   }
-  capture(h, 9, Hs, (size_t)M * 512, s);
+  capture(h, 9, HI, (size_t)M * 512, s);
   mark(h, 10, s);
-  linear(Hs, w.wac, w.wac_x3, h->nac, 64, w.bac, LG, 0);
-  launch_att_head(LG, iB, (int)g.T3, h->cfg.classes_num, h->nac, (int)g.out_frames, d_fw, d_clip,
-                  is_gru(h) ? d_emb : nullptr, s);
-  if (!is_gru(h) && d_emb) launch_transpose_btd(Hs, iB, (int)g.T3, 512, d_emb, s);
+  // head projection (att|cla rows or fc rows, zero-padded to nac), then its finish
+  linear(HI, w.wac, w.wac_x3, h->nac, 64, w.bac, LG, 0);
+  if (h->head == HEAD_ATT)
+    launch_att_head(LG, iB, (int)g.T3, h->cfg.classes_num, h->nac, (int)g.out_frames, d_fw, d_clip,
+                    h->emb_cla ? d_emb : nullptr, s);
+  else
+    launch_fc_head(LG, iB, (int)g.T3, h->cfg.classes_num, h->nac, h->head == HEAD_FC_MAX, d_fw, d_clip, s);
+  if (!h->emb_cla && d_emb) launch_transpose_btd(HI, iB, (int)g.T3, 512, d_emb, s);
   mark(h, 11, s);
   return launch_status(h);
 }
@@ -746,8 +782,8 @@ sedx_status sedx_check_error(sedx_handle* h) {
 sedx_status sedx_create(const sedx_config* cfg, int device, sedx_handle** out) {
   if (!cfg || !out) return SEDX_EINVAL;
   *out = nullptr;
-  if (cfg->model_type != SEDX_MODEL_GRU_FRAMEATT && cfg->model_type != SEDX_MODEL_TRANSFORMER_FRAMEATT)
-    return SEDX_EINVAL;
+  int seq = 0, head = 0;
+  if (!model_parts(cfg->model_type, &seq, &head)) return SEDX_EINVAL;
   if (cfg->mel_bins != 64) return SEDX_EINVAL;
   if (cfg->window_size != 256 && cfg->window_size != 512 && cfg->window_size != 1024) return SEDX_EINVAL;
   if (cfg->hop_size <= 0 || cfg->sample_rate <= 0 || cfg->classes_num <= 0 || cfg->classes_num > 256)
@@ -757,7 +793,11 @@ sedx_status sedx_create(const sedx_config* cfg, int device, sedx_handle** out) {
   sedx_handle* h = new sedx_handle();
   h->cfg = *cfg;
   h->device = device;
-  h->nac = ((2 * cfg->classes_num + 63) / 64) * 64;
+  h->seq = seq;
+  h->head = head;
+  h->pad100 = cfg->model_type == SEDX_MODEL_GRU_FRAMEATT;
+  h->emb_cla = head == HEAD_ATT && seq != SEQ_MHA;
+  h->nac = (((head == HEAD_ATT ? 2 : 1) * cfg->classes_num + 63) / 64) * 64;
   build_expected(h);
   *out = h;
   return SEDX_OK;
@@ -1008,7 +1048,7 @@ sedx_status sedx_finalize_weights(sedx_handle* h) {
       }
     return px;
   };
-  if (is_gru(h)) {
+  if (h->seq == SEQ_GRU) {
     w_ih.resize(1536 * 512);
     b_ih.resize(1536);
     whhT.resize(2 * 256 * 768);
@@ -1026,7 +1066,7 @@ sedx_status sedx_finalize_weights(sedx_handle* h) {
         for (int k = 0; k < 256; ++k) whhT[((size_t)d * 256 + k) * 768 + r] = whh[(size_t)r * 256 + k];
       whh_nat.insert(whh_nat.end(), whh.begin(), whh.end());
     }
-  } else {
+  } else if (h->seq == SEQ_MHA) {
     wqkv.resize(1536 * 512);
     bqkv.resize(1536);
     const char* nm[3] = {"w_qs", "w_ks", "w_vs"};
@@ -1039,8 +1079,14 @@ sedx_status sedx_finalize_weights(sedx_handle* h) {
     wfc = get("multihead.fc.weight");
     bfc = get("multihead.fc.bias");
   }
+  // head projection, rows zero-padded to nac: att | cla, or fc
   std::vector<float> wac((size_t)h->nac * 512, 0.f), bac(h->nac, 0.f);
-  {
+  if (h->head != HEAD_ATT) {
+    const auto& wf = get("fc.weight");
+    const auto& bf = get("fc.bias");
+    std::copy(wf.begin(), wf.end(), wac.begin());
+    std::copy(bf.begin(), bf.end(), bac.begin());
+  } else {
     const auto& wa = get("att_block.att.weight");
     const auto& ba = get("att_block.att.bias");
     const auto& wc = get("att_block.cla.weight");
@@ -1117,13 +1163,13 @@ sedx_status sedx_finalize_weights(sedx_handle* h) {
     add((void**)&W.wu[i], packed_wu[i].data(), packed_wu[i].size() * 4);
     if (!packed_wu43[i].empty()) add((void**)&W.wu43[i], packed_wu43[i].data(), packed_wu43[i].size() * 4);
   }
-  if (is_gru(h)) {
+  if (h->seq == SEQ_GRU) {
     add((void**)&W.w_ih, w_ih.data(), w_ih.size() * 4);
     add((void**)&W.b_ih, b_ih.data(), b_ih.size() * 4);
     add((void**)&W.whhT, whhT.data(), whhT.size() * 4);
     add((void**)&W.whh, whh_nat.data(), whh_nat.size() * 4);
     add((void**)&W.bhh, bhh.data(), bhh.size() * 4);
-  } else {
+  } else if (h->seq == SEQ_MHA) {
     add((void**)&W.wqkv, wqkv.data(), wqkv.size() * 4);
     add((void**)&W.bqkv, bqkv.data(), bqkv.size() * 4);
     add((void**)&W.wfc, wfc.data(), wfc.size() * 4);
@@ -1132,10 +1178,10 @@ sedx_status sedx_finalize_weights(sedx_handle* h) {
   add((void**)&W.wac, wac.data(), wac.size() * 4);
   add((void**)&W.bac, bac.data(), bac.size() * 4);
   std::vector<uint16_t> w_ih_x3, wqkv_x3, wfc_x3, wac_x3;
-  if (is_gru(h)) {
+  if (h->seq == SEQ_GRU) {
     w_ih_x3 = pack_linear_x3(w_ih, 1536, 512, 128);
     add(&W.w_ih_x3, w_ih_x3.data(), w_ih_x3.size() * 2);
-  } else {
+  } else if (h->seq == SEQ_MHA) {
     wqkv_x3 = pack_linear_x3(wqkv, 1536, 512, 128);
     wfc_x3 = pack_linear_x3(wfc, 512, 512, 128);
     add(&W.wqkv_x3, wqkv_x3.data(), wqkv_x3.size() * 2);

@@ -326,7 +326,12 @@ void launch_mha(const float* QKV, int B, int T, float* O, hipStream_t s);
 // AttBlock finish + framewise expansion.  logits [B][T][ldl] (0..C-1 att, C..2C-1 cla)
 void launch_att_head(const float* logits, int B, int T, int C, int ldl, int out_frames,
                      float* framewise, float* clipwise, float* emb_cla, hipStream_t s);
-// embedding for the Transformer model: E [B][T][D] -> emb [B][D][T]
+// fc head finish (models.py:284-288, :369-373): sigmoid of logits [B][T][ldl]
+// (columns 0..C-1), x8 frame repeat -> framewise [B][8T][C], clipwise [B][C] =
+// the max (max_pool) or the mean over the frames
+void launch_fc_head(const float* logits, int B, int T, int C, int ldl, bool max_pool, float* framewise,
+                    float* clipwise, hipStream_t s);
+// embedding of the 512-channel models: E [B][T][D] -> emb [B][D][T]
 void launch_transpose_btd(const float* E, int B, int T, int D, float* out, hipStream_t s);
 
 // ---- windowed drivers (windows.cpp) ---------------------------------------

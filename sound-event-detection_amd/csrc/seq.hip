@@ -9,6 +9,9 @@
 //   att_head_kernel AttBlock finish (clamp, exp, normalise over T, sigmoid,
 //                   weighted sum) + x8 frame repeat + GRU last-frame padding
 //                   (pytorch/models.py:161-175, :84-95, :65-81)
+//   fc_head_kernel  fc head finish of the FrameMax / FrameAvg models (sigmoid,
+//                   x8 frame repeat, max / mean over the frames)
+//                   (pytorch/models.py:284-288, :369-373)
 //   merge_plan_kernel  overlap-add of window predictions + avg_merge divisors (host plan)
 //                   (utils/utilities.py:405-446)
 #include "sedx_internal.h"
@@ -425,6 +428,77 @@ void launch_att_head(const float* logits, int B, int T, int C, int ldl, int out_
                      float* framewise, float* clipwise, float* emb_cla, hipStream_t s) {
   hipLaunchKernelGGL(att_head_kernel, dim3(B), dim3(256), 0, s, logits, T, C, ldl, out_frames,
                      framewise, clipwise, emb_cla);
+}
+
+// ---------------------------------------------------------------------------
+// fc head finish (pytorch/models.py:284-288 FrameMax, :369-373 FrameAvg,
+// :550-554, :967-971): framewise = sigmoid(fc logits) repeated x8, clipwise =
+// its max or mean over the frames.  One workgroup per clip, att_head_kernel's
+// shape: classes in chunks of 32, frames in staging chunks of 128; sigmoid of
+// a chunk lands in LDS once and the coalesced x8 framewise store and the
+// reduction both read it from there.  Thread = (class slot cs = tid / 8,
+// t-lane l = tid % 8) for the reduction.
+//   max:  the stored framewise values themselves (fmaxf of the LDS copies), so
+//         clipwise equals the framewise maximum bit for bit.
+//   mean: each of the T distinct values stands for 8 frames, so the mean over
+//         8T frames is their sum / T; summed in float64 (a T-long fp32 chain
+//         would round once per term) and rounded to fp32 once.
+// ---------------------------------------------------------------------------
+template <bool MAXP>
+__global__ __launch_bounds__(256) void fc_head_kernel(const float* __restrict__ logits, int T, int C, int ldl,
+                                                      float* __restrict__ fw, float* __restrict__ clip) {
+  constexpr int TC = 128;
+  __shared__ float s_p[TC][33];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int cs = tid >> 3, l = tid & 7;
+  const int cc = tid & 31, tq = tid >> 5;
+  const float* lg = logits + (int64_t)b * T * ldl;
+  const int64_t out_frames = 8 * (int64_t)T;
+  for (int c0 = 0; c0 < C; c0 += 32) {
+    const int nc = min(32, C - c0);
+    const bool act = cs < nc;
+    float mx = 0.0f;                              // sigmoid > 0
+    double sum = 0.0;
+    for (int t0 = 0; t0 < T; t0 += TC) {
+      const int nt = min(TC, T - t0);
+      __syncthreads();                            // the previous chunk's readers are done
+      if (cc < nc)
+        for (int t = tq; t < nt; t += 8)
+          s_p[t][cc] = 1.0f / (1.0f + expf(-lg[(int64_t)(t0 + t) * ldl + c0 + cc]));
+      __syncthreads();
+      if (act)
+        for (int t = l; t < nt; t += 8) {
+          const float v = s_p[t][cs];
+          if (MAXP)
+            mx = fmaxf(mx, v);
+          else
+            sum += (double)v;
+        }
+      if (cc < nc)
+        for (int fr = tq; fr < nt * 8; fr += 8)
+          fw[((int64_t)b * out_frames + 8 * (int64_t)t0 + fr) * C + c0 + cc] = s_p[fr >> 3][cc];
+    }
+    if (MAXP) {
+      mx = fmaxf(mx, __shfl_xor(mx, 1));
+      mx = fmaxf(mx, __shfl_xor(mx, 2));
+      mx = fmaxf(mx, __shfl_xor(mx, 4));
+      if (act && l == 0) clip[(int64_t)b * C + c0 + cs] = mx;
+    } else {
+      sum += __shfl_xor(sum, 1);
+      sum += __shfl_xor(sum, 2);
+      sum += __shfl_xor(sum, 4);
+      if (act && l == 0) clip[(int64_t)b * C + c0 + cs] = (float)(sum / (double)T);
+    }
+  }
+}
+
+void launch_fc_head(const float* logits, int B, int T, int C, int ldl, bool max_pool, float* framewise,
+                    float* clipwise, hipStream_t s) {
+  if (B <= 0 || T <= 0 || C <= 0 || ldl < C) return note_launch_error(hipErrorInvalidValue);
+  if (max_pool)
+    hipLaunchKernelGGL(fc_head_kernel<true>, dim3(B), dim3(256), 0, s, logits, T, C, ldl, framewise, clipwise);
+  else
+    hipLaunchKernelGGL(fc_head_kernel<false>, dim3(B), dim3(256), 0, s, logits, T, C, ldl, framewise, clipwise);
 }
 
 __global__ __launch_bounds__(256) void transpose_btd_kernel(const float* __restrict__ E, int T,

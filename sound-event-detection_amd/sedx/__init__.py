@@ -1,7 +1,10 @@
 """sedx — MI355X-native inference path of yazdayy/sound-event-detection.
 
 Public surface (mirrors the reference's hot-path API):
-  sedx.models      Cnn_9layers_Gru_FrameAtt, Cnn_9layers_Transformer_FrameAtt (+ helpers)
+  sedx.models      the seven 9-layer models: Cnn_9layers_Gru_FrameAtt,
+                   Cnn_9layers_Transformer_FrameAtt, Cnn_9layers_FrameMax,
+                   Cnn_9layers_FrameAvg, Cnn_9layers_FrameAtt, Cnn_9layers_Gru_FrameAvg,
+                   Cnn_9layers_Transformer_FrameAvg (+ helpers)
   sedx.inference   predict_windows, inference_prob, gamma_features, events_from_framewise
   sedx.calibrate   optimize_sed_thresholds, segment_counts, segment_metrics, segment_targets
   sedx.distributed clip sharding + framewise gather over RCCL

@@ -5,7 +5,11 @@ reference constructor ``(sample_rate, window_size, hop_size, mel_bins, fmin,
 fmax, classes_num, feature_type)``, ``forward(input, mixup_lambda=None,
 timeshift=False, spec_augment=True)`` and the exact state_dict keys/shapes
 (so ``model.load_state_dict(torch.load(path)['model'])`` works unchanged).
-The submodules are parameter containers; the whole eval-mode forward runs in
+The reference's five other models on the same 9-layer trunk
+(``Cnn_9layers_FrameMax``, ``Cnn_9layers_FrameAvg``, ``Cnn_9layers_FrameAtt``:
+seven constructor arguments, ``forward(input, mixup_lambda=None)``;
+``Cnn_9layers_Gru_FrameAvg``, ``Cnn_9layers_Transformer_FrameAvg``) follow the
+same rule.  The submodules are parameter containers; the whole eval-mode forward runs in
 libsedx (HIP kernels for gfx950) through the C ABI in include/sedx.h.  There
 is no CPU or eager-PyTorch fallback: a non-HIP input raises.
 
@@ -30,11 +34,16 @@ import torch.nn as nn
 from . import _lib
 from .stft import Spectrogram, LogmelFilterBank
 
-__all__ = ['Cnn_9layers_Gru_FrameAtt', 'Cnn_9layers_Transformer_FrameAtt', 'ConvBlock',
+__all__ = ['Cnn_9layers_Gru_FrameAtt', 'Cnn_9layers_Transformer_FrameAtt',
+           'Cnn_9layers_FrameMax', 'Cnn_9layers_FrameAvg', 'Cnn_9layers_FrameAtt',
+           'Cnn_9layers_Gru_FrameAvg', 'Cnn_9layers_Transformer_FrameAvg', 'ConvBlock',
            'AttBlock', 'MultiHead', 'interpolate', 'pad_framewise_output', 'roundup',
            'init_layer', 'init_bn', 'init_gru']
 
-MODEL_IDS = {'Cnn_9layers_Gru_FrameAtt': 0, 'Cnn_9layers_Transformer_FrameAtt': 1}
+# sedx_model (include/sedx.h)
+MODEL_IDS = {'Cnn_9layers_Gru_FrameAtt': 0, 'Cnn_9layers_Transformer_FrameAtt': 1,
+             'Cnn_9layers_FrameMax': 2, 'Cnn_9layers_FrameAvg': 3, 'Cnn_9layers_FrameAtt': 4,
+             'Cnn_9layers_Gru_FrameAvg': 5, 'Cnn_9layers_Transformer_FrameAvg': 6}
 FEATURE_IDS = {'logmel': 0, 'gamma': 1}
 
 
@@ -234,9 +243,15 @@ class _HandleCache(dict):
 
 
 class _SedModel(nn.Module):
-    """Shared construction + native forward for the two hot-path models."""
+    """Shared construction (the 9-layer CNN trunk) + native forward of every
+    model class below.  ``classes_num`` is the class count of the outputs and
+    of the native handle."""
 
     _model_name = None
+    # 'embedding' is cla (batch, classes, seq) for the AttBlock models that
+    # return it (models.py:459, :686); every other model returns the head's
+    # 512-channel input (batch, 512, seq)
+    _embedding_cla = False
 
     def __init__(self, sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num,
                  feature_type='logmel'):
@@ -426,7 +441,7 @@ class _SedModel(nn.Module):
         dev = x.device
         fw = torch.empty((B, fr.value, C), dtype=torch.float32, device=dev)
         clip = torch.empty((B, C), dtype=torch.float32, device=dev)
-        emb_shape = (B, C, sl.value) if self._model_name == 'Cnn_9layers_Gru_FrameAtt' else (B, 512, sl.value)
+        emb_shape = (B, C, sl.value) if self._embedding_cla else (B, 512, sl.value)
         emb = torch.empty(emb_shape, dtype=torch.float32, device=dev)
         wsz = ctypes.c_size_t()
         _lib.check(L.sedx_workspace_size(nat.h, B, length, ctypes.byref(wsz)), nat.h, 'workspace_size')
@@ -442,6 +457,7 @@ class _SedModel(nn.Module):
 class Cnn_9layers_Gru_FrameAtt(_SedModel):
     """pytorch/models.py:564-688."""
     _model_name = 'Cnn_9layers_Gru_FrameAtt'
+    _embedding_cla = True
 
     def __init__(self, sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num,
                  feature_type):
@@ -466,3 +482,86 @@ class Cnn_9layers_Transformer_FrameAtt(_SedModel):
         self.multihead = MultiHead(8, 512, 64, 64, 0.2)
         self.att_block = AttBlock(n_in=512, n_out=classes_num, activation='sigmoid')
         init_bn(self.bn0)
+
+
+class _CnnOnlyModel(_SedModel):
+    """The CNN-only classes: seven constructor arguments (no feature_type,
+    always logmel) and ``forward(input, mixup_lambda=None)``
+    (models.py:214-215, :255)."""
+
+    def __init__(self, sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num):
+        super().__init__(sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num,
+                         'logmel')
+
+    def forward(self, input, mixup_lambda=None):
+        return super().forward(input, mixup_lambda=mixup_lambda)
+
+
+class Cnn_9layers_FrameMax(_CnnOnlyModel):
+    """pytorch/models.py:213-295: sigmoid(fc) per frame, clipwise = max over
+    the frames; embedding = block 4's frequency mean."""
+    _model_name = 'Cnn_9layers_FrameMax'
+
+    def __init__(self, sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num):
+        super().__init__(sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num)
+        self.fc = nn.Linear(512, classes_num, bias=True)
+        init_bn(self.bn0)
+        init_layer(self.fc)
+
+
+class Cnn_9layers_FrameAvg(_CnnOnlyModel):
+    """pytorch/models.py:298-380: as FrameMax with clipwise = mean over the frames."""
+    _model_name = 'Cnn_9layers_FrameAvg'
+
+    def __init__(self, sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num):
+        super().__init__(sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num)
+        self.fc = nn.Linear(512, classes_num, bias=True)
+        init_bn(self.bn0)
+        init_layer(self.fc)
+
+
+class Cnn_9layers_FrameAtt(_CnnOnlyModel):
+    """pytorch/models.py:383-461.  The reference builds ``AttBlock(n_out=25)``
+    whatever ``classes_num`` is (:416), so the model has 25 classes: the
+    state_dict, the native handle and the outputs are 25-class, and
+    ``classes_num`` reads 25."""
+    _model_name = 'Cnn_9layers_FrameAtt'
+    _embedding_cla = True
+
+    def __init__(self, sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num):
+        super().__init__(sample_rate, window_size, hop_size, mel_bins, fmin, fmax, 25)
+        self.att_block = AttBlock(n_in=512, n_out=25, activation='sigmoid')
+        init_bn(self.bn0)
+
+
+class Cnn_9layers_Gru_FrameAvg(_SedModel):
+    """pytorch/models.py:466-561: bi-GRU, sigmoid(fc), mean; the framewise
+    output is the 8 * seq_len frames (no padding to a multiple of 100, :551).
+    ``feature_type`` is accepted and ignored, as in the reference (:512-518:
+    no gamma branch)."""
+    _model_name = 'Cnn_9layers_Gru_FrameAvg'
+
+    def __init__(self, sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num,
+                 feature_type):
+        super().__init__(sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num,
+                         'logmel')
+        self.gru = nn.GRU(input_size=512, hidden_size=256, num_layers=1, bias=True,
+                          batch_first=True, bidirectional=True)
+        self.fc = nn.Linear(512, classes_num, bias=True)
+        init_bn(self.bn0)
+        init_gru(self.gru)
+        init_layer(self.fc)
+
+
+class Cnn_9layers_Transformer_FrameAvg(_SedModel):
+    """pytorch/models.py:880-978: MultiHead, sigmoid(fc), mean (always logmel)."""
+    _model_name = 'Cnn_9layers_Transformer_FrameAvg'
+
+    def __init__(self, sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num,
+                 feature_type):
+        super().__init__(sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num,
+                         'logmel')
+        self.multihead = MultiHead(8, 512, 64, 64, 0.2)
+        self.fc = nn.Linear(512, classes_num, bias=True)
+        init_bn(self.bn0)
+        init_layer(self.fc)

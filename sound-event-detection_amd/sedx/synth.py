@@ -7,7 +7,9 @@ the golden fixtures under ``tests/golden/`` never need to store the 24.7 MB
 state_dict: tests regenerate it from the seed.
 
 Keys/shapes follow the reference state_dict (SURVEY.md Appendix A;
-``pytorch/models.py:564-624`` GRU model, ``:981-1027`` Transformer model).
+``pytorch/models.py:564-624`` GRU model, ``:981-1027`` Transformer model;
+the five other 9-layer models: ``:213-250``, ``:298-338``, ``:383-421``,
+``:466-510``, ``:880-927``).
 Only the learnable tensors and BN statistics are produced here; the frontend
 buffers (``spectrogram_extractor.stft.conv_{real,imag}.weight``,
 ``logmel_extractor.melW``) come from the model constructors.
@@ -32,11 +34,39 @@ def _bn(rng, prefix, n, mean_range=(-1.0, 1.0), var_range=(0.5, 2.0)):
     }
 
 
+# model -> (sequence layer, head): what follows the CNN trunk
+MODEL_PARTS = {
+    'Cnn_9layers_Gru_FrameAtt': ('gru', 'att'),
+    'Cnn_9layers_Transformer_FrameAtt': ('mha', 'att'),
+    'Cnn_9layers_FrameMax': (None, 'fc'),
+    'Cnn_9layers_FrameAvg': (None, 'fc'),
+    'Cnn_9layers_FrameAtt': (None, 'att'),
+    'Cnn_9layers_Gru_FrameAvg': ('gru', 'fc'),
+    'Cnn_9layers_Transformer_FrameAvg': ('mha', 'fc'),
+}
+# the weight seed of every model's golden fixtures (tests/golden/)
+GOLDEN_SEEDS = {
+    'Cnn_9layers_Gru_FrameAtt': 0,
+    'Cnn_9layers_Transformer_FrameAtt': 1,
+    'Cnn_9layers_FrameMax': 2,
+    'Cnn_9layers_FrameAvg': 3,
+    'Cnn_9layers_FrameAtt': 4,
+    'Cnn_9layers_Gru_FrameAvg': 5,
+    'Cnn_9layers_Transformer_FrameAvg': 6,
+}
+
+
 def make_state_dict(model_type, classes_num=25, seed=0):
-    """Return {key: np.ndarray} for the non-frontend parameters of
-    ``Cnn_9layers_Gru_FrameAtt`` or ``Cnn_9layers_Transformer_FrameAtt``."""
-    if model_type not in ('Cnn_9layers_Gru_FrameAtt', 'Cnn_9layers_Transformer_FrameAtt'):
+    """Return {key: np.ndarray} for the non-frontend parameters of one of the
+    seven 9-layer models (``MODEL_PARTS``).  Draw order: the trunk, the
+    sequence layer's tensors, the head's (so two models with one seed share
+    every tensor up to the first that differs).  ``Cnn_9layers_FrameAtt``'s
+    AttBlock has 25 classes whatever ``classes_num`` is (models.py:416)."""
+    if model_type not in MODEL_PARTS:
         raise ValueError('unknown model_type %r' % model_type)
+    seq, head = MODEL_PARTS[model_type]
+    if model_type == 'Cnn_9layers_FrameAtt':
+        classes_num = 25
     rng = np.random.default_rng(seed)
     sd = {}
     # bn0 normalises log-mel dB values (models.py:607,642-644); realistic stats
@@ -47,7 +77,7 @@ def make_state_dict(model_type, classes_num=25, seed=0):
         sd[p + '.conv2.weight'] = _xavier_uniform(rng, (cout, cout, 3, 3), cout * 9, cout * 9)
         sd.update(_bn(rng, p + '.bn1', cout))
         sd.update(_bn(rng, p + '.bn2', cout))
-    if model_type == 'Cnn_9layers_Gru_FrameAtt':
+    if seq == 'gru':
         # init_gru (models.py:35-60): U(+-sqrt(3/fan_in)) per gate block; small
         # random biases so the bias paths are exercised.
         for sfx in ('', '_reverse'):
@@ -57,7 +87,7 @@ def make_state_dict(model_type, classes_num=25, seed=0):
             sd['gru.weight_hh_l0' + sfx] = rng.uniform(-b_hh, b_hh, (768, 256)).astype(np.float32)
             sd['gru.bias_ih_l0' + sfx] = rng.uniform(-0.1, 0.1, 768).astype(np.float32)
             sd['gru.bias_hh_l0' + sfx] = rng.uniform(-0.1, 0.1, 768).astype(np.float32)
-    else:
+    elif seq == 'mha':
         # MultiHead init (models.py:835-852): normal(0, sqrt(2/(d_model+d_k)))
         std_qkv = np.sqrt(2.0 / (512 + 64))
         for nm in ('w_qs', 'w_ks', 'w_vs'):
@@ -68,6 +98,12 @@ def make_state_dict(model_type, classes_num=25, seed=0):
         std_fc = np.sqrt(2.0 / (512 + 512))
         sd['multihead.fc.weight'] = rng.normal(0, std_fc, (512, 512)).astype(np.float32)
         sd['multihead.fc.bias'] = rng.uniform(-0.05, 0.05, 512).astype(np.float32)
+    if head == 'fc':
+        # nn.Linear(512, classes_num) with init_layer's xavier weight
+        # (models.py:247, :253); a negative bias like cla's below
+        sd['fc.weight'] = _xavier_uniform(rng, (classes_num, 512), 512, classes_num)
+        sd['fc.bias'] = rng.uniform(-0.5, 0.0, classes_num).astype(np.float32)
+        return sd
     sd['att_block.att.weight'] = _xavier_uniform(rng, (classes_num, 512, 1), 512, classes_num)
     sd['att_block.att.bias'] = rng.uniform(-0.1, 0.1, classes_num).astype(np.float32)
     sd['att_block.cla.weight'] = _xavier_uniform(rng, (classes_num, 512, 1), 512, classes_num)
