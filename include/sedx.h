@@ -56,7 +56,14 @@ typedef enum {
   SEDX_MODEL_CNN_FRAMEATT = 4,          /* Cnn_9layers_FrameAtt  :383-461: trunk, AttBlock     */
   SEDX_MODEL_GRU_FRAMEAVG = 5,          /* Cnn_9layers_Gru_FrameAvg  :466-561: bi-GRU, fc, mean
                                            (no padding to a multiple of 100, :551)            */
-  SEDX_MODEL_TRANSFORMER_FRAMEAVG = 6   /* Cnn_9layers_Transformer_FrameAvg  :880-978: MultiHead, fc, mean */
+  SEDX_MODEL_TRANSFORMER_FRAMEAVG = 6,  /* Cnn_9layers_Transformer_FrameAvg  :880-978: MultiHead, fc, mean */
+  /* the same trunk, then the 3-block Conformer encoder (models_2020/conformer/:
+   * ConformerEncoder(512, adim 144, aheads 4, elayers 3, eunits 576, kernel 7))
+   * and a 144-wide head; framewise padded to a multiple of 100 with its last
+   * frame (:1359-1360, :1571-1572).  fp32 in every precision mode. */
+  SEDX_MODEL_CONFORMER_FRAMEATT = 7,    /* Cnn_9layers_Conformer_FrameAtt  :1189-1410: AttBlock(144, 25) */
+  SEDX_MODEL_CONFORMER_FRAMEAVG = 8     /* Cnn_9layers_Conformer_FrameAvg  :1412-1625: fc(144), mean over
+                                           the padded frames (:1575)                                   */
 } sedx_model;
 
 typedef enum { SEDX_FEATURE_LOGMEL = 0, SEDX_FEATURE_GAMMA = 1 } sedx_feature;
@@ -99,7 +106,14 @@ int32_t sedx_abi_version(void);
  * multihead.layer_norm.*) are accepted and ignored.  The key set is the
  * model's own: the fc models take fc.weight [C, 512] / fc.bias [C] and no
  * att_block.*, the CNN-only models no gru.* / multihead.*; a key of another
- * family is SEDX_EKEY.  Replaces
+ * family is SEDX_EKEY.  The Conformer models take encoder.input_layer.{0,1}.*,
+ * encoder.input_layer.4.pe [1, 5000, 144] (loaded, not recomputed),
+ * encoder.conformer_blocks.{0,1,2}.* (ffn1 / ffn2 feed_forward_module.{0,1,4},
+ * mhsa.{r_w_bias, r_r_bias, qkv_net, o_net, layer_norm, pos_emb.inv_freq,
+ * r_net}, conv.conv.{0,1.conv,3.conv,5,8.conv}, norm) and a 144-wide head
+ * (att_block.{att,cla}.weight [25, 144, 1] or fc.weight [C, 144]);
+ * classifier.* and linear_emb.* (unused at inference) are accepted and
+ * ignored.  Replaces
  * model.load_state_dict(checkpoint['model']) (pytorch/predict.py:232-233). */
 sedx_status sedx_load_param(sedx_handle* h, const char* key, const float* h_data,
                             const int64_t* shape, int32_t ndim);
@@ -109,8 +123,8 @@ sedx_status sedx_finalize_weights(sedx_handle* h);
 
 /* Output geometry for a batch of waveforms of L samples (logmel) or of
  * feature matrices with T frames (gamma): frames of framewise_output
- * (after x8 interpolation and, Cnn_9layers_Gru_FrameAtt only, padding to a
- * multiple of 100: models.py:62-95, :678-681) and the sequence length after
+ * (after x8 interpolation and, Cnn_9layers_Gru_FrameAtt and the Conformer
+ * models only, padding to a multiple of 100: models.py:62-95, :678-681) and the sequence length after
  * the CNN. */
 sedx_status sedx_output_geometry(const sedx_handle* h, int64_t L_or_T, int64_t* out_frames,
                                  int64_t* seq_len);
@@ -125,8 +139,11 @@ sedx_status sedx_workspace_size(const sedx_handle* h, int64_t B, int64_t L_or_T,
  *   d_embedding  GRU_FRAMEATT, CNN_FRAMEATT: [B, classes_num, seq_len] (cla);
  *                every other model: [B, 512, seq_len], the head's input
  *                transposed (the GRU / MHA output; CNN_FRAMEMAX / CNN_FRAMEAVG:
- *                block 4's frequency mean)
+ *                block 4's frequency mean); the Conformer models:
+ *                [B, 144, seq_len], the encoder output transposed
  *                (may be NULL)
+ * The Conformer models hold at most 5000 sequence frames (the positional
+ * table): beyond, the forward, geometry and workspace queries are SEDX_EINVAL.
  *   d_workspace  NULL = handle-owned cache, else >= sedx_workspace_size bytes. */
 sedx_status sedx_forward(sedx_handle* h, const float* d_wave, int64_t B, int64_t L,
                          float* d_framewise, float* d_clipwise, float* d_embedding,
@@ -421,7 +438,7 @@ sedx_status sedx_set_pipelined(sedx_handle* h, int32_t on);
  * on its stream at the stage boundaries; sedx_stage_times waits for them and
  * returns milliseconds for: 0 frontend, 1 conv1 of block 1, 2..8 the seven
  * implicit-GEMM convs (b1c2, b2c1, b2c2, b3c1, b3c2, b4c1, b4c2), 9 GRU / MHA
- * incl. projections (~0 for the CNN-only models), 10 AttBlock / fc head,
+ * incl. projections (~0 for the CNN-only models; the whole Conformer encoder), 10 AttBlock / fc head,
  * 11 pipeline wait: with
  * sedx_set_pipelined on, the stream's wait for the previous forward's conv
  * stack (between the frontend and block 1; ~0 otherwise), so stage 0 times
@@ -439,7 +456,14 @@ sedx_status sedx_set_pipelined(sedx_handle* h, int32_t on);
  *   3,5,7  conv1 of block 2..4        [items][T'][F'][C]
  *   8  block 4 + freq mean            [items][T/8][512]
  *   9  GRU / MHA output               [items][T/8][512]
- *      (the head's input; CNN-only models: the same contents as stage 8)
+ *      (the head's input; CNN-only models: the same contents as stage 8;
+ *      Conformer models: the encoder output [items][T/8][144])
+ * Conformer models only, capture ids beyond the timing stages (all
+ * [items][T/8][144]; SEDX_N_STAGES and the timed stages are unchanged):
+ *   20          the encoder's input layer output
+ *   21 + 4b + j block b = 0..2: j = 0 after ffn1, 1 after mhsa, 2 after the
+ *               conv module, 3 the block's output (after ffn2 and its norm);
+ *               32 is the same tensor as 9
  * stage < 0 or d_buf == NULL switches capture off. */
 sedx_status sedx_set_capture(sedx_handle* h, int32_t stage, float* d_buf, size_t bytes);
 sedx_status sedx_set_profiling(sedx_handle* h, int32_t on);

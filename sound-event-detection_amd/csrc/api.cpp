@@ -23,12 +23,40 @@ using namespace sedx;
 namespace {
 
 // a model = the CNN trunk, then a sequence layer, then a head
-enum SeqKind { SEQ_NONE = 0, SEQ_GRU = 1, SEQ_MHA = 2 };
+enum SeqKind { SEQ_NONE = 0, SEQ_GRU = 1, SEQ_MHA = 2, SEQ_CONFORMER = 3 };
 enum HeadKind { HEAD_ATT = 0, HEAD_FC_AVG = 1, HEAD_FC_MAX = 2 };
 
 struct Tensor {
   std::vector<int64_t> shape;
   std::vector<float> data;
+};
+
+// one ConformerBlock (conformer_block.py:8-24); every matrix in its
+// state_dict layout [out][in]
+struct CfBlockWeights {
+  float* ffn_g[2] = {};    // ffn1 / ffn2: LayerNorm weight, bias [144]
+  float* ffn_be[2] = {};
+  float* ffn_w1[2] = {};   // [576][144]
+  float* ffn_b1[2] = {};
+  float* ffn_w2[2] = {};   // [144][576]
+  float* ffn_b2[2] = {};
+  float* att_g = nullptr;  // mhsa.layer_norm
+  float* att_be = nullptr;
+  float* wqkv = nullptr;   // [432][144]
+  float* wo = nullptr;     // [144][144]
+  float* rnet = nullptr;   // [144][144]
+  float* rwb = nullptr;    // [4][36]
+  float* rrb = nullptr;
+  float* cv_g = nullptr;   // conv module's LayerNorm
+  float* cv_be = nullptr;
+  float* pw1_w = nullptr;  // [288][144]
+  float* pw1_b = nullptr;
+  float* dw_wt = nullptr;  // [7][144]: depthwise taps x BN scale, tap-major
+  float* dw_b = nullptr;   // [144]: folded bias
+  float* pw2_w = nullptr;  // [144][144]
+  float* pw2_b = nullptr;
+  float* norm_g = nullptr; // the block's final LayerNorm
+  float* norm_be = nullptr;
 };
 
 struct DevWeights {
@@ -63,8 +91,16 @@ struct DevWeights {
   float* bqkv = nullptr;
   float* wfc = nullptr;    // [512][512]
   float* bfc = nullptr;
-  float* wac = nullptr;    // [nac][512]
+  float* wac = nullptr;    // [nac][hw]
   float* bac = nullptr;
+  // Conformer encoder (fp32 in every mode)
+  float* cf_in_w = nullptr;      // [144][512]
+  float* cf_in_b = nullptr;
+  float* cf_in_g = nullptr;      // input layer's LayerNorm
+  float* cf_in_be = nullptr;
+  float* cf_pe = nullptr;        // [5000][144] (the state_dict's buffer)
+  float* cf_inv_freq = nullptr;  // [3][72]
+  CfBlockWeights cf[CF_BLOCKS];
   // x3 (split bf16) packs of the linear weights for linear_x3.hip
   void* w_ih_x3 = nullptr;
   void* wqkv_x3 = nullptr;
@@ -94,6 +130,7 @@ struct sedx_handle {
   int head = HEAD_ATT;
   bool pad100 = false;       // framewise padded to a multiple of 100 (Cnn_9layers_Gru_FrameAtt, models.py:678-681)
   bool emb_cla = false;      // d_embedding is cla [B][C][T3] (models.py:683-686, :459), else the head's input transposed
+  int hw = 512;              // width of the head's input: 512, or 144 after the Conformer encoder
   int nac = 64;              // rows of the head projection: att|cla (2C) or fc (C), rounded up to 64
   int g_nfft = 0, g_nwin = 0, g_hop = 0;
   void* ws = nullptr;        // cached workspace
@@ -274,9 +311,20 @@ bool model_parts(int32_t model_type, int* seq, int* head) {
     case SEDX_MODEL_CNN_FRAMEATT: *seq = SEQ_NONE, *head = HEAD_ATT; return true;
     case SEDX_MODEL_GRU_FRAMEAVG: *seq = SEQ_GRU, *head = HEAD_FC_AVG; return true;
     case SEDX_MODEL_TRANSFORMER_FRAMEAVG: *seq = SEQ_MHA, *head = HEAD_FC_AVG; return true;
+    case SEDX_MODEL_CONFORMER_FRAMEATT: *seq = SEQ_CONFORMER, *head = HEAD_ATT; return true;
+    case SEDX_MODEL_CONFORMER_FRAMEAVG: *seq = SEQ_CONFORMER, *head = HEAD_FC_AVG; return true;
     default: return false;
   }
 }
+
+// keys of modules the Conformer models build and never call at inference
+// (models.py:1290-1300, :1505-1515): accepted with any shape, not stored
+bool ignored_key(const sedx_handle* h, const std::string& k) {
+  if (h->seq != SEQ_CONFORMER) return false;
+  return k == "classifier.weight" || k == "classifier.bias" || k == "linear_emb.weight" || k == "linear_emb.bias";
+}
+
+std::string cf_block_key(int b) { return "encoder.conformer_blocks." + std::to_string(b) + "."; }
 
 void add_bn(std::map<std::string, std::vector<int64_t>>& e, const std::string& p, int64_t n) {
   for (const char* s : {".weight", ".bias", ".running_mean", ".running_var"}) e[p + s] = {n};
@@ -299,13 +347,13 @@ void build_expected(sedx_handle* h) {
   }
   const int64_t C = h->cfg.classes_num;
   if (h->head == HEAD_ATT) {
-    e["att_block.att.weight"] = {C, 512, 1};
+    e["att_block.att.weight"] = {C, h->hw, 1};
     e["att_block.att.bias"] = {C};
-    e["att_block.cla.weight"] = {C, 512, 1};
+    e["att_block.cla.weight"] = {C, h->hw, 1};
     e["att_block.cla.bias"] = {C};
     add_bn(e, "att_block.bn_att", C);   // unused in forward (models.py:161-169)
   } else {
-    e["fc.weight"] = {C, 512};          // nn.Linear(512, classes_num) (models.py:247, :332, :503, :921)
+    e["fc.weight"] = {C, h->hw};        // nn.Linear(512, classes_num) (models.py:247, :332, :503, :921; 144: :1500)
     e["fc.bias"] = {C};
   }
   if (h->seq == SEQ_GRU) {
@@ -322,10 +370,48 @@ void build_expected(sedx_handle* h) {
     }
     e["multihead.layer_norm.weight"] = {512};   // unused in forward (models.py:853-877)
     e["multihead.layer_norm.bias"] = {512};
+  } else if (h->seq == SEQ_CONFORMER) {
+    auto ln = [&](const std::string& p) { e[p + ".weight"] = {CF_D}, e[p + ".bias"] = {CF_D}; };
+    auto lin = [&](const std::string& p, int64_t out, int64_t in, bool bias) {
+      e[p + ".weight"] = {out, in};
+      if (bias) e[p + ".bias"] = {out};
+    };
+    lin("encoder.input_layer.0", CF_D, 512, true);
+    ln("encoder.input_layer.1");
+    e["encoder.input_layer.4.pe"] = {1, CF_MAX_T, CF_D};
+    for (int b = 0; b < CF_BLOCKS; ++b) {
+      const std::string p = cf_block_key(b);
+      for (const char* f : {"ffn1", "ffn2"}) {
+        const std::string q = p + f + ".feed_forward_module.";
+        ln(q + "0");
+        lin(q + "1", CF_FF, CF_D, true);
+        lin(q + "4", CF_D, CF_FF, true);
+      }
+      e[p + "mhsa.r_w_bias"] = {4, CF_D / 4};
+      e[p + "mhsa.r_r_bias"] = {4, CF_D / 4};
+      lin(p + "mhsa.qkv_net", 3 * CF_D, CF_D, false);
+      lin(p + "mhsa.o_net", CF_D, CF_D, false);
+      ln(p + "mhsa.layer_norm");
+      e[p + "mhsa.pos_emb.inv_freq"] = {CF_D / 2};
+      lin(p + "mhsa.r_net", CF_D, CF_D, false);
+      ln(p + "conv.conv.0");
+      e[p + "conv.conv.1.conv.weight"] = {2 * CF_D, CF_D, 1};
+      e[p + "conv.conv.1.conv.bias"] = {2 * CF_D};
+      e[p + "conv.conv.3.conv.weight"] = {CF_D, 1, 7};
+      e[p + "conv.conv.3.conv.bias"] = {CF_D};
+      add_bn(e, p + "conv.conv.5", CF_D);
+      e[p + "conv.conv.8.conv.weight"] = {CF_D, CF_D, 1};
+      e[p + "conv.conv.8.conv.bias"] = {CF_D};
+      ln(p + "norm");
+    }
   }
 }
 
 int64_t conv_T(const sedx_handle* h, int64_t L) { return L / h->cfg.hop_size + 1; }
+
+// the Conformer encoder's positional table has CF_MAX_T rows; the reference
+// fails on a longer sequence too (embedding.py:30: the add does not broadcast)
+bool seq_too_long(const sedx_handle* h, int64_t T3) { return h->seq == SEQ_CONFORMER && T3 > CF_MAX_T; }
 
 struct Geometry {
   int64_t T, T1, T2, T3, fw_len, out_frames;
@@ -340,7 +426,8 @@ Geometry geometry_from_T(const sedx_handle* h, int64_t T) {
   g.fw_len = 8 * g.T3;
   g.out_frames = g.fw_len;
   // pad_framewise_output(roundup) models.py:678-681: Cnn_9layers_Gru_FrameAtt
-  // alone (Cnn_9layers_Gru_FrameAvg returns the 8 T3 frames, :551)
+  // (Cnn_9layers_Gru_FrameAvg returns the 8 T3 frames, :551) and the two
+  // Conformer models (:1359-1360, :1571-1572)
   if (h->pad100 && g.fw_len != 1000)
     g.out_frames = (g.fw_len % 100 == 0) ? g.fw_len : g.fw_len + 100 - g.fw_len % 100;
   return g;
@@ -372,6 +459,10 @@ WsLayout ws_layout(const sedx_handle* h, int64_t B, const Geometry& g) {
   // head scratch (after the conv stack): G/QKV + H + O + logits
   a = std::max(a, (size_t)B * g.T3 * (1536 + 512 + 512 + h->nac) + 4 * 64 +
                       gru_coop_workspace_bytes((int)B) / sizeof(float) + 64);
+  // Conformer encoder scratch: x, LayerNorm(x), the widest hidden (576), the
+  // attention / depthwise output, r and r_k of the 3 blocks, the logits
+  if (h->seq == SEQ_CONFORMER)
+    a = std::max(a, (size_t)B * g.T3 * (3 * CF_D + CF_FF + h->nac) + 2 * CF_BLOCKS * (size_t)g.T3 * CF_D + 8 * 64);
   l.bufA = off;
   off += align_up(a);
   size_t b = (size_t)B * g.T1 * 32 * 64;
@@ -512,7 +603,7 @@ sedx_status run_body(sedx_handle* h, int64_t B, const Geometry& g, float* ws, co
   float* G = A;                                   // [M][1536]
   float* Hs = A + align_up((size_t)M * 1536);     // [M][512]
   float* O = Hs + align_up((size_t)M * 512);      // [M][512]
-  float* LG = O + align_up((size_t)M * 512);      // [M][nac]
+  float* LG = O + align_up((size_t)M * 512);      // [M][nac] (the Conformer branch places its own)
   // GEMMs: x3 split-bf16 MFMA in x3 mode, fp32 MFMA in exact mode
   auto linear = [&](const float* a, const float* wf, void* wx, int n, int bn, const float* bias, float* c,
                     int act) {
@@ -524,7 +615,55 @@ sedx_status run_body(sedx_handle* h, int64_t B, const Geometry& g, float* ws, co
   // the head's input [M][512]: the sequence layer's output, or (no sequence
   // layer: no projection, no recurrence / MHA launch) the stage-8 buffer itself
   const float* HI = h->seq == SEQ_NONE ? S : Hs;
-  if (h->seq == SEQ_GRU) {
+  if (h->seq == SEQ_CONFORMER) {
+    // fp32 in every precision mode.  In A: x [M][144] (updated in place by
+    // the residual epilogues), LayerNorm(x), the hidden [M][<= 576], the
+    // attention / depthwise output, r | r_k [3][T3][144], the logits
+    const int T3 = (int)g.T3;
+    float* X = A;
+    float* Xn = X + align_up((size_t)M * CF_D);
+    float* Hb = Xn + align_up((size_t)M * CF_D);
+    float* AV = Hb + align_up((size_t)M * CF_FF);
+    float* Rr = AV + align_up((size_t)M * CF_D);
+    float* RK = Rr + align_up((size_t)CF_BLOCKS * T3 * CF_D);
+    LG = RK + align_up((size_t)CF_BLOCKS * T3 * CF_D);
+    const size_t nx = (size_t)M * CF_D;
+    // r and r_k = r_net(r) of every block: on device, every forward
+    launch_cf_relpos(w.cf_inv_freq, T3, CF_BLOCKS, Rr, s);
+    for (int b = 0; b < CF_BLOCKS; ++b)
+      launch_cf_gemm(Rr + (size_t)b * T3 * CF_D, T3, CF_D, w.cf[b].rnet, CF_D, nullptr, nullptr,
+                     RK + (size_t)b * T3 * CF_D, CF_EPI_NONE, s);
+    // input layer (conformer_encoder.py:22-28)
+    launch_cf_gemm(S, M, 512, w.cf_in_w, CF_D, w.cf_in_b, nullptr, Xn, CF_EPI_NONE, s);
+    launch_cf_input_norm(Xn, iB, T3, w.cf_in_g, w.cf_in_be, w.cf_pe, X, s);
+    capture(h, 20, X, nx, s);
+    for (int b = 0; b < CF_BLOCKS; ++b) {
+      const CfBlockWeights& c = w.cf[b];
+      auto ffn = [&](int f) {              // x = 0.5 ffn(x) + x
+        launch_cf_layernorm(X, M, c.ffn_g[f], c.ffn_be[f], Xn, s);
+        launch_cf_gemm(Xn, M, CF_D, c.ffn_w1[f], CF_FF, c.ffn_b1[f], nullptr, Hb, CF_EPI_SWISH, s);
+        launch_cf_gemm(Hb, M, CF_FF, c.ffn_w2[f], CF_D, c.ffn_b2[f], X, X, CF_EPI_HALF_RES, s);
+      };
+      ffn(0);
+      capture(h, 21 + 4 * b, X, nx, s);
+      // mhsa: x = x + o_net(attention(qkv_net(LN(x))))
+      launch_cf_layernorm(X, M, c.att_g, c.att_be, Xn, s);
+      launch_cf_gemm(Xn, M, CF_D, c.wqkv, 3 * CF_D, nullptr, nullptr, Hb, CF_EPI_NONE, s);
+      launch_cf_relattn(Hb, iB, T3, RK + (size_t)b * T3 * CF_D, c.rwb, c.rrb, AV, s);
+      launch_cf_gemm(AV, M, CF_D, c.wo, CF_D, nullptr, X, X, CF_EPI_RES, s);
+      capture(h, 22 + 4 * b, X, nx, s);
+      // conv module: x = conv(x) + x
+      launch_cf_layernorm(X, M, c.cv_g, c.cv_be, Xn, s);
+      launch_cf_gemm(Xn, M, CF_D, c.pw1_w, 2 * CF_D, c.pw1_b, nullptr, Hb, CF_EPI_NONE, s);
+      launch_cf_glu_dwconv(Hb, iB, T3, c.dw_wt, c.dw_b, AV, s);
+      launch_cf_gemm(AV, M, CF_D, c.pw2_w, CF_D, c.pw2_b, X, X, CF_EPI_RES, s);
+      capture(h, 23 + 4 * b, X, nx, s);
+      ffn(1);
+      launch_cf_layernorm(X, M, c.norm_g, c.norm_be, X, s);
+      capture(h, 24 + 4 * b, X, nx, s);
+    }
+    HI = X;
+  } else if (h->seq == SEQ_GRU) {
     linear(S, w.w_ih, w.w_ih_x3, 1536, 128, w.b_ih, G, 0);
     if (h->gru_kernel == SEDX_GRU_KERNEL_SIMPLE)
       launch_gru(G, iB, (int)g.T3, w.whhT, w.bhh, Hs, s);
@@ -554,16 +693,20 @@ sedx_status run_body(sedx_handle* h, int64_t B, const Geometry& g, float* ws, co
     launch_mha(G, iB, (int)g.T3, O, s);
     linear(O, w.wfc, w.wfc_x3, 512, 128, w.bfc, Hs, 1);
   }
-  capture(h, 9, HI, (size_t)M * 512, s);
+  capture(h, 9, HI, (size_t)M * h->hw, s);
   mark(h, 10, s);
   // head projection (att|cla rows or fc rows, zero-padded to nac), then its finish
-  linear(HI, w.wac, w.wac_x3, h->nac, 64, w.bac, LG, 0);
+  if (h->seq == SEQ_CONFORMER)
+    launch_cf_gemm(HI, M, CF_D, w.wac, h->nac, w.bac, nullptr, LG, CF_EPI_NONE, s);
+  else
+    linear(HI, w.wac, w.wac_x3, h->nac, 64, w.bac, LG, 0);
   if (h->head == HEAD_ATT)
     launch_att_head(LG, iB, (int)g.T3, h->cfg.classes_num, h->nac, (int)g.out_frames, d_fw, d_clip,
                     h->emb_cla ? d_emb : nullptr, s);
   else
-    launch_fc_head(LG, iB, (int)g.T3, h->cfg.classes_num, h->nac, h->head == HEAD_FC_MAX, d_fw, d_clip, s);
-  if (!h->emb_cla && d_emb) launch_transpose_btd(HI, iB, (int)g.T3, 512, d_emb, s);
+    launch_fc_head(LG, iB, (int)g.T3, h->cfg.classes_num, h->nac, h->head == HEAD_FC_MAX, d_fw, d_clip, s,
+                   (int)g.out_frames);
+  if (!h->emb_cla && d_emb) launch_transpose_btd(HI, iB, (int)g.T3, h->hw, d_emb, s);
   mark(h, 11, s);
   return launch_status(h);
 }
@@ -618,6 +761,9 @@ sedx_status window_geometry(const sedx_handle* h, int64_t L_clip, const sedx_win
       g.len = len;
       g.g = geometry_from_T(h, conv_T(h, len));
       if (g.g.T3 < 1) return fail(hm, SEDX_EINVAL, "window %d too short for the CNN", w);
+      if (seq_too_long(h, g.g.T3))
+        return fail(hm, SEDX_EINVAL, "window %d gives %lld sequence frames: the Conformer encoder holds %d", w,
+                    (long long)g.g.T3, CF_MAX_T);
       wg->groups.push_back(g);
     }
     ++wg->groups.back().nw;
@@ -721,7 +867,8 @@ sedx_status sedx_set_capture(sedx_handle* h, int32_t stage, float* d_buf, size_t
     h->cap_bytes = 0;
     return SEDX_OK;
   }
-  if (stage == 1 || stage > 9) return fail(h, SEDX_EINVAL, "stage %d cannot be captured", (int)stage);
+  const bool cf_stage = h->seq == SEQ_CONFORMER && stage >= 20 && stage <= 20 + 4 * CF_BLOCKS;
+  if (stage == 1 || (stage > 9 && !cf_stage)) return fail(h, SEDX_EINVAL, "stage %d cannot be captured", (int)stage);
   h->cap_stage = stage;
   h->cap_buf = d_buf;
   h->cap_bytes = bytes;
@@ -795,8 +942,9 @@ sedx_status sedx_create(const sedx_config* cfg, int device, sedx_handle** out) {
   h->device = device;
   h->seq = seq;
   h->head = head;
-  h->pad100 = cfg->model_type == SEDX_MODEL_GRU_FRAMEATT;
-  h->emb_cla = head == HEAD_ATT && seq != SEQ_MHA;
+  h->pad100 = cfg->model_type == SEDX_MODEL_GRU_FRAMEATT || seq == SEQ_CONFORMER;
+  h->emb_cla = head == HEAD_ATT && seq != SEQ_MHA && seq != SEQ_CONFORMER;
+  h->hw = seq == SEQ_CONFORMER ? CF_D : 512;
   h->nac = (((head == HEAD_ATT ? 2 : 1) * cfg->classes_num + 63) / 64) * 64;
   build_expected(h);
   *out = h;
@@ -824,6 +972,7 @@ sedx_status sedx_load_param(sedx_handle* h, const char* key, const float* h_data
                             const int64_t* shape, int32_t ndim) {
   if (!h || !key || !h_data || (ndim > 0 && !shape) || ndim < 0 || ndim > 8) return SEDX_EINVAL;
   auto it = h->expected.find(key);
+  if (it == h->expected.end() && ignored_key(h, key)) return SEDX_OK;
   if (it == h->expected.end()) return fail(h, SEDX_EKEY, "unexpected key in state_dict: %s", key);
   std::vector<int64_t> sh(shape, shape + ndim);
   if (sh != it->second) return fail(h, SEDX_EKEY, "size mismatch for %s", key);
@@ -1080,7 +1229,8 @@ sedx_status sedx_finalize_weights(sedx_handle* h) {
     bfc = get("multihead.fc.bias");
   }
   // head projection, rows zero-padded to nac: att | cla, or fc
-  std::vector<float> wac((size_t)h->nac * 512, 0.f), bac(h->nac, 0.f);
+  const int hw = h->hw;
+  std::vector<float> wac((size_t)h->nac * hw, 0.f), bac(h->nac, 0.f);
   if (h->head != HEAD_ATT) {
     const auto& wf = get("fc.weight");
     const auto& bf = get("fc.bias");
@@ -1092,9 +1242,9 @@ sedx_status sedx_finalize_weights(sedx_handle* h) {
     const auto& wc = get("att_block.cla.weight");
     const auto& bc = get("att_block.cla.bias");
     for (int c = 0; c < C; ++c) {
-      std::copy(wa.begin() + (size_t)c * 512, wa.begin() + (size_t)(c + 1) * 512, wac.begin() + (size_t)c * 512);
-      std::copy(wc.begin() + (size_t)c * 512, wc.begin() + (size_t)(c + 1) * 512,
-                wac.begin() + (size_t)(C + c) * 512);
+      std::copy(wa.begin() + (size_t)c * hw, wa.begin() + (size_t)(c + 1) * hw, wac.begin() + (size_t)c * hw);
+      std::copy(wc.begin() + (size_t)c * hw, wc.begin() + (size_t)(c + 1) * hw,
+                wac.begin() + (size_t)(C + c) * hw);
       bac[c] = ba[c];
       bac[C + c] = bc[c];
     }
@@ -1187,8 +1337,68 @@ sedx_status sedx_finalize_weights(sedx_handle* h) {
     add(&W.wqkv_x3, wqkv_x3.data(), wqkv_x3.size() * 2);
     add(&W.wfc_x3, wfc_x3.data(), wfc_x3.size() * 2);
   }
-  wac_x3 = pack_linear_x3(wac, h->nac, 512, 64);
-  add(&W.wac_x3, wac_x3.data(), wac_x3.size() * 2);
+  if (hw == 512) {   // the 144-wide projection runs fp32 in every mode
+    wac_x3 = pack_linear_x3(wac, h->nac, 512, 64);
+    add(&W.wac_x3, wac_x3.data(), wac_x3.size() * 2);
+  }
+  // Conformer encoder: the state_dict's own tensors, except the depthwise
+  // conv with its BatchNorm1d folded in (eval mode, eps 1e-5)
+  std::vector<float> cf_inv_freq, cf_dw_wt[CF_BLOCKS], cf_dw_b[CF_BLOCKS];
+  if (h->seq == SEQ_CONFORMER) {
+    auto up = [&](float** dst, const std::string& k) {
+      const auto& v = get(k);
+      add((void**)dst, v.data(), v.size() * 4);
+    };
+    up(&W.cf_in_w, "encoder.input_layer.0.weight");
+    up(&W.cf_in_b, "encoder.input_layer.0.bias");
+    up(&W.cf_in_g, "encoder.input_layer.1.weight");
+    up(&W.cf_in_be, "encoder.input_layer.1.bias");
+    up(&W.cf_pe, "encoder.input_layer.4.pe");
+    for (int b = 0; b < CF_BLOCKS; ++b) {
+      const std::string p = cf_block_key(b);
+      CfBlockWeights& c = W.cf[b];
+      for (int f = 0; f < 2; ++f) {
+        const std::string q = p + (f ? "ffn2" : "ffn1") + ".feed_forward_module.";
+        up(&c.ffn_g[f], q + "0.weight");
+        up(&c.ffn_be[f], q + "0.bias");
+        up(&c.ffn_w1[f], q + "1.weight");
+        up(&c.ffn_b1[f], q + "1.bias");
+        up(&c.ffn_w2[f], q + "4.weight");
+        up(&c.ffn_b2[f], q + "4.bias");
+      }
+      up(&c.att_g, p + "mhsa.layer_norm.weight");
+      up(&c.att_be, p + "mhsa.layer_norm.bias");
+      up(&c.wqkv, p + "mhsa.qkv_net.weight");
+      up(&c.wo, p + "mhsa.o_net.weight");
+      up(&c.rnet, p + "mhsa.r_net.weight");
+      up(&c.rwb, p + "mhsa.r_w_bias");
+      up(&c.rrb, p + "mhsa.r_r_bias");
+      up(&c.cv_g, p + "conv.conv.0.weight");
+      up(&c.cv_be, p + "conv.conv.0.bias");
+      up(&c.pw1_w, p + "conv.conv.1.conv.weight");
+      up(&c.pw1_b, p + "conv.conv.1.conv.bias");
+      up(&c.pw2_w, p + "conv.conv.8.conv.weight");
+      up(&c.pw2_b, p + "conv.conv.8.conv.bias");
+      up(&c.norm_g, p + "norm.weight");
+      up(&c.norm_be, p + "norm.bias");
+      const auto& fr = get(p + "mhsa.pos_emb.inv_freq");
+      cf_inv_freq.insert(cf_inv_freq.end(), fr.begin(), fr.end());
+      std::vector<double> sc;
+      std::vector<float> mu, bi;
+      bn_fold(p + "conv.conv.5", CF_D, sc, mu, bi);
+      const auto& dw = get(p + "conv.conv.3.conv.weight");   // [144][1][7]
+      const auto& db = get(p + "conv.conv.3.conv.bias");
+      cf_dw_wt[b].resize(7 * CF_D);
+      cf_dw_b[b].resize(CF_D);
+      for (int ch_ = 0; ch_ < CF_D; ++ch_) {
+        for (int t = 0; t < 7; ++t) cf_dw_wt[b][t * CF_D + ch_] = (float)((double)dw[ch_ * 7 + t] * sc[ch_]);
+        cf_dw_b[b][ch_] = (float)(((double)db[ch_] - (double)mu[ch_]) * sc[ch_] + (double)bi[ch_]);
+      }
+      add((void**)&c.dw_wt, cf_dw_wt[b].data(), cf_dw_wt[b].size() * 4);
+      add((void**)&c.dw_b, cf_dw_b[b].data(), cf_dw_b[b].size() * 4);
+    }
+    add((void**)&W.cf_inv_freq, cf_inv_freq.data(), cf_inv_freq.size() * 4);
+  }
   if (!g_wT.empty()) {
     add((void**)&W.g_twiddle, g_tw.data(), g_tw.size() * 8);
     add((void**)&W.g_window, g_win.data(), g_win.size() * 8);
@@ -1290,6 +1500,9 @@ sedx_status sedx_output_geometry(const sedx_handle* h, int64_t L_or_T, int64_t* 
   if (!h || !out_frames || !seq_len) return SEDX_EINVAL;
   const int64_t T = (h->cfg.feature_type == SEDX_FEATURE_GAMMA) ? L_or_T : conv_T(h, L_or_T);
   const Geometry g = geometry_from_T(h, T);
+  if (seq_too_long(h, g.T3))
+    return fail(const_cast<sedx_handle*>(h), SEDX_EINVAL, "%lld sequence frames: the Conformer encoder holds %d",
+                (long long)g.T3, CF_MAX_T);
   *out_frames = g.out_frames;
   *seq_len = g.T3;
   return SEDX_OK;
@@ -1298,7 +1511,11 @@ sedx_status sedx_output_geometry(const sedx_handle* h, int64_t L_or_T, int64_t* 
 sedx_status sedx_workspace_size(const sedx_handle* h, int64_t B, int64_t L_or_T, size_t* bytes) {
   if (!h || !bytes || B <= 0) return SEDX_EINVAL;
   const int64_t T = (h->cfg.feature_type == SEDX_FEATURE_GAMMA) ? L_or_T : conv_T(h, L_or_T);
-  *bytes = ws_layout(h, B, geometry_from_T(h, T)).total_bytes;
+  const Geometry g = geometry_from_T(h, T);
+  if (seq_too_long(h, g.T3))
+    return fail(const_cast<sedx_handle*>(h), SEDX_EINVAL, "%lld sequence frames: the Conformer encoder holds %d",
+                (long long)g.T3, CF_MAX_T);
+  *bytes = ws_layout(h, B, g).total_bytes;
   return SEDX_OK;
 }
 
@@ -1318,6 +1535,8 @@ static sedx_status forward_wave(sedx_handle* h, const float* d_wave, const int16
                 (long long)L, n2);
   const Geometry g = geometry_from_T(h, conv_T(h, L));
   if (g.T3 < 1) return fail(h, SEDX_EINVAL, "input too short for the 3 pooling stages");
+  if (seq_too_long(h, g.T3))
+    return fail(h, SEDX_EINVAL, "%lld sequence frames: the Conformer encoder holds %d", (long long)g.T3, CF_MAX_T);
   if (B * g.T > INT32_MAX / 64) return fail(h, SEDX_EINVAL, "batch too large");
   DeviceGuard dg(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1379,6 +1598,8 @@ sedx_status sedx_forward_features(sedx_handle* h, const float* d_feat, int64_t B
     return fail(h, SEDX_EINVAL, "null pointer or empty batch");
   const Geometry g = geometry_from_T(h, T);
   if (g.T3 < 1) return fail(h, SEDX_EINVAL, "input too short for the 3 pooling stages");
+  if (seq_too_long(h, g.T3))
+    return fail(h, SEDX_EINVAL, "%lld sequence frames: the Conformer encoder holds %d", (long long)g.T3, CF_MAX_T);
   DeviceGuard dg(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const WsLayout l = ws_layout(h, B, g);

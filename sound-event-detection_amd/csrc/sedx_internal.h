@@ -4,6 +4,7 @@
 //   X0        [items][T][64]                   log-mel after bn0 (conv input, Cin=1, F=64)
 //   act NHWC  [items][T][F][C]                 conv activations, channels innermost
 //   seq       [items][T4][512]                 CNN output after freq-mean (GRU/MHA input)
+//   enc       [items][T4][144]                 Conformer encoder activations (conformer.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -329,10 +330,41 @@ void launch_att_head(const float* logits, int B, int T, int C, int ldl, int out_
 // fc head finish (models.py:284-288, :369-373): sigmoid of logits [B][T][ldl]
 // (columns 0..C-1), x8 frame repeat -> framewise [B][8T][C], clipwise [B][C] =
 // the max (max_pool) or the mean over the frames
+// out_frames > 8T (the Conformer FrameAvg model, models.py:1571-1575; mean
+// only): frames 8T .. out_frames - 1 repeat the last frame and the mean runs
+// over all out_frames frames
 void launch_fc_head(const float* logits, int B, int T, int C, int ldl, bool max_pool, float* framewise,
-                    float* clipwise, hipStream_t s);
-// embedding of the 512-channel models: E [B][T][D] -> emb [B][D][T]
+                    float* clipwise, hipStream_t s, int out_frames = 0);
+// embedding of the fc / MultiHead / Conformer models: E [B][T][D] -> emb [B][D][T]
 void launch_transpose_btd(const float* E, int B, int T, int D, float* out, hipStream_t s);
+
+// ---- Conformer encoder (conformer.hip) --------------------------------------
+// fp32 in every precision mode.  Activations [items * T][width], CF_D = 144.
+constexpr int CF_D = 144;        // adim
+constexpr int CF_FF = 576;       // eunits
+constexpr int CF_BLOCKS = 3;     // elayers
+constexpr int CF_MAX_T = 5000;   // rows of the positional table pe (PositionalEncoding max_len)
+enum CfEpi { CF_EPI_NONE = 0, CF_EPI_SWISH = 1, CF_EPI_HALF_RES = 2, CF_EPI_RES = 3 };
+// C[M][N] = epi(A[M][K] . W[N][K]^T + bias[N]) on fp32 MFMA; K % 144 == 0 or
+// K % 128 == 0, any N; bias nullable.  epi: NONE y, SWISH y sigmoid(y), HALF_RES 0.5 y + res,
+// RES y + res (res [M][N]; may alias C).  Per-output summation order
+// independent of M.
+void launch_cf_gemm(const float* A, int M, int K, const float* W, int N, const float* bias, const float* res,
+                    float* C, int epi, hipStream_t s);
+// y = LayerNorm_144(x) gamma + beta (eps 1e-5); x may alias y
+void launch_cf_layernorm(const float* x, int M, const float* gamma, const float* beta, float* y, hipStream_t s);
+// the encoder's input layer after its Linear: relu(LayerNorm(x)) * 12 + pe[t]; x [B][T][144], pe [>= T][144]
+void launch_cf_input_norm(const float* x, int B, int T, const float* gamma, const float* beta, const float* pe,
+                          float* y, hipStream_t s);
+// r [nblk][T][144] = [sin(p f), cos(p f)], p = T - 1 - j, f = inv_freq [nblk][72]
+void launch_cf_relpos(const float* inv_freq, int T, int nblk, float* r, hipStream_t s);
+// relative-position attention core: QKV [B][T][432], rk [T][144] = r_net(r),
+// rwb / rrb [4][36] -> O [B][T][144]
+void launch_cf_relattn(const float* QKV, int B, int T, const float* rk, const float* rwb, const float* rrb,
+                       float* O, hipStream_t s);
+// GLU + depthwise 7-tap conv over time + folded BN + Swish: Y [B][T][288],
+// wt [7][144] (BN scale folded in), bf [144] -> Z [B][T][144]
+void launch_cf_glu_dwconv(const float* Y, int B, int T, const float* wt, const float* bf, float* Z, hipStream_t s);
 
 // ---- windowed drivers (windows.cpp) ---------------------------------------
 // loop control of predict.py:297-338 / main_strong.py:786-832: the sample

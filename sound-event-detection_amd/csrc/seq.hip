@@ -442,18 +442,24 @@ void launch_att_head(const float* logits, int B, int T, int C, int ldl, int out_
 //         clipwise equals the framewise maximum bit for bit.
 //   mean: each of the T distinct values stands for 8 frames, so the mean over
 //         8T frames is their sum / T; summed in float64 (a T-long fp32 chain
-//         would round once per term) and rounded to fp32 once.
+//         would round once per term) and rounded to fp32 once.  With
+//         out_frames > 8T (the Conformer FrameAvg model pads the framewise
+//         output with its last frame before the mean, models.py:1571-1575):
+//         (8 sum + npad last) / out_frames, in float64, one rounding.
 // ---------------------------------------------------------------------------
 template <bool MAXP>
 __global__ __launch_bounds__(256) void fc_head_kernel(const float* __restrict__ logits, int T, int C, int ldl,
-                                                      float* __restrict__ fw, float* __restrict__ clip) {
+                                                      int out_frames_, float* __restrict__ fw,
+                                                      float* __restrict__ clip) {
   constexpr int TC = 128;
   __shared__ float s_p[TC][33];
+  __shared__ float s_last[32];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int cs = tid >> 3, l = tid & 7;
   const int cc = tid & 31, tq = tid >> 5;
   const float* lg = logits + (int64_t)b * T * ldl;
-  const int64_t out_frames = 8 * (int64_t)T;
+  const int64_t out_frames = out_frames_;
+  const int npad = out_frames_ - 8 * T;           // frames past 8T repeat the last one
   for (int c0 = 0; c0 < C; c0 += 32) {
     const int nc = min(32, C - c0);
     const bool act = cs < nc;
@@ -477,6 +483,7 @@ __global__ __launch_bounds__(256) void fc_head_kernel(const float* __restrict__ 
       if (cc < nc)
         for (int fr = tq; fr < nt * 8; fr += 8)
           fw[((int64_t)b * out_frames + 8 * (int64_t)t0 + fr) * C + c0 + cc] = s_p[fr >> 3][cc];
+      if (npad > 0 && t0 + nt == T && tid < nc) s_last[tid] = s_p[nt - 1][tid];
     }
     if (MAXP) {
       mx = fmaxf(mx, __shfl_xor(mx, 1));
@@ -487,18 +494,33 @@ __global__ __launch_bounds__(256) void fc_head_kernel(const float* __restrict__ 
       sum += __shfl_xor(sum, 1);
       sum += __shfl_xor(sum, 2);
       sum += __shfl_xor(sum, 4);
-      if (act && l == 0) clip[(int64_t)b * C + c0 + cs] = (float)(sum / (double)T);
+      // padded: the mean over all out_frames frames, each of the T values 8
+      // times and the last one npad times more, still one rounding
+      if (act && l == 0 && npad == 0) clip[(int64_t)b * C + c0 + cs] = (float)(sum / (double)T);
+    }
+    if (npad > 0) {
+      __syncthreads();                            // s_last
+      if (!MAXP && act && l == 0)
+        clip[(int64_t)b * C + c0 + cs] =
+            (float)((8.0 * sum + (double)npad * (double)s_last[cs]) / (double)out_frames);
+      if (cc < nc)
+        for (int f = 8 * T + tq; f < out_frames_; f += 8)
+          fw[((int64_t)b * out_frames + f) * C + c0 + cc] = s_last[cc];
     }
   }
 }
 
 void launch_fc_head(const float* logits, int B, int T, int C, int ldl, bool max_pool, float* framewise,
-                    float* clipwise, hipStream_t s) {
-  if (B <= 0 || T <= 0 || C <= 0 || ldl < C) return note_launch_error(hipErrorInvalidValue);
+                    float* clipwise, hipStream_t s, int out_frames) {
+  if (out_frames == 0) out_frames = 8 * T;
+  if (B <= 0 || T <= 0 || C <= 0 || ldl < C || out_frames < 8 * T || (max_pool && out_frames != 8 * T))
+    return note_launch_error(hipErrorInvalidValue);
   if (max_pool)
-    hipLaunchKernelGGL(fc_head_kernel<true>, dim3(B), dim3(256), 0, s, logits, T, C, ldl, framewise, clipwise);
+    hipLaunchKernelGGL(fc_head_kernel<true>, dim3(B), dim3(256), 0, s, logits, T, C, ldl, out_frames, framewise,
+                       clipwise);
   else
-    hipLaunchKernelGGL(fc_head_kernel<false>, dim3(B), dim3(256), 0, s, logits, T, C, ldl, framewise, clipwise);
+    hipLaunchKernelGGL(fc_head_kernel<false>, dim3(B), dim3(256), 0, s, logits, T, C, ldl, out_frames, framewise,
+                       clipwise);
 }
 
 __global__ __launch_bounds__(256) void transpose_btd_kernel(const float* __restrict__ E, int T,

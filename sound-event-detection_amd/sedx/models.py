@@ -9,7 +9,12 @@ The reference's five other models on the same 9-layer trunk
 (``Cnn_9layers_FrameMax``, ``Cnn_9layers_FrameAvg``, ``Cnn_9layers_FrameAtt``:
 seven constructor arguments, ``forward(input, mixup_lambda=None)``;
 ``Cnn_9layers_Gru_FrameAvg``, ``Cnn_9layers_Transformer_FrameAvg``) follow the
-same rule.  The submodules are parameter containers; the whole eval-mode forward runs in
+same rule, and so do the two Conformer models on that trunk
+(``Cnn_9layers_Conformer_FrameAtt``, ``Cnn_9layers_Conformer_FrameAvg``:
+``(..., classes_num, cnn_kwargs=None, encoder_kwargs=None,
+encoder_type="Conformer", pooling="token", layer_init="pytorch")`` and
+``forward(x, mixup_lambda=None, timeshift=False, spec_augment=True,
+mask=None)``).  The submodules are parameter containers; the whole eval-mode forward runs in
 libsedx (HIP kernels for gfx950) through the C ABI in include/sedx.h.  There
 is no CPU or eager-PyTorch fallback: a non-HIP input raises.
 
@@ -36,14 +41,16 @@ from .stft import Spectrogram, LogmelFilterBank
 
 __all__ = ['Cnn_9layers_Gru_FrameAtt', 'Cnn_9layers_Transformer_FrameAtt',
            'Cnn_9layers_FrameMax', 'Cnn_9layers_FrameAvg', 'Cnn_9layers_FrameAtt',
-           'Cnn_9layers_Gru_FrameAvg', 'Cnn_9layers_Transformer_FrameAvg', 'ConvBlock',
+           'Cnn_9layers_Gru_FrameAvg', 'Cnn_9layers_Transformer_FrameAvg',
+           'Cnn_9layers_Conformer_FrameAtt', 'Cnn_9layers_Conformer_FrameAvg', 'ConformerEncoder', 'ConvBlock',
            'AttBlock', 'MultiHead', 'interpolate', 'pad_framewise_output', 'roundup',
            'init_layer', 'init_bn', 'init_gru']
 
 # sedx_model (include/sedx.h)
 MODEL_IDS = {'Cnn_9layers_Gru_FrameAtt': 0, 'Cnn_9layers_Transformer_FrameAtt': 1,
              'Cnn_9layers_FrameMax': 2, 'Cnn_9layers_FrameAvg': 3, 'Cnn_9layers_FrameAtt': 4,
-             'Cnn_9layers_Gru_FrameAvg': 5, 'Cnn_9layers_Transformer_FrameAvg': 6}
+             'Cnn_9layers_Gru_FrameAvg': 5, 'Cnn_9layers_Transformer_FrameAvg': 6,
+             'Cnn_9layers_Conformer_FrameAtt': 7, 'Cnn_9layers_Conformer_FrameAvg': 8}
 FEATURE_IDS = {'logmel': 0, 'gamma': 1}
 
 
@@ -168,6 +175,138 @@ class MultiHead(nn.Module):
 
 
 # ---------------------------------------------------------------------------
+# Conformer encoder containers (pytorch/models_2020/conformer/): the module
+# tree of the reference, so the state_dict has its keys, shapes and order
+# ---------------------------------------------------------------------------
+def _fused(name):
+    def forward(self, *args, **kwargs):
+        raise RuntimeError('%s is fused into the native model forward (libsedx)' % name)
+    return forward
+
+
+class _Slot(nn.Module):
+    """A parameter-free position of an nn.Sequential (Swish, GLU, Permute)."""
+    forward = _fused('the Conformer encoder')
+
+
+class _PositionalEncoding(nn.Module):
+    """models_2020/transformer/embedding.py:8-31: the ``pe`` buffer
+    [1, max_len, d_model], sin on the even columns, cos on the odd."""
+
+    def __init__(self, d_model, dropout_rate, max_len=5000):
+        super().__init__()
+        self.dropout = nn.Dropout(p=dropout_rate)
+        pe = torch.zeros(max_len, d_model)
+        position = torch.arange(0, max_len, dtype=torch.float32).unsqueeze(1)
+        div_term = torch.exp(torch.arange(0, d_model, 2, dtype=torch.float32) * -(math.log(10000.0) / d_model))
+        pe[:, 0::2] = torch.sin(position * div_term)
+        pe[:, 1::2] = torch.cos(position * div_term)
+        self.max_len = max_len
+        self.xscale = math.sqrt(d_model)
+        self.register_buffer('pe', pe.unsqueeze(0))
+
+    forward = _fused('PositionalEncoding')
+
+
+class _MacaronFeedForward(nn.Module):
+    """conformer/macaron_feed_forward.py: LN, Linear, Swish, Dropout, Linear, Dropout."""
+
+    def __init__(self, d_model, d_ff, dropout):
+        super().__init__()
+        self.feed_forward_module = nn.Sequential(nn.LayerNorm(d_model), nn.Linear(d_model, d_ff), _Slot(),
+                                                 nn.Dropout(dropout), nn.Linear(d_ff, d_model),
+                                                 nn.Dropout(dropout))
+
+    forward = _fused('MacaronFeedForward')
+
+
+class _PositionalEmbedding(nn.Module):
+    """conformer/attention.py:126-133: the ``inv_freq`` buffer."""
+
+    def __init__(self, demb):
+        super().__init__()
+        self.demb = demb
+        self.register_buffer('inv_freq', 1 / (10000 ** (torch.arange(0.0, demb, 2.0) / demb)))
+
+    forward = _fused('PositionalEmbedding')
+
+
+class _RelMultiHeadAttn(nn.Module):
+    """conformer/attention.py:145-172 (pre_lnorm=True; weights only)."""
+
+    def __init__(self, n_head, d_model, dropout):
+        super().__init__()
+        self.n_head, self.d_model, self.d_head = n_head, d_model, d_model // n_head
+        self.qkv_net = nn.Linear(d_model, 3 * n_head * self.d_head, bias=False)
+        self.drop = nn.Dropout(dropout)
+        self.dropatt = nn.Dropout(0)
+        self.o_net = nn.Linear(n_head * self.d_head, d_model, bias=False)
+        self.layer_norm = nn.LayerNorm(d_model)
+        self.pos_emb = _PositionalEmbedding(d_model)
+        self.r_w_bias = nn.Parameter(torch.zeros(n_head, self.d_head))
+        self.r_r_bias = nn.Parameter(torch.zeros(n_head, self.d_head))
+        self.r_net = nn.Linear(d_model, n_head * self.d_head, bias=False)
+
+    forward = _fused('RelMultiHeadAttn')
+
+
+class _Conv1dBox(nn.Module):
+    """conformer/convolution.py:5-28: a Conv1d under the name ``conv``."""
+
+    def __init__(self, cin, cout, kernel_size, padding, groups):
+        super().__init__()
+        self.conv = nn.Conv1d(cin, cout, kernel_size, 1, padding, groups=groups)
+
+    forward = _fused('ConvolutionModule')
+
+
+class _ConvolutionModule(nn.Module):
+    """conformer/convolution.py:38-55: LN, pointwise, GLU, depthwise, Permute,
+    BatchNorm1d, Permute, Swish, pointwise, Dropout."""
+
+    def __init__(self, d_model, dropout, kernel_size):
+        super().__init__()
+        self.conv = nn.Sequential(nn.LayerNorm(d_model), _Conv1dBox(d_model, 2 * d_model, 1, 0, 1), _Slot(),
+                                  _Conv1dBox(d_model, d_model, kernel_size, int(kernel_size / 2), d_model),
+                                  _Slot(), nn.BatchNorm1d(d_model), _Slot(), _Slot(),
+                                  _Conv1dBox(d_model, d_model, 1, 0, 1), nn.Dropout(dropout))
+
+    forward = _fused('ConvolutionModule')
+
+
+class _ConformerBlock(nn.Module):
+    """conformer/conformer_block.py:7-14."""
+
+    def __init__(self, d_model, d_ff, n_head, dropout, kernel_size):
+        super().__init__()
+        self.ffn1 = _MacaronFeedForward(d_model, d_ff, dropout)
+        self.mhsa = _RelMultiHeadAttn(n_head, d_model, dropout)
+        self.conv = _ConvolutionModule(d_model, dropout, kernel_size)
+        self.ffn2 = _MacaronFeedForward(d_model, d_ff, dropout)
+        self.norm = nn.LayerNorm(d_model)
+
+    forward = _fused('ConformerBlock')
+
+
+class ConformerEncoder(nn.Module):
+    """conformer/conformer_encoder.py:7-29 (weights only).  The native encoder
+    implements the reference's one shape: (512, 144, 3 blocks, 576, 4 heads,
+    kernel 7)."""
+
+    def __init__(self, idim, adim=144, dropout_rate=0.1, elayers=3, eunits=576, aheads=4, kernel_size=7):
+        super().__init__()
+        if (idim, adim, elayers, eunits, aheads, kernel_size) != (512, 144, 3, 576, 4, 7):
+            raise ValueError('the native Conformer encoder implements the reference shape '
+                             '(idim 512, adim 144, elayers 3, eunits 576, aheads 4, kernel_size 7)')
+        self.input_layer = nn.Sequential(nn.Linear(idim, adim), nn.LayerNorm(adim), nn.Dropout(dropout_rate),
+                                         nn.ReLU(), _PositionalEncoding(adim, dropout_rate))
+        self.conformer_blocks = nn.Sequential(*[_ConformerBlock(adim, eunits, aheads, dropout_rate, kernel_size)
+                                                for _ in range(elayers)])
+
+    forward = _fused('ConformerEncoder')
+
+
+# ---------------------------------------------------------------------------
 # native handle management
 # ---------------------------------------------------------------------------
 class _Native(object):
@@ -252,6 +391,7 @@ class _SedModel(nn.Module):
     # return it (models.py:459, :686); every other model returns the head's
     # 512-channel input (batch, 512, seq)
     _embedding_cla = False
+    _embedding_width = 512     # 144 after the Conformer encoder
 
     def __init__(self, sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num,
                  feature_type='logmel'):
@@ -441,7 +581,7 @@ class _SedModel(nn.Module):
         dev = x.device
         fw = torch.empty((B, fr.value, C), dtype=torch.float32, device=dev)
         clip = torch.empty((B, C), dtype=torch.float32, device=dev)
-        emb_shape = (B, C, sl.value) if self._embedding_cla else (B, 512, sl.value)
+        emb_shape = (B, C, sl.value) if self._embedding_cla else (B, self._embedding_width, sl.value)
         emb = torch.empty(emb_shape, dtype=torch.float32, device=dev)
         wsz = ctypes.c_size_t()
         _lib.check(L.sedx_workspace_size(nat.h, B, length, ctypes.byref(wsz)), nat.h, 'workspace_size')
@@ -565,3 +705,63 @@ class Cnn_9layers_Transformer_FrameAvg(_SedModel):
         self.fc = nn.Linear(512, classes_num, bias=True)
         init_bn(self.bn0)
         init_layer(self.fc)
+
+
+class _ConformerModel(_SedModel):
+    """The two Conformer classes (pytorch/models.py:1189-1300, :1412-1515):
+    the reference constructor and ``forward(x, mixup_lambda=None,
+    timeshift=False, spec_augment=True, mask=None)``; always logmel.  The
+    encoder and the 144-wide head run fp32 in every precision mode.  The
+    sequence holds at most 5000 frames (the ``pe`` table)."""
+    _embedding_width = 144
+    _head_classes = None       # the handle's class count when it is not classes_num
+
+    def __init__(self, sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num,
+                 cnn_kwargs=None, encoder_kwargs=None, encoder_type='Conformer', pooling='token',
+                 layer_init='pytorch'):
+        if encoder_type == 'Transformer':
+            raise ValueError('encoder_type="Transformer" (models_2020/transformer) is not implemented natively; '
+                             'only the Conformer encoder is')
+        if encoder_type != 'Conformer':
+            raise ValueError("Choose encoder_type in ['Transformer', 'Conformer']")
+        if pooling != 'token':
+            raise ValueError('pooling=%r: the reference forward uses none of its pooling branches, and only '
+                             'the default module tree (pooling="token") is mirrored' % (pooling,))
+        if layer_init.lower() != 'pytorch':
+            raise ValueError('layer_init=%r: load a state_dict instead (inference-only model)' % (layer_init,))
+        super().__init__(sample_rate, window_size, hop_size, mel_bins, fmin, fmax,
+                         self._head_classes or classes_num, 'logmel')
+        self.pooling = pooling
+        self.encoder_kwargs = {'adim': 144, 'aheads': 4, 'dropout_rate': 0.1, 'elayers': 3, 'eunits': 576,
+                               'kernel_size': 7}
+        self.encoder = ConformerEncoder(512, **self.encoder_kwargs)
+        self._build_head(classes_num)
+        self.classifier = nn.Linear(144, classes_num)      # unused in forward (models.py:1290, :1505)
+        self.linear_emb = nn.Linear(1, 512)                # unused in forward (pooling == "token")
+
+    def forward(self, x, mixup_lambda=None, timeshift=False, spec_augment=True, mask=None):
+        if mask is not None:
+            raise ValueError('mask must be None: the native encoder implements the unmasked forward')
+        return super().forward(x, mixup_lambda=mixup_lambda, timeshift=timeshift, spec_augment=spec_augment)
+
+
+class Cnn_9layers_Conformer_FrameAtt(_ConformerModel):
+    """pytorch/models.py:1189-1410: trunk, Conformer encoder, ``AttBlock(144,
+    25)`` -- 25 classes whatever ``classes_num`` is (:1288), like
+    ``Cnn_9layers_FrameAtt``; framewise padded to a multiple of 100 with its
+    last frame; embedding = the encoder output (batch, 144, seq)."""
+    _model_name = 'Cnn_9layers_Conformer_FrameAtt'
+    _head_classes = 25
+
+    def _build_head(self, classes_num):
+        self.att_block = AttBlock(n_in=144, n_out=25, activation='sigmoid')
+
+
+class Cnn_9layers_Conformer_FrameAvg(_ConformerModel):
+    """pytorch/models.py:1412-1625: trunk, Conformer encoder, sigmoid(fc);
+    framewise padded to a multiple of 100 with its last frame, clipwise = the
+    mean over the padded frames (:1575)."""
+    _model_name = 'Cnn_9layers_Conformer_FrameAvg'
+
+    def _build_head(self, classes_num):
+        self.fc = nn.Linear(144, classes_num, bias=True)

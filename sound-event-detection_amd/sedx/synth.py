@@ -9,7 +9,8 @@ state_dict: tests regenerate it from the seed.
 Keys/shapes follow the reference state_dict (SURVEY.md Appendix A;
 ``pytorch/models.py:564-624`` GRU model, ``:981-1027`` Transformer model;
 the five other 9-layer models: ``:213-250``, ``:298-338``, ``:383-421``,
-``:466-510``, ``:880-927``).
+``:466-510``, ``:880-927``; the two Conformer models: ``:1189-1300``,
+``:1412-1515`` with ``models_2020/conformer/``).
 Only the learnable tensors and BN statistics are produced here; the frontend
 buffers (``spectrogram_extractor.stft.conv_{real,imag}.weight``,
 ``logmel_extractor.melW``) come from the model constructors.
@@ -43,6 +44,8 @@ MODEL_PARTS = {
     'Cnn_9layers_FrameAtt': (None, 'att'),
     'Cnn_9layers_Gru_FrameAvg': ('gru', 'fc'),
     'Cnn_9layers_Transformer_FrameAvg': ('mha', 'fc'),
+    'Cnn_9layers_Conformer_FrameAtt': ('conformer', 'att'),
+    'Cnn_9layers_Conformer_FrameAvg': ('conformer', 'fc'),
 }
 # the weight seed of every model's golden fixtures (tests/golden/)
 GOLDEN_SEEDS = {
@@ -56,17 +59,82 @@ GOLDEN_SEEDS = {
 }
 
 
+# the two Conformer models' (tests/golden/conformer_*; GOLDEN_SEEDS is the
+# seven earlier models' and stays as it is)
+CONFORMER_GOLDEN_SEEDS = {
+    'Cnn_9layers_Conformer_FrameAtt': 7,
+    'Cnn_9layers_Conformer_FrameAvg': 8,
+}
+CONFORMER_DIM, CONFORMER_FF, CONFORMER_BLOCKS, CONFORMER_HEADS, CONFORMER_KERNEL = 144, 576, 3, 4, 7
+
+
+def _layer_norm(rng, prefix, n):
+    # nn.LayerNorm starts at (1, 0): drawn, so that the affine part is exercised
+    return {prefix + '.weight': rng.uniform(0.5, 1.5, n).astype(np.float32),
+            prefix + '.bias': rng.uniform(-0.2, 0.2, n).astype(np.float32)}
+
+
+def _linear(rng, prefix, out, fan_in, shape=None, bias=True):
+    # nn.Linear / nn.Conv1d default: U(+-1/sqrt(fan_in)) for weight and bias
+    a = 1.0 / np.sqrt(fan_in)
+    sd = {prefix + '.weight': rng.uniform(-a, a, shape or (out, fan_in)).astype(np.float32)}
+    if bias:
+        sd[prefix + '.bias'] = rng.uniform(-a, a, out).astype(np.float32)
+    return sd
+
+
+def _conformer_encoder(rng):
+    """ConformerEncoder(512, 144, elayers 3, eunits 576, aheads 4, kernel 7)
+    in state_dict order, without its two kinds of constant buffers
+    (``encoder.input_layer.4.pe``, ``...mhsa.pos_emb.inv_freq``: from the
+    model constructor, like the frontend's)."""
+    D, FF = CONFORMER_DIM, CONFORMER_FF
+    sd = {}
+    sd.update(_linear(rng, 'encoder.input_layer.0', D, 512))
+    sd.update(_layer_norm(rng, 'encoder.input_layer.1', D))
+    for b in range(CONFORMER_BLOCKS):
+        p = 'encoder.conformer_blocks.%d.' % b
+
+        def ffn(name):
+            q = p + name + '.feed_forward_module.'
+            sd.update(_layer_norm(rng, q + '0', D))
+            sd.update(_linear(rng, q + '1', FF, D))
+            sd.update(_linear(rng, q + '4', D, FF))
+        ffn('ffn1')
+        # zeros in the reference's constructor
+        sd[p + 'mhsa.r_w_bias'] = rng.uniform(-0.1, 0.1, (CONFORMER_HEADS, D // CONFORMER_HEADS)).astype(np.float32)
+        sd[p + 'mhsa.r_r_bias'] = rng.uniform(-0.1, 0.1, (CONFORMER_HEADS, D // CONFORMER_HEADS)).astype(np.float32)
+        sd.update(_linear(rng, p + 'mhsa.qkv_net', 3 * D, D, bias=False))
+        sd.update(_linear(rng, p + 'mhsa.o_net', D, D, bias=False))
+        sd.update(_layer_norm(rng, p + 'mhsa.layer_norm', D))
+        sd.update(_linear(rng, p + 'mhsa.r_net', D, D, bias=False))
+        sd.update(_layer_norm(rng, p + 'conv.conv.0', D))
+        sd.update(_linear(rng, p + 'conv.conv.1.conv', 2 * D, D, shape=(2 * D, D, 1)))
+        sd.update(_linear(rng, p + 'conv.conv.3.conv', D, CONFORMER_KERNEL, shape=(D, 1, CONFORMER_KERNEL)))
+        sd.update(_bn(rng, p + 'conv.conv.5', D, mean_range=(-0.3, 0.3), var_range=(0.05, 0.3)))
+        sd.update(_linear(rng, p + 'conv.conv.8.conv', D, D, shape=(D, D, 1)))
+        ffn('ffn2')
+        sd.update(_layer_norm(rng, p + 'norm', D))
+    return sd
+
+
 def make_state_dict(model_type, classes_num=25, seed=0):
     """Return {key: np.ndarray} for the non-frontend parameters of one of the
-    seven 9-layer models (``MODEL_PARTS``).  Draw order: the trunk, the
+    nine 9-layer models (``MODEL_PARTS``).  Draw order: the trunk, the
     sequence layer's tensors, the head's (so two models with one seed share
     every tensor up to the first that differs).  ``Cnn_9layers_FrameAtt``'s
-    AttBlock has 25 classes whatever ``classes_num`` is (models.py:416)."""
+    AttBlock has 25 classes whatever ``classes_num`` is (models.py:416), and so
+    has ``Cnn_9layers_Conformer_FrameAtt``'s (:1288).  The Conformer models get
+    every encoder tensor drawn (LayerNorm weights and biases and the two
+    relative-position biases included, which PyTorch initialises to constants),
+    then the head, then the two modules they never call."""
     if model_type not in MODEL_PARTS:
         raise ValueError('unknown model_type %r' % model_type)
     seq, head = MODEL_PARTS[model_type]
-    if model_type == 'Cnn_9layers_FrameAtt':
+    ctor_classes = classes_num
+    if model_type in ('Cnn_9layers_FrameAtt', 'Cnn_9layers_Conformer_FrameAtt'):
         classes_num = 25
+    width = CONFORMER_DIM if seq == 'conformer' else 512
     rng = np.random.default_rng(seed)
     sd = {}
     # bn0 normalises log-mel dB values (models.py:607,642-644); realistic stats
@@ -98,17 +166,23 @@ def make_state_dict(model_type, classes_num=25, seed=0):
         std_fc = np.sqrt(2.0 / (512 + 512))
         sd['multihead.fc.weight'] = rng.normal(0, std_fc, (512, 512)).astype(np.float32)
         sd['multihead.fc.bias'] = rng.uniform(-0.05, 0.05, 512).astype(np.float32)
+    elif seq == 'conformer':
+        sd.update(_conformer_encoder(rng))
     if head == 'fc':
         # nn.Linear(512, classes_num) with init_layer's xavier weight
         # (models.py:247, :253); a negative bias like cla's below
-        sd['fc.weight'] = _xavier_uniform(rng, (classes_num, 512), 512, classes_num)
+        sd['fc.weight'] = _xavier_uniform(rng, (classes_num, width), width, classes_num)
         sd['fc.bias'] = rng.uniform(-0.5, 0.0, classes_num).astype(np.float32)
-        return sd
-    sd['att_block.att.weight'] = _xavier_uniform(rng, (classes_num, 512, 1), 512, classes_num)
-    sd['att_block.att.bias'] = rng.uniform(-0.1, 0.1, classes_num).astype(np.float32)
-    sd['att_block.cla.weight'] = _xavier_uniform(rng, (classes_num, 512, 1), 512, classes_num)
-    sd['att_block.cla.bias'] = rng.uniform(-0.5, 0.0, classes_num).astype(np.float32)
-    sd.update(_bn(rng, 'att_block.bn_att', classes_num))
+    else:
+        sd['att_block.att.weight'] = _xavier_uniform(rng, (classes_num, width, 1), width, classes_num)
+        sd['att_block.att.bias'] = rng.uniform(-0.1, 0.1, classes_num).astype(np.float32)
+        sd['att_block.cla.weight'] = _xavier_uniform(rng, (classes_num, width, 1), width, classes_num)
+        sd['att_block.cla.bias'] = rng.uniform(-0.5, 0.0, classes_num).astype(np.float32)
+        sd.update(_bn(rng, 'att_block.bn_att', classes_num))
+    if seq == 'conformer':
+        # built and never called at inference (models.py:1290-1300, :1505-1515)
+        sd.update(_linear(rng, 'classifier', ctor_classes, CONFORMER_DIM))
+        sd.update(_linear(rng, 'linear_emb', 512, 1))
     return sd
 
 
