@@ -20,102 +20,8 @@
 
 using namespace sedx;
 
-namespace {
-
-// a model = the CNN trunk, then a sequence layer, then a head
-enum SeqKind { SEQ_NONE = 0, SEQ_GRU = 1, SEQ_MHA = 2, SEQ_CONFORMER = 3 };
-enum HeadKind { HEAD_ATT = 0, HEAD_FC_AVG = 1, HEAD_FC_MAX = 2 };
-
-struct Tensor {
-  std::vector<int64_t> shape;
-  std::vector<float> data;
-};
-
-// one ConformerBlock (conformer_block.py:8-24); every matrix in its
-// state_dict layout [out][in]
-struct CfBlockWeights {
-  float* ffn_g[2] = {};    // ffn1 / ffn2: LayerNorm weight, bias [144]
-  float* ffn_be[2] = {};
-  float* ffn_w1[2] = {};   // [576][144]
-  float* ffn_b1[2] = {};
-  float* ffn_w2[2] = {};   // [144][576]
-  float* ffn_b2[2] = {};
-  float* att_g = nullptr;  // mhsa.layer_norm
-  float* att_be = nullptr;
-  float* wqkv = nullptr;   // [432][144]
-  float* wo = nullptr;     // [144][144]
-  float* rnet = nullptr;   // [144][144]
-  float* rwb = nullptr;    // [4][36]
-  float* rrb = nullptr;
-  float* cv_g = nullptr;   // conv module's LayerNorm
-  float* cv_be = nullptr;
-  float* pw1_w = nullptr;  // [288][144]
-  float* pw1_b = nullptr;
-  float* dw_wt = nullptr;  // [7][144]: depthwise taps x BN scale, tap-major
-  float* dw_b = nullptr;   // [144]: folded bias
-  float* pw2_w = nullptr;  // [144][144]
-  float* pw2_b = nullptr;
-  float* norm_g = nullptr; // the block's final LayerNorm
-  float* norm_be = nullptr;
-};
-
-struct DevWeights {
-  float2* twiddle = nullptr;
-  float* window = nullptr;
-  float* mel_w = nullptr;
-  float* mel_tab = nullptr;   // logmel512_kernel's per-(slot, lane) band weights
-  float* mel_mt = nullptr;    // logmel512_kernel's MFMA mel table (FrontendParams::mel_mt)
-  int32_t mt_klo[4] = {}, mt_ns[4] = {}, mt_off[4] = {}, mt_floats = 0;
-  int32_t mel_wmax = 0;
-  int32_t* mel_off = nullptr;
-  int32_t* mel_lo = nullptr;
-  float* bn0_scale = nullptr;
-  float* bn0_mean = nullptr;
-  float* bn0_bias = nullptr;
-  float* c1_w = nullptr;
-  float* c1_wt = nullptr;
-  float* c1_b = nullptr;
-  float* zero = nullptr;   // ZERO_BLOCK_FLOATS zeros (LDS-DMA source of out-of-clip halo pixels)
-  float* trash = nullptr;  // 32 KB write-only scratch (the Winograd kernel's dummy / out-of-range stores)
-  float* wp[8] = {};    // packed conv weights: block k conv j -> index 2(k-1)+(j-1); [0] unused
-  float* cb[8] = {};    // folded biases
-  void* wx3[8] = {};    // split bf16 hi/lo packs for conv3x3_x3 (same indices)
-  float* wu[8] = {};    // Winograd U = G g G^T packs for conv3x3_wino (same indices)
-  float* wu43[8] = {};  // F(4x4,3x3) U packs for conv3x3_wino43 (block 1's conv2: 1, blocks 2-4: 2..7)
-  float* w_ih = nullptr;   // [1536][512]
-  float* b_ih = nullptr;   // [1536]
-  float* whhT = nullptr;   // [2][256][768]
-  float* whh = nullptr;    // [2][768][256] (cooperative recurrence)
-  float* bhh = nullptr;    // [2][768]
-  float* wqkv = nullptr;   // [1536][512]
-  float* bqkv = nullptr;
-  float* wfc = nullptr;    // [512][512]
-  float* bfc = nullptr;
-  float* wac = nullptr;    // [nac][hw]
-  float* bac = nullptr;
-  // Conformer encoder (fp32 in every mode)
-  float* cf_in_w = nullptr;      // [144][512]
-  float* cf_in_b = nullptr;
-  float* cf_in_g = nullptr;      // input layer's LayerNorm
-  float* cf_in_be = nullptr;
-  float* cf_pe = nullptr;        // [5000][144] (the state_dict's buffer)
-  float* cf_inv_freq = nullptr;  // [3][72]
-  CfBlockWeights cf[CF_BLOCKS];
-  // x3 (split bf16) packs of the linear weights for linear_x3.hip
-  void* w_ih_x3 = nullptr;
-  void* wqkv_x3 = nullptr;
-  void* wfc_x3 = nullptr;
-  void* wac_x3 = nullptr;
-  // gamma
-  double2* g_twiddle = nullptr;
-  double* g_window = nullptr;
-  double* g_weightsT = nullptr;  // [gamma_kp(nfft)][64] ERB weights (fft_weights)
-};
-
-}  // namespace
-
-struct sedx_handle {
-  sedx_config cfg;
+// the model (cfg, seq, head, hw, nac: sedx_create, weights.h) and its state
+struct sedx_handle : sedx::Model {
   int device = 0;
   std::string err;
   std::map<std::string, Tensor> params;
@@ -124,14 +30,8 @@ struct sedx_handle {
   void* blob = nullptr;      // single device allocation for all packed weights
   size_t blob_bytes = 0;
   DevWeights w;
-  // the model as a pair (sedx_create, model_parts): what follows the CNN
-  // trunk, and the head that reads its output
-  int seq = SEQ_GRU;
-  int head = HEAD_ATT;
   bool pad100 = false;       // framewise padded to a multiple of 100 (Cnn_9layers_Gru_FrameAtt, models.py:678-681)
   bool emb_cla = false;      // d_embedding is cla [B][C][T3] (models.py:683-686, :459), else the head's input transposed
-  int hw = 512;              // width of the head's input: 512, or 144 after the Conformer encoder
-  int nac = 64;              // rows of the head projection: att|cla (2C) or fc (C), rounded up to 64
   int g_nfft = 0, g_nwin = 0, g_hop = 0;
   void* ws = nullptr;        // cached workspace
   size_t ws_bytes = 0;
@@ -300,112 +200,6 @@ struct DeviceGuard {
     if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
   }
 };
-
-// sedx_model -> (seq, head); false for an unknown model_type
-bool model_parts(int32_t model_type, int* seq, int* head) {
-  switch (model_type) {
-    case SEDX_MODEL_GRU_FRAMEATT: *seq = SEQ_GRU, *head = HEAD_ATT; return true;
-    case SEDX_MODEL_TRANSFORMER_FRAMEATT: *seq = SEQ_MHA, *head = HEAD_ATT; return true;
-    case SEDX_MODEL_CNN_FRAMEMAX: *seq = SEQ_NONE, *head = HEAD_FC_MAX; return true;
-    case SEDX_MODEL_CNN_FRAMEAVG: *seq = SEQ_NONE, *head = HEAD_FC_AVG; return true;
-    case SEDX_MODEL_CNN_FRAMEATT: *seq = SEQ_NONE, *head = HEAD_ATT; return true;
-    case SEDX_MODEL_GRU_FRAMEAVG: *seq = SEQ_GRU, *head = HEAD_FC_AVG; return true;
-    case SEDX_MODEL_TRANSFORMER_FRAMEAVG: *seq = SEQ_MHA, *head = HEAD_FC_AVG; return true;
-    case SEDX_MODEL_CONFORMER_FRAMEATT: *seq = SEQ_CONFORMER, *head = HEAD_ATT; return true;
-    case SEDX_MODEL_CONFORMER_FRAMEAVG: *seq = SEQ_CONFORMER, *head = HEAD_FC_AVG; return true;
-    default: return false;
-  }
-}
-
-// keys of modules the Conformer models build and never call at inference
-// (models.py:1290-1300, :1505-1515): accepted with any shape, not stored
-bool ignored_key(const sedx_handle* h, const std::string& k) {
-  if (h->seq != SEQ_CONFORMER) return false;
-  return k == "classifier.weight" || k == "classifier.bias" || k == "linear_emb.weight" || k == "linear_emb.bias";
-}
-
-std::string cf_block_key(int b) { return "encoder.conformer_blocks." + std::to_string(b) + "."; }
-
-void add_bn(std::map<std::string, std::vector<int64_t>>& e, const std::string& p, int64_t n) {
-  for (const char* s : {".weight", ".bias", ".running_mean", ".running_var"}) e[p + s] = {n};
-}
-
-void build_expected(sedx_handle* h) {
-  auto& e = h->expected;
-  const int64_t K = h->cfg.window_size / 2 + 1;
-  e["spectrogram_extractor.stft.conv_real.weight"] = {K, 1, h->cfg.window_size};
-  e["spectrogram_extractor.stft.conv_imag.weight"] = {K, 1, h->cfg.window_size};
-  e["logmel_extractor.melW"] = {K, h->cfg.mel_bins};
-  add_bn(e, "bn0", 64);
-  const int64_t ch[5] = {1, 64, 128, 256, 512};
-  for (int k = 1; k <= 4; ++k) {
-    const std::string p = "conv_block" + std::to_string(k);
-    e[p + ".conv1.weight"] = {ch[k], ch[k - 1], 3, 3};
-    e[p + ".conv2.weight"] = {ch[k], ch[k], 3, 3};
-    add_bn(e, p + ".bn1", ch[k]);
-    add_bn(e, p + ".bn2", ch[k]);
-  }
-  const int64_t C = h->cfg.classes_num;
-  if (h->head == HEAD_ATT) {
-    e["att_block.att.weight"] = {C, h->hw, 1};
-    e["att_block.att.bias"] = {C};
-    e["att_block.cla.weight"] = {C, h->hw, 1};
-    e["att_block.cla.bias"] = {C};
-    add_bn(e, "att_block.bn_att", C);   // unused in forward (models.py:161-169)
-  } else {
-    e["fc.weight"] = {C, h->hw};        // nn.Linear(512, classes_num) (models.py:247, :332, :503, :921; 144: :1500)
-    e["fc.bias"] = {C};
-  }
-  if (h->seq == SEQ_GRU) {
-    for (const char* s : {"", "_reverse"}) {
-      e[std::string("gru.weight_ih_l0") + s] = {768, 512};
-      e[std::string("gru.weight_hh_l0") + s] = {768, 256};
-      e[std::string("gru.bias_ih_l0") + s] = {768};
-      e[std::string("gru.bias_hh_l0") + s] = {768};
-    }
-  } else if (h->seq == SEQ_MHA) {
-    for (const char* n : {"w_qs", "w_ks", "w_vs", "fc"}) {
-      e[std::string("multihead.") + n + ".weight"] = {512, 512};
-      e[std::string("multihead.") + n + ".bias"] = {512};
-    }
-    e["multihead.layer_norm.weight"] = {512};   // unused in forward (models.py:853-877)
-    e["multihead.layer_norm.bias"] = {512};
-  } else if (h->seq == SEQ_CONFORMER) {
-    auto ln = [&](const std::string& p) { e[p + ".weight"] = {CF_D}, e[p + ".bias"] = {CF_D}; };
-    auto lin = [&](const std::string& p, int64_t out, int64_t in, bool bias) {
-      e[p + ".weight"] = {out, in};
-      if (bias) e[p + ".bias"] = {out};
-    };
-    lin("encoder.input_layer.0", CF_D, 512, true);
-    ln("encoder.input_layer.1");
-    e["encoder.input_layer.4.pe"] = {1, CF_MAX_T, CF_D};
-    for (int b = 0; b < CF_BLOCKS; ++b) {
-      const std::string p = cf_block_key(b);
-      for (const char* f : {"ffn1", "ffn2"}) {
-        const std::string q = p + f + ".feed_forward_module.";
-        ln(q + "0");
-        lin(q + "1", CF_FF, CF_D, true);
-        lin(q + "4", CF_D, CF_FF, true);
-      }
-      e[p + "mhsa.r_w_bias"] = {4, CF_D / 4};
-      e[p + "mhsa.r_r_bias"] = {4, CF_D / 4};
-      lin(p + "mhsa.qkv_net", 3 * CF_D, CF_D, false);
-      lin(p + "mhsa.o_net", CF_D, CF_D, false);
-      ln(p + "mhsa.layer_norm");
-      e[p + "mhsa.pos_emb.inv_freq"] = {CF_D / 2};
-      lin(p + "mhsa.r_net", CF_D, CF_D, false);
-      ln(p + "conv.conv.0");
-      e[p + "conv.conv.1.conv.weight"] = {2 * CF_D, CF_D, 1};
-      e[p + "conv.conv.1.conv.bias"] = {2 * CF_D};
-      e[p + "conv.conv.3.conv.weight"] = {CF_D, 1, 7};
-      e[p + "conv.conv.3.conv.bias"] = {CF_D};
-      add_bn(e, p + "conv.conv.5", CF_D);
-      e[p + "conv.conv.8.conv.weight"] = {CF_D, CF_D, 1};
-      e[p + "conv.conv.8.conv.bias"] = {CF_D};
-      ln(p + "norm");
-    }
-  }
-}
 
 int64_t conv_T(const sedx_handle* h, int64_t L) { return L / h->cfg.hop_size + 1; }
 
@@ -929,24 +723,20 @@ sedx_status sedx_check_error(sedx_handle* h) {
 sedx_status sedx_create(const sedx_config* cfg, int device, sedx_handle** out) {
   if (!cfg || !out) return SEDX_EINVAL;
   *out = nullptr;
-  int seq = 0, head = 0;
-  if (!model_parts(cfg->model_type, &seq, &head)) return SEDX_EINVAL;
   if (cfg->mel_bins != 64) return SEDX_EINVAL;
   if (cfg->window_size != 256 && cfg->window_size != 512 && cfg->window_size != 1024) return SEDX_EINVAL;
   if (cfg->hop_size <= 0 || cfg->sample_rate <= 0 || cfg->classes_num <= 0 || cfg->classes_num > 256)
     return SEDX_EINVAL;
   if (cfg->feature_type == SEDX_FEATURE_GAMMA && cfg->model_type != SEDX_MODEL_GRU_FRAMEATT)
     return SEDX_EINVAL;
+  Model m;   // after the range checks: nac is computed from classes_num
+  if (!make_model(*cfg, &m)) return SEDX_EINVAL;
   sedx_handle* h = new sedx_handle();
-  h->cfg = *cfg;
+  static_cast<Model&>(*h) = m;
   h->device = device;
-  h->seq = seq;
-  h->head = head;
-  h->pad100 = cfg->model_type == SEDX_MODEL_GRU_FRAMEATT || seq == SEQ_CONFORMER;
-  h->emb_cla = head == HEAD_ATT && seq != SEQ_MHA && seq != SEQ_CONFORMER;
-  h->hw = seq == SEQ_CONFORMER ? CF_D : 512;
-  h->nac = (((head == HEAD_ATT ? 2 : 1) * cfg->classes_num + 63) / 64) * 64;
-  build_expected(h);
+  h->pad100 = cfg->model_type == SEDX_MODEL_GRU_FRAMEATT || m.seq == SEQ_CONFORMER;
+  h->emb_cla = m.head == HEAD_ATT && m.seq != SEQ_MHA && m.seq != SEQ_CONFORMER;
+  h->expected = expected_params(m);
   *out = h;
   return SEDX_OK;
 }
@@ -972,7 +762,7 @@ sedx_status sedx_load_param(sedx_handle* h, const char* key, const float* h_data
                             const int64_t* shape, int32_t ndim) {
   if (!h || !key || !h_data || (ndim > 0 && !shape) || ndim < 0 || ndim > 8) return SEDX_EINVAL;
   auto it = h->expected.find(key);
-  if (it == h->expected.end() && ignored_key(h, key)) return SEDX_OK;
+  if (it == h->expected.end() && ignored_key(*h, key)) return SEDX_OK;
   if (it == h->expected.end()) return fail(h, SEDX_EKEY, "unexpected key in state_dict: %s", key);
   std::vector<int64_t> sh(shape, shape + ndim);
   if (sh != it->second) return fail(h, SEDX_EKEY, "size mismatch for %s", key);
@@ -988,438 +778,26 @@ sedx_status sedx_load_param(sedx_handle* h, const char* key, const float* h_data
 
 sedx_status sedx_finalize_weights(sedx_handle* h) {
   if (!h) return SEDX_EINVAL;
-  for (auto& kv : h->expected)
-    if (!h->params.count(kv.first))
-      return fail(h, SEDX_EKEY, "missing key in state_dict: %s", kv.first.c_str());
+  // host work first, before any device call: the key check and every packed
+  // layout, as the host image of one allocation (weights.cpp)
+  DevWeights w;
+  WeightBlob blob;
+  GammaGeom gg;
+  if (sedx_status st = prepare_weights(*h, h->params, &w, &blob, &gg, &h->err)) return st;
   DeviceGuard dg(h->device);
-  const auto& P = h->params;
-  auto get = [&](const std::string& k) -> const std::vector<float>& { return P.at(k).data; };
-  const int nfft = h->cfg.window_size, K = nfft / 2 + 1;
-  const int C = h->cfg.classes_num;
-
-  // ---- STFT weights -> window (row k=0 of conv_real is the window since DFT[n,0]=1) ----
-  const auto& wr = get("spectrogram_extractor.stft.conv_real.weight");
-  const auto& wi = get("spectrogram_extractor.stft.conv_imag.weight");
-  std::vector<float> window(wr.begin(), wr.begin() + nfft);
-  {
-    // the FFT frontend requires conv_real/imag = Re/Im(DFT) * window (stft.py:209-217)
-    double maxerr = 0;
-    const int rows[6] = {1, 2, K / 3, K / 2, K - 2, K - 1};
-    for (int r : rows)
-      for (int n = 0; n < nfft; ++n) {
-        const double ang = -2.0 * M_PI * (double)((int64_t)n * r % nfft) / nfft;
-        maxerr = std::max(maxerr, std::fabs(wr[(size_t)r * nfft + n] - std::cos(ang) * window[n]));
-        maxerr = std::max(maxerr, std::fabs(wi[(size_t)r * nfft + n] - std::sin(ang) * window[n]));
-      }
-    if (maxerr > 1e-5)
-      return fail(h, SEDX_EINVAL, "STFT conv weights are not a windowed DFT (max err %.3g); "
-                                  "the FFT frontend cannot reproduce them", maxerr);
-  }
-  std::vector<float> tw(2 * nfft);
-  for (int m = 0; m < nfft; ++m) {
-    tw[2 * m] = (float)std::cos(-2.0 * M_PI * m / nfft);
-    tw[2 * m + 1] = (float)std::sin(-2.0 * M_PI * m / nfft);
-  }
-  // ---- mel bands ----
-  const auto& melW = get("logmel_extractor.melW");  // [K][64]
-  std::vector<float> mel_w;
-  std::vector<int32_t> mel_off(65), mel_lo(64);
-  for (int m = 0; m < 64; ++m) {
-    int lo = -1, hi = -1;
-    for (int k = 0; k < K; ++k)
-      if (melW[(size_t)k * 64 + m] != 0.0f) {
-        if (lo < 0) lo = k;
-        hi = k;
-      }
-    mel_off[m] = (int32_t)mel_w.size();
-    mel_lo[m] = lo < 0 ? 0 : lo;
-    if (lo >= 0)
-      for (int k = lo; k <= hi; ++k) mel_w.push_back(melW[(size_t)k * 64 + m]);
-  }
-  mel_off[64] = (int32_t)mel_w.size();
-  // the n_fft 512 kernel's band table: slot q of lane b is band
-  // fe16_band_host(b, q), zero-padded to FE16_MEL_MW bins
-  std::vector<float> mel_tab((size_t)4 * 16 * FE16_MEL_MW, 0.f);
-  int32_t mel_wmax = 0;
-  for (int m = 0; m < 64; ++m) mel_wmax = std::max(mel_wmax, mel_off[m + 1] - mel_off[m]);
-  mel_wmax = (mel_wmax + 3) & ~3;
-  for (int q = 0; q < 4; ++q)
-    for (int b = 0; b < 16; ++b) {
-      const int m = fe16_band_host(b, q), wd = mel_off[m + 1] - mel_off[m];
-      for (int e = 0; e < std::min(wd, FE16_MEL_MW); ++e)
-        mel_tab[((size_t)q * 16 + b) * FE16_MEL_MW + e] = mel_w[mel_off[m] + e];
-    }
-  if (mel_w.empty()) mel_w.push_back(0.f);
-  // the MFMA mel path's table (n_fft 512): per 16-band tile j the bin range
-  // its bands cover, in 4-bin steps: [step][4 bins][16 bands] of melW (zero
-  // outside a band, and past the last bin)
-  std::vector<float> mel_mt;
-  int32_t mt_klo[4] = {}, mt_ns[4] = {}, mt_off[4] = {};
-  if (nfft == 512) {
-    for (int j = 0; j < 4; ++j) {
-      int klo = K, khi = -1;
-      for (int m = 16 * j; m < 16 * j + 16; ++m) {
-        const int wd = mel_off[m + 1] - mel_off[m];
-        if (wd <= 0) continue;
-        klo = std::min(klo, mel_lo[m]);
-        khi = std::max(khi, mel_lo[m] + wd - 1);
-      }
-      const int ns = khi < klo ? 0 : (khi - klo + 1 + 3) / 4;
-      mt_klo[j] = ns ? klo : 0;
-      mt_ns[j] = ns;
-      mt_off[j] = (int32_t)mel_mt.size();
-      for (int st = 0; st < ns; ++st)
-        for (int kk = 0; kk < 4; ++kk)
-          for (int n = 0; n < 16; ++n) {
-            const int k = klo + 4 * st + kk, m = 16 * j + n;
-            mel_mt.push_back(k < K ? melW[(size_t)k * 64 + m] : 0.f);
-          }
-    }
-  }
-
-  auto bn_fold = [&](const std::string& p, int n, std::vector<double>& sc, std::vector<float>& mu,
-                     std::vector<float>& bi) {
-    const auto& g = get(p + ".weight");
-    const auto& b = get(p + ".bias");
-    const auto& m = get(p + ".running_mean");
-    const auto& v = get(p + ".running_var");
-    sc.resize(n);
-    mu.resize(n);
-    bi.resize(n);
-    for (int i = 0; i < n; ++i) {
-      sc[i] = (double)g[i] / std::sqrt((double)v[i] + 1e-5);
-      mu[i] = m[i];
-      bi[i] = b[i];
-    }
-  };
-  std::vector<double> s0;
-  std::vector<float> mu0, bi0, sc0f(64);
-  bn_fold("bn0", 64, s0, mu0, bi0);
-  for (int i = 0; i < 64; ++i) sc0f[i] = (float)s0[i];
-
-  // ---- conv weights: fold BN, pack [Cin/4][9][khalf 2][Cout][ks 2] (exact:
-  // channel 2 ks + khalf of a 4-channel chunk; the MFMA B fragments of both
-  // k-steps are one 8-byte LDS read) ----
-  const int ch[5] = {1, 64, 128, 256, 512};
-  std::vector<float> packed[8], cbias[8], c1w(64 * 9), c1b(64);
-  std::vector<uint16_t> packed_x3[8];
-  std::vector<float> packed_wu[8], packed_wu43[8];
-  for (int k = 1; k <= 4; ++k)
-    for (int j = 1; j <= 2; ++j) {
-      const std::string p = "conv_block" + std::to_string(k);
-      const int cin = (j == 1) ? ch[k - 1] : ch[k], cout = ch[k];
-      const auto& wt = get(p + ".conv" + std::to_string(j) + ".weight");
-      std::vector<double> sc;
-      std::vector<float> mu, bi;
-      bn_fold(p + ".bn" + std::to_string(j), cout, sc, mu, bi);
-      std::vector<float> bias(cout);
-      for (int o = 0; o < cout; ++o) bias[o] = (float)((double)bi[o] - (double)mu[o] * sc[o]);
-      if (k == 1 && j == 1) {
-        for (int o = 0; o < 64; ++o)
-          for (int t = 0; t < 9; ++t) c1w[o * 9 + t] = (float)(wt[(size_t)o * 9 + t] * sc[o]);
-        c1b = bias;
-        continue;
-      }
-      const int idx = 2 * (k - 1) + (j - 1);
-      std::vector<float>& pk = packed[idx];
-      pk.assign((size_t)cin * 9 * cout, 0.f);
-      for (int o = 0; o < cout; ++o)
-        for (int i = 0; i < cin; ++i)
-          for (int t = 0; t < 9; ++t) {
-            const int chunk = i / 4, kc = i % 4, ks = kc >> 1, kh = kc & 1;
-            pk[((((size_t)chunk * 9 + t) * 2 + kh) * cout + o) * 2 + ks] =
-                (float)(wt[((size_t)o * cin + i) * 9 + t] * sc[o]);
-          }
-      cbias[idx] = bias;
-      // Winograd pack: U = G g G^T from the float64 BN-folded weights
-      {
-        std::vector<double> wf((size_t)cout * cin * 9);
-        for (int o = 0; o < cout; ++o)
-          for (size_t k = 0; k < (size_t)cin * 9; ++k) wf[(size_t)o * cin * 9 + k] = wt[(size_t)o * cin * 9 + k] * sc[o];
-        packed_wu[idx].assign((size_t)cin * cout * 16, 0.f);
-        pack_conv_wino(wf.data(), cin, cout, packed_wu[idx].data());
-        {   // block 1's conv2 and blocks 2-4: the F(4x4,3x3) pack as well
-          packed_wu43[idx].assign((size_t)2 * cin * cout * 36, 0.f);
-          pack_conv_wino43(wf.data(), cin, cout, packed_wu43[idx].data());
-        }
-      }
-      // 3xbf16 split pack: [Cout/BN][Cin/16][9][BN][4 slots x 8 bf16], slot c at c ^ ((n>>2)&3)
-      {
-        const int BN = (cout == 64) ? 64 : 128;
-        std::vector<uint16_t>& px = packed_x3[idx];
-        px.assign((size_t)cout * cin * 9 * 2, 0);
-        auto rne = [](float x) -> uint32_t {
-          uint32_t u;
-          std::memcpy(&u, &x, 4);
-          return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-        };
-        for (int o = 0; o < cout; ++o)
-          for (int i = 0; i < cin; ++i)
-            for (int t = 0; t < 9; ++t) {
-              const float x = (float)(wt[((size_t)o * cin + i) * 9 + t] * sc[o]);
-              const uint32_t hb = rne(x);
-              const uint32_t hbits = hb << 16;
-              float hf;
-              std::memcpy(&hf, &hbits, 4);
-              const uint32_t lb = rne(x - hf);
-              const int nt = o / BN, n = o % BN, chunk = i / 16, k = i % 16;
-              const int sw = (n >> 2) & 3;
-              const size_t rec = ((((size_t)nt * (cin / 16) + chunk) * 9 + t) * BN + n) * 32;
-              px[rec + 8 * ((k / 8) ^ sw) + (k % 8)] = (uint16_t)hb;
-              px[rec + 8 * ((2 + k / 8) ^ sw) + (k % 8)] = (uint16_t)lb;
-            }
-      }
-    }
-
-  // ---- head ----
-  std::vector<float> w_ih, b_ih, whhT, bhh, wqkv, bqkv, wfc, bfc, whh_nat;
-  // W [N][K] -> [N/BN][K/16][BN][4 slots x 8 bf16], slot c at c ^ ((n>>2)&3)
-  // (the conv x3 layout with a single tap; linear_x3.hip)
-  auto pack_linear_x3 = [](const std::vector<float>& W, int N, int K, int BN) {
-    std::vector<uint16_t> px((size_t)N * K * 2, 0);
-    auto rne = [](float x) -> uint32_t {
-      uint32_t u;
-      std::memcpy(&u, &x, 4);
-      return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-    };
-    for (int o = 0; o < N; ++o)
-      for (int i = 0; i < K; ++i) {
-        const float x = W[(size_t)o * K + i];
-        const uint32_t hb = rne(x);
-        const uint32_t hbits = hb << 16;
-        float hf;
-        std::memcpy(&hf, &hbits, 4);
-        const uint32_t lb = rne(x - hf);
-        const int nt = o / BN, n = o % BN, ks = i / 16, k = i % 16, sw = (n >> 2) & 3;
-        const size_t rec = (((size_t)nt * (K / 16) + ks) * BN + n) * 32;
-        px[rec + 8 * ((k / 8) ^ sw) + (k % 8)] = (uint16_t)hb;
-        px[rec + 8 * ((2 + k / 8) ^ sw) + (k % 8)] = (uint16_t)lb;
-      }
-    return px;
-  };
-  if (h->seq == SEQ_GRU) {
-    w_ih.resize(1536 * 512);
-    b_ih.resize(1536);
-    whhT.resize(2 * 256 * 768);
-    bhh.resize(2 * 768);
-    const char* sfx[2] = {"", "_reverse"};
-    for (int d = 0; d < 2; ++d) {
-      const auto& wih = get(std::string("gru.weight_ih_l0") + sfx[d]);
-      const auto& whh = get(std::string("gru.weight_hh_l0") + sfx[d]);
-      const auto& bi = get(std::string("gru.bias_ih_l0") + sfx[d]);
-      const auto& bh = get(std::string("gru.bias_hh_l0") + sfx[d]);
-      std::copy(wih.begin(), wih.end(), w_ih.begin() + (size_t)d * 768 * 512);
-      std::copy(bi.begin(), bi.end(), b_ih.begin() + d * 768);
-      std::copy(bh.begin(), bh.end(), bhh.begin() + d * 768);
-      for (int r = 0; r < 768; ++r)
-        for (int k = 0; k < 256; ++k) whhT[((size_t)d * 256 + k) * 768 + r] = whh[(size_t)r * 256 + k];
-      whh_nat.insert(whh_nat.end(), whh.begin(), whh.end());
-    }
-  } else if (h->seq == SEQ_MHA) {
-    wqkv.resize(1536 * 512);
-    bqkv.resize(1536);
-    const char* nm[3] = {"w_qs", "w_ks", "w_vs"};
-    for (int i = 0; i < 3; ++i) {
-      const auto& ww = get(std::string("multihead.") + nm[i] + ".weight");
-      const auto& bb = get(std::string("multihead.") + nm[i] + ".bias");
-      std::copy(ww.begin(), ww.end(), wqkv.begin() + (size_t)i * 512 * 512);
-      std::copy(bb.begin(), bb.end(), bqkv.begin() + i * 512);
-    }
-    wfc = get("multihead.fc.weight");
-    bfc = get("multihead.fc.bias");
-  }
-  // head projection, rows zero-padded to nac: att | cla, or fc
-  const int hw = h->hw;
-  std::vector<float> wac((size_t)h->nac * hw, 0.f), bac(h->nac, 0.f);
-  if (h->head != HEAD_ATT) {
-    const auto& wf = get("fc.weight");
-    const auto& bf = get("fc.bias");
-    std::copy(wf.begin(), wf.end(), wac.begin());
-    std::copy(bf.begin(), bf.end(), bac.begin());
-  } else {
-    const auto& wa = get("att_block.att.weight");
-    const auto& ba = get("att_block.att.bias");
-    const auto& wc = get("att_block.cla.weight");
-    const auto& bc = get("att_block.cla.bias");
-    for (int c = 0; c < C; ++c) {
-      std::copy(wa.begin() + (size_t)c * hw, wa.begin() + (size_t)(c + 1) * hw, wac.begin() + (size_t)c * hw);
-      std::copy(wc.begin() + (size_t)c * hw, wc.begin() + (size_t)(c + 1) * hw,
-                wac.begin() + (size_t)(C + c) * hw);
-      bac[c] = ba[c];
-      bac[C + c] = bc[c];
-    }
-  }
-
-  // ---- gammatone tables (float64, numpy operation order: gamma_weights.cpp) ----
-  std::vector<double> g_tw, g_win, g_wT;
-  if (h->cfg.feature_type == SEDX_FEATURE_GAMMA) {
-    // fft_gtgram (fftweight.py:151-152) + gtgram_strides (gtgram.py:23-40)
-    const double fs = h->cfg.sample_rate;
-    const double win_t = (double)h->cfg.window_size / fs, hop_t = (double)h->cfg.hop_size / fs;
-    const int nfft_g = (int)std::pow(2.0, std::ceil(std::log2(2 * win_t * fs)));
-    auto rhaz = [](double x) { return (x > 0 ? 1.0 : (x < 0 ? -1.0 : 0.0)) * std::floor(std::fabs(x) + 0.5); };
-    const int nwin = (int)rhaz(win_t * fs), nhop = (int)rhaz(hop_t * fs);
-    if (nfft_g != 512 && nfft_g != 1024 && nfft_g != 2048)
-      return fail(h, SEDX_EINVAL, "gammatone nfft %d unsupported", nfft_g);
-    h->g_nfft = nfft_g;
-    h->g_nwin = nwin;
-    h->g_hop = nhop;
-    gamma_tables(fs, nfft_g, nwin, 64, h->cfg.fmin, g_wT, gamma_kp(nfft_g), g_tw, g_win);
-  }
-
-  // ---- upload: one blob ----
-  struct Item {
-    void** dst;
-    const void* src;
-    size_t bytes;
-  };
-  std::vector<Item> items;
-  auto add = [&](void** dst, const void* src, size_t bytes) { items.push_back({dst, src, bytes}); };
-  DevWeights& W = h->w;
-  W = DevWeights();
-  add((void**)&W.twiddle, tw.data(), tw.size() * 4);
-  add((void**)&W.window, window.data(), window.size() * 4);
-  add((void**)&W.mel_w, mel_w.data(), mel_w.size() * 4);
-  add((void**)&W.mel_tab, mel_tab.data(), mel_tab.size() * 4);
-  if (!mel_mt.empty() && mel_mt.size() <= (size_t)FE_MT_MAX_FLOATS) {
-    add((void**)&W.mel_mt, mel_mt.data(), mel_mt.size() * 4);
-    for (int j = 0; j < 4; ++j) {
-      W.mt_klo[j] = mt_klo[j];
-      W.mt_ns[j] = mt_ns[j];
-      W.mt_off[j] = mt_off[j];
-    }
-    W.mt_floats = (int32_t)mel_mt.size();
-  }
-  W.mel_wmax = mel_wmax;
-  add((void**)&W.mel_off, mel_off.data(), mel_off.size() * 4);
-  add((void**)&W.mel_lo, mel_lo.data(), mel_lo.size() * 4);
-  add((void**)&W.bn0_scale, sc0f.data(), 64 * 4);
-  add((void**)&W.bn0_mean, mu0.data(), 64 * 4);
-  add((void**)&W.bn0_bias, bi0.data(), 64 * 4);
-  add((void**)&W.c1_w, c1w.data(), c1w.size() * 4);
-  std::vector<float> c1wt(9 * 64);               // [tap][64]: channel pairs adjacent
-  for (int o = 0; o < 64; ++o)
-    for (int t = 0; t < 9; ++t) c1wt[t * 64 + o] = c1w[o * 9 + t];
-  add((void**)&W.c1_wt, c1wt.data(), c1wt.size() * 4);
-  add((void**)&W.c1_b, c1b.data(), c1b.size() * 4);
-  std::vector<float> zeros(ZERO_BLOCK_FLOATS, 0.f);   // >= Cin + 4 floats: the Winograd halo DMA steps through it
-  add((void**)&W.zero, zeros.data(), zeros.size() * 4);
-  std::vector<float> trash(64 * 128, 0.f);
-  add((void**)&W.trash, trash.data(), trash.size() * 4);
-  for (int i = 1; i < 8; ++i) {
-    add((void**)&W.wp[i], packed[i].data(), packed[i].size() * 4);
-    add((void**)&W.cb[i], cbias[i].data(), cbias[i].size() * 4);
-    add((void**)&W.wx3[i], packed_x3[i].data(), packed_x3[i].size() * 2);
-    add((void**)&W.wu[i], packed_wu[i].data(), packed_wu[i].size() * 4);
-    if (!packed_wu43[i].empty()) add((void**)&W.wu43[i], packed_wu43[i].data(), packed_wu43[i].size() * 4);
-  }
-  if (h->seq == SEQ_GRU) {
-    add((void**)&W.w_ih, w_ih.data(), w_ih.size() * 4);
-    add((void**)&W.b_ih, b_ih.data(), b_ih.size() * 4);
-    add((void**)&W.whhT, whhT.data(), whhT.size() * 4);
-    add((void**)&W.whh, whh_nat.data(), whh_nat.size() * 4);
-    add((void**)&W.bhh, bhh.data(), bhh.size() * 4);
-  } else if (h->seq == SEQ_MHA) {
-    add((void**)&W.wqkv, wqkv.data(), wqkv.size() * 4);
-    add((void**)&W.bqkv, bqkv.data(), bqkv.size() * 4);
-    add((void**)&W.wfc, wfc.data(), wfc.size() * 4);
-    add((void**)&W.bfc, bfc.data(), bfc.size() * 4);
-  }
-  add((void**)&W.wac, wac.data(), wac.size() * 4);
-  add((void**)&W.bac, bac.data(), bac.size() * 4);
-  std::vector<uint16_t> w_ih_x3, wqkv_x3, wfc_x3, wac_x3;
-  if (h->seq == SEQ_GRU) {
-    w_ih_x3 = pack_linear_x3(w_ih, 1536, 512, 128);
-    add(&W.w_ih_x3, w_ih_x3.data(), w_ih_x3.size() * 2);
-  } else if (h->seq == SEQ_MHA) {
-    wqkv_x3 = pack_linear_x3(wqkv, 1536, 512, 128);
-    wfc_x3 = pack_linear_x3(wfc, 512, 512, 128);
-    add(&W.wqkv_x3, wqkv_x3.data(), wqkv_x3.size() * 2);
-    add(&W.wfc_x3, wfc_x3.data(), wfc_x3.size() * 2);
-  }
-  if (hw == 512) {   // the 144-wide projection runs fp32 in every mode
-    wac_x3 = pack_linear_x3(wac, h->nac, 512, 64);
-    add(&W.wac_x3, wac_x3.data(), wac_x3.size() * 2);
-  }
-  // Conformer encoder: the state_dict's own tensors, except the depthwise
-  // conv with its BatchNorm1d folded in (eval mode, eps 1e-5)
-  std::vector<float> cf_inv_freq, cf_dw_wt[CF_BLOCKS], cf_dw_b[CF_BLOCKS];
-  if (h->seq == SEQ_CONFORMER) {
-    auto up = [&](float** dst, const std::string& k) {
-      const auto& v = get(k);
-      add((void**)dst, v.data(), v.size() * 4);
-    };
-    up(&W.cf_in_w, "encoder.input_layer.0.weight");
-    up(&W.cf_in_b, "encoder.input_layer.0.bias");
-    up(&W.cf_in_g, "encoder.input_layer.1.weight");
-    up(&W.cf_in_be, "encoder.input_layer.1.bias");
-    up(&W.cf_pe, "encoder.input_layer.4.pe");
-    for (int b = 0; b < CF_BLOCKS; ++b) {
-      const std::string p = cf_block_key(b);
-      CfBlockWeights& c = W.cf[b];
-      for (int f = 0; f < 2; ++f) {
-        const std::string q = p + (f ? "ffn2" : "ffn1") + ".feed_forward_module.";
-        up(&c.ffn_g[f], q + "0.weight");
-        up(&c.ffn_be[f], q + "0.bias");
-        up(&c.ffn_w1[f], q + "1.weight");
-        up(&c.ffn_b1[f], q + "1.bias");
-        up(&c.ffn_w2[f], q + "4.weight");
-        up(&c.ffn_b2[f], q + "4.bias");
-      }
-      up(&c.att_g, p + "mhsa.layer_norm.weight");
-      up(&c.att_be, p + "mhsa.layer_norm.bias");
-      up(&c.wqkv, p + "mhsa.qkv_net.weight");
-      up(&c.wo, p + "mhsa.o_net.weight");
-      up(&c.rnet, p + "mhsa.r_net.weight");
-      up(&c.rwb, p + "mhsa.r_w_bias");
-      up(&c.rrb, p + "mhsa.r_r_bias");
-      up(&c.cv_g, p + "conv.conv.0.weight");
-      up(&c.cv_be, p + "conv.conv.0.bias");
-      up(&c.pw1_w, p + "conv.conv.1.conv.weight");
-      up(&c.pw1_b, p + "conv.conv.1.conv.bias");
-      up(&c.pw2_w, p + "conv.conv.8.conv.weight");
-      up(&c.pw2_b, p + "conv.conv.8.conv.bias");
-      up(&c.norm_g, p + "norm.weight");
-      up(&c.norm_be, p + "norm.bias");
-      const auto& fr = get(p + "mhsa.pos_emb.inv_freq");
-      cf_inv_freq.insert(cf_inv_freq.end(), fr.begin(), fr.end());
-      std::vector<double> sc;
-      std::vector<float> mu, bi;
-      bn_fold(p + "conv.conv.5", CF_D, sc, mu, bi);
-      const auto& dw = get(p + "conv.conv.3.conv.weight");   // [144][1][7]
-      const auto& db = get(p + "conv.conv.3.conv.bias");
-      cf_dw_wt[b].resize(7 * CF_D);
-      cf_dw_b[b].resize(CF_D);
-      for (int ch_ = 0; ch_ < CF_D; ++ch_) {
-        for (int t = 0; t < 7; ++t) cf_dw_wt[b][t * CF_D + ch_] = (float)((double)dw[ch_ * 7 + t] * sc[ch_]);
-        cf_dw_b[b][ch_] = (float)(((double)db[ch_] - (double)mu[ch_]) * sc[ch_] + (double)bi[ch_]);
-      }
-      add((void**)&c.dw_wt, cf_dw_wt[b].data(), cf_dw_wt[b].size() * 4);
-      add((void**)&c.dw_b, cf_dw_b[b].data(), cf_dw_b[b].size() * 4);
-    }
-    add((void**)&W.cf_inv_freq, cf_inv_freq.data(), cf_inv_freq.size() * 4);
-  }
-  if (!g_wT.empty()) {
-    add((void**)&W.g_twiddle, g_tw.data(), g_tw.size() * 8);
-    add((void**)&W.g_window, g_win.data(), g_win.size() * 8);
-    add((void**)&W.g_weightsT, g_wT.data(), g_wT.size() * 8);
-  }
-  size_t total = 0;
-  for (auto& it : items) total += (it.bytes + 255) & ~size_t(255);
   if (h->blob) {
     (void)hipFree(h->blob);
     h->blob = nullptr;
+    h->w = DevWeights();
   }
-  HIP_TRY(h, hipMalloc(&h->blob, total));
-  h->blob_bytes = total;
-  std::vector<char> host(total, 0);
-  size_t off = 0;
-  for (auto& it : items) {
-    std::memcpy(host.data() + off, it.src, it.bytes);
-    *it.dst = static_cast<char*>(h->blob) + off;
-    off += (it.bytes + 255) & ~size_t(255);
-  }
-  HIP_TRY(h, hipMemcpy(h->blob, host.data(), total, hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMalloc(&h->blob, blob.image.size()));
+  h->blob_bytes = blob.image.size();
+  HIP_TRY(h, hipMemcpy(h->blob, blob.image.data(), blob.image.size(), hipMemcpyHostToDevice));
+  blob.bind(h->blob);   // sets w's pointers
+  h->w = w;
+  h->g_nfft = gg.nfft;
+  h->g_nwin = gg.nwin;
+  h->g_hop = gg.hop;
   if (!h->gru_err_host) {
     void* p = nullptr;
     HIP_TRY(h, hipHostMalloc(&p, 64, hipHostMallocMapped | hipHostMallocCoherent));
@@ -1555,7 +933,7 @@ static sedx_status forward_wave(sedx_handle* h, const float* d_wave, const int16
   p.sig_len = L;
   p.T = (int32_t)g.T;
   p.hop = h->cfg.hop_size;
-  p.twiddle = h->w.twiddle;
+  p.twiddle = reinterpret_cast<const float2*>(h->w.twiddle);
   p.window = h->w.window;
   p.mel_w = h->w.mel_w;
   p.mel_tab = h->w.mel_tab;
@@ -1644,7 +1022,7 @@ sedx_status sedx_gamma_features(sedx_handle* h, const float* d_audio, int64_t B,
   p.hop = h->g_hop;
   p.nfft = h->g_nfft;
   p.kp = gamma_kp(h->g_nfft);
-  p.twiddle = h->w.g_twiddle;
+  p.twiddle = reinterpret_cast<const double2*>(h->w.g_twiddle);
   p.window = h->w.g_window;
   p.weightsT = h->w.g_weightsT;
   p.mag = reinterpret_cast<double*>(base);
@@ -1768,7 +1146,7 @@ static sedx_status forward_windows_impl(sedx_handle* h, const float* d_audio, in
     p.sig_len = g.len;
     p.T = (int32_t)g.g.T;
     p.hop = h->cfg.hop_size;
-    p.twiddle = h->w.twiddle;
+    p.twiddle = reinterpret_cast<const float2*>(h->w.twiddle);
     p.window = h->w.window;
     p.mel_w = h->w.mel_w;
     p.mel_tab = h->w.mel_tab;

@@ -107,7 +107,7 @@ struct WinoGeom {
   static_assert(!C1 || (F == 64 && NT == 2 && PLP <= 64 * WAVES && UX <= WAVES && NBUF >= 3), "C1: block 1 (64 bins), a conv1 group per wave");
 };
 
-// Diagnostic builds only (tools/wino_b1_bench.cpp, tools/gpu_r04d.sh; never
+// Diagnostic builds only (tools/wino_b1_bench.cpp; never
 // the library): SEDX_WINO_STAMPS accumulates per-wave s_memtime intervals by
 // phase, from every wave of every 16th workgroup, into g_wino_stamps:
 //   [0] prologue  [1] item top (chunk 0 reads + transform, next item's DMA
@@ -1152,26 +1152,6 @@ void wino_stamps_rw(unsigned long long* h, bool reset) {
 }
 #endif
 
-// U = G g G^T per (input channel, output channel) in float64 from the
-// BN-folded weights, rounded once to fp32, packed [Cin/4][16 p][2 h][Cout][2 ks]
-// with channel 4 chunk + 2 h + ks (one 8-byte LDS read gives a lane both
-// k-steps of a position).
-void pack_conv_wino(const double* wf, int Cin, int Cout, float* Up) {
-  static const double Gm[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-  for (int o = 0; o < Cout; ++o)
-    for (int i = 0; i < Cin; ++i) {
-      const double* g = wf + ((size_t)o * Cin + i) * 9;
-      double tmp[4][3];
-      for (int a = 0; a < 4; ++a)
-        for (int y = 0; y < 3; ++y) tmp[a][y] = Gm[a][0] * g[0 * 3 + y] + Gm[a][1] * g[1 * 3 + y] + Gm[a][2] * g[2 * 3 + y];
-      const int chunk = i / 4, h = (i % 4) >> 1, ks = i & 1;
-      for (int a = 0; a < 4; ++a)
-        for (int c = 0; c < 4; ++c) {
-          const double u = tmp[a][0] * Gm[c][0] + tmp[a][1] * Gm[c][1] + tmp[a][2] * Gm[c][2];
-          const int p = 4 * a + c;
-          Up[((((size_t)chunk * 16 + p) * 2 + h) * Cout + o) * 2 + ks] = (float)u;
-        }
-    }
-}
+// pack_conv_wino (the host pack of U): weights.cpp
 
 }  // namespace sedx

@@ -1183,36 +1183,6 @@ void launch_c4_to_nhwc(const float* src, int B, int T, int F, int C, float* dst,
                      reinterpret_cast<const float4*>(src), T, F, C / 4, n, reinterpret_cast<float4*>(dst));
 }
 
-// U = G g G^T per (input channel, output channel) in float64 from the
-// BN-folded weights wf [Cout][Cin][9], rounded once to fp32, packed twice:
-// [Cout/64][Cin/4][36 p][4 k][16 m][4 nt] with output channel 64 group +
-// 16 nt + m and input channel 4 chunk + k (a chunk's slab is the LDS image;
-// lane l = 16 k + m reads its 4 channel tiles as one 16-byte word), then the
-// same values as [Cout/16][Cin/4][36 p][4 k][16 m] (16-channel items: a
-// chunk's 9 KiB slab of one channel tile).  Up: 2 Cin Cout 36 floats.
-void pack_conv_wino43(const double* wf, int Cin, int Cout, float* Up) {
-  static const double Gm[6][3] = {{1.0 / 4, 0, 0},
-                                  {-1.0 / 6, -1.0 / 6, -1.0 / 6},
-                                  {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                                  {1.0 / 24, 1.0 / 12, 1.0 / 6},
-                                  {1.0 / 24, -1.0 / 12, 1.0 / 6},
-                                  {0, 0, 1}};
-  const int nch = Cin / 4;
-  for (int o = 0; o < Cout; ++o)
-    for (int i = 0; i < Cin; ++i) {
-      const double* g = wf + ((size_t)o * Cin + i) * 9;
-      double tmp[6][3];
-      for (int a = 0; a < 6; ++a)
-        for (int y = 0; y < 3; ++y) tmp[a][y] = Gm[a][0] * g[0 * 3 + y] + Gm[a][1] * g[1 * 3 + y] + Gm[a][2] * g[2 * 3 + y];
-      const int grp = o / 64, nt = (o % 64) / 16, m = o % 16, chunk = i / 4, k = i % 4;
-      for (int a = 0; a < 6; ++a)
-        for (int c = 0; c < 6; ++c) {
-          const double u = tmp[a][0] * Gm[c][0] + tmp[a][1] * Gm[c][1] + tmp[a][2] * Gm[c][2];
-          const int p = 6 * a + c;
-          Up[(((((size_t)grp * nch + chunk) * 36 + p) * 4 + k) * 16 + m) * 4 + nt] = (float)u;
-          Up[(size_t)Cin * Cout * 36 + ((((size_t)(o / 16) * nch + chunk) * 36 + p) * 4 + k) * 16 + m] = (float)u;
-        }
-    }
-}
+// pack_conv_wino43 (the host packs of U): weights.cpp
 
 }  // namespace sedx

@@ -1210,8 +1210,6 @@ __global__ __launch_bounds__(256) void gamma_quant_kernel(GammaParams p) {
   }
 }
 
-int gamma_kp(int nfft) { return ((nfft / 2 + 1) + 31) / 32 * 32; }
-
 size_t gamma_workspace_bytes(int64_t B, int64_t T, int nfft) {
   auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
   return al((size_t)B * T * gamma_kp(nfft) * sizeof(double)) + al((size_t)B * 64 * T * sizeof(double)) +

@@ -11,7 +11,7 @@
 #include <cmath>
 #include <vector>
 
-#include "sedx_internal.h"
+#include "weights.h"
 
 namespace sedx {
 namespace {

@@ -19,15 +19,13 @@
 #include <vector>
 
 #include "../../include/sedx.h"
+// the host side of the weight contract: the constants the packing shares with
+// the kernels, DevWeights, and every packed layout (weights.cpp)
+#include "weights.h"
 
 namespace sedx {
 
 // ---- frontend -------------------------------------------------------------
-// logmel512_kernel: lane b of a frame's 16-lane row sums mel bands b, 31 - b,
-// 32 + b, 63 - b (slots q = 0..3, balanced widths) from a zero-padded table
-constexpr int FE16_MEL_MW = 36;
-constexpr int FE_MT_MAX_FLOATS = 8192;    // MFMA mel table limit (32 KB of LDS)
-inline int fe16_band_host(int b, int q) { return q == 0 ? b : q == 1 ? 31 - b : q == 2 ? 32 + b : 63 - b; }
 struct FrontendParams {
   const float* audio;       // base pointer (fp32 samples)
   const int16_t* audio_i16; // or int16 samples, dequantised x / 32767 on load (utilities.py:78-79)
@@ -82,10 +80,6 @@ struct GammaParams {
   unsigned long long* mm;  // [B][2] workspace: ordered max / min of db per clip
   float* out;              // [B][64][T] dequantised features
 };
-int gamma_kp(int nfft);
-// host: ERB weights [kp][nfilts] (zero rows past nfft/2), twiddles [2 nfft], window [nfft]
-void gamma_tables(double fs, int nfft, int nwin, int nfilts, double fmin, std::vector<double>& weightsT,
-                  int kp, std::vector<double>& twiddle, std::vector<double>& window);
 size_t gamma_workspace_bytes(int64_t B, int64_t T, int nfft);
 // spec_variant (nfft 2048): 0 the workgroup Stockham spectrum, 1 one wave per frame
 void launch_gamma(const GammaParams& p, hipStream_t s, int spec_variant = 0);
@@ -100,13 +94,11 @@ void launch_block1_exact(const float* xpad, int B, int T, const float* w1, const
                          const float* bias, float* out, const float* zero16, hipStream_t s);
 
 enum ConvEpi { EPI_STORE = 0, EPI_POOL2 = 1, EPI_FMEAN = 2 };
-// floats in the handle's device zero block (the halo DMA's source for pixels
-// outside the clip; the Winograd DMA walks it by up to Cin + 4 floats)
-constexpr int ZERO_BLOCK_FLOATS = 1024;
 constexpr int CONV_SCHED_INTS = 256;   // per conv launch: 8 tile-claim counters, 128 B apart
 // 3x3 conv (pad 1) + folded BN + ReLU (+ epilogue), implicit GEMM on fp32 MFMA.
 //  in [B][T][F][Cin] -> EPI_STORE: [B][T][F][Cout], EPI_POOL2: [B][T/2][F/2][Cout],
-//  EPI_FMEAN: [B][T][Cout].  wp = packed [Cin/4][9][2][Cout][2] (channel 2 ks + khalf), bias [Cout].
+//  EPI_FMEAN: [B][T][Cout].  wp = pack_conv_exact's [Cin/4][9][2][Cout][2] (channel 2 ks + khalf;
+//  weights.cpp), bias [Cout].
 //  F in {32, 16, 8}, Cout % 128 == 0 (block 1 runs launch_block1_exact).
 // zero16: >= 16 bytes of zeros in device memory (the halo DMA's source for
 // pixels outside the clip).
@@ -115,7 +107,7 @@ void launch_conv3x3(const float* in, int B, int T, int F, int Cin, int Cout,
                     const float* zero16, hipStream_t s);
 
 // Same contract as fp32 Winograd F(2x2, 3x3) (conv_wino.hip): U from
-// pack_conv_wino (wf = BN-folded weights [Cout][Cin][9] in float64);
+// pack_conv_wino (weights.cpp; wf = BN-folded weights [Cout][Cin][9] in float64);
 // F in {64, 32, 16, 8}, Cout % 32 == 0 (F = 64: block 1's conv2, fed by
 // launch_conv1_nhwc).
 // zero16 here: >= Cin + 4 floats of zeros; trash: >= 64 x 128 floats of device scratch; out-of-range epilogue stores land
@@ -126,11 +118,10 @@ void launch_conv3x3(const float* in, int B, int T, int F, int Cin, int Cout,
 void launch_conv3x3_wino(const float* in, int B, int T, int F, int Cin, int Cout,
                          const float* U, const float* bias, float* out, int epi,
                          const float* zero16, float* trash, hipStream_t s, int order = 0);
-void pack_conv_wino(const double* wf, int Cin, int Cout, float* U);   // U: Cin * Cout * 16 floats
 // Same contract as fp32 Winograd F(4x4,3x3) (conv_wino43.hip), blocks 2-4:
 // F in {32, 16, 8}, Cin % 8 == 0 and >= 16, Cout % 64 == 0 and <= 512; U43
-// from pack_conv_wino43 (2 Cin Cout 36 floats: the 64- and the 16-channel
-// item packs); nt_force: 0 = the launcher's choice of item shape, 4 =
+// from pack_conv_wino43 (weights.cpp; 2 Cin Cout 36 floats: the 64- and the
+// 16-channel item packs); nt_force: 0 = the launcher's choice of item shape, 4 =
 // 64-channel items, 1 = 16-channel items of 32 tiles, 2 = 16-channel items of
 // 16 tiles (F = 16 / 8, c4 only) — A/B and tests, all bit-identical; pixels outside the clip are
 // zero-filled by the buffer DMA's range check (no zero block); trash >= 64 x
@@ -145,7 +136,6 @@ void launch_conv3x3_wino43(const float* in, int B, int T, int F, int Cin, int Co
                            bool c4 = false, int nt_force = 0, int* sched = nullptr);
 // [B][C/4][T][F][4] -> [B][T][F][C] (stage captures of the C4 layers)
 void launch_c4_to_nhwc(const float* src, int B, int T, int F, int C, float* dst, hipStream_t s);
-void pack_conv_wino43(const double* wf, int Cin, int Cout, float* U);   // U: 2 * Cin * Cout * 36 floats
 // block 1 as one Winograd launch: conv1 (w1 [64][9] folded, b1 [64], ReLU)
 // computed into conv2's halo images in LDS, conv2 (U of block 1's conv2) +
 // bias + ReLU + 2x2 pool: X0 [B][T][64] -> [B][T/2][32][64]; bit-identical to
@@ -162,8 +152,8 @@ void launch_conv1_nhwc(const float* x0, int B, int T, const float* w1, const flo
 void launch_conv1_c4(const float* x0, int B, int T, const float* w1, const float* b1, float* out, hipStream_t s);
 
 // Same contract on bf16 MFMA with a 3-term hi/lo split (fp32-class accuracy).
-// wp = host-packed split weights [Cout/BN][Cin/16][9][BN][4 x 16 B] (BN = 64 if
-// Cout == 64 else 128), slots XOR-swizzled by ((n >> 2) & 3).
+// wp = pack_x3's split weights (weights.cpp) [Cout/BN][Cin/16][9][BN][4 x 16 B]
+// (BN = 64 if Cout == 64 else 128), slots XOR-swizzled by ((n >> 2) & 3).
 //
 // packed FP32: no kernel of this library contains packed FP32 VALU
 // instructions (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32); the Makefile
@@ -293,7 +283,7 @@ size_t block1_pad_floats(int B, int T);
 // C[M][N] = act(A[M][K] . W[N][K]^T + bias[N]);  act: 0 none, 1 relu
 void launch_linear(const float* A, int M, int K, const float* W, int N, const float* bias,
                    float* C, int act, hipStream_t s);
-// x3 (split-bf16 MFMA) GEMM, W pre-packed by the host (linear_x3.hip);
+// x3 (split-bf16 MFMA) GEMM, W packed by pack_x3 with one tap (weights.cpp; linear_x3.hip);
 // K % 32 == 0, N % BN == 0, BN in {64, 128}
 void launch_linear_x3(const float* A, int M, int K, const void* Wp, int N, int BN, const float* bias,
                       float* C, int act, hipStream_t s);
@@ -340,10 +330,6 @@ void launch_transpose_btd(const float* E, int B, int T, int D, float* out, hipSt
 
 // ---- Conformer encoder (conformer.hip) --------------------------------------
 // fp32 in every precision mode.  Activations [items * T][width], CF_D = 144.
-constexpr int CF_D = 144;        // adim
-constexpr int CF_FF = 576;       // eunits
-constexpr int CF_BLOCKS = 3;     // elayers
-constexpr int CF_MAX_T = 5000;   // rows of the positional table pe (PositionalEncoding max_len)
 enum CfEpi { CF_EPI_NONE = 0, CF_EPI_SWISH = 1, CF_EPI_HALF_RES = 2, CF_EPI_RES = 3 };
 // C[M][N] = epi(A[M][K] . W[N][K]^T + bias[N]) on fp32 MFMA; K % 144 == 0 or
 // K % 128 == 0, any N; bias nullable.  epi: NONE y, SWISH y sigmoid(y), HALF_RES 0.5 y + res,

@@ -1,0 +1,615 @@
+// state_dict -> packed device weights, host arithmetic only (weights.h).
+// Every layout a kernel reads is built here, beside the comment that states
+// it; tests/native/asan_driver.cpp reads each pack back the way its kernel
+// addresses it.
+#include "weights.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+
+namespace sedx {
+
+// ---- the model --------------------------------------------------------------
+// sedx_model -> (seq, head); false for an unknown model_type
+static bool model_parts(int32_t model_type, int* seq, int* head) {
+  switch (model_type) {
+    case SEDX_MODEL_GRU_FRAMEATT: *seq = SEQ_GRU, *head = HEAD_ATT; return true;
+    case SEDX_MODEL_TRANSFORMER_FRAMEATT: *seq = SEQ_MHA, *head = HEAD_ATT; return true;
+    case SEDX_MODEL_CNN_FRAMEMAX: *seq = SEQ_NONE, *head = HEAD_FC_MAX; return true;
+    case SEDX_MODEL_CNN_FRAMEAVG: *seq = SEQ_NONE, *head = HEAD_FC_AVG; return true;
+    case SEDX_MODEL_CNN_FRAMEATT: *seq = SEQ_NONE, *head = HEAD_ATT; return true;
+    case SEDX_MODEL_GRU_FRAMEAVG: *seq = SEQ_GRU, *head = HEAD_FC_AVG; return true;
+    case SEDX_MODEL_TRANSFORMER_FRAMEAVG: *seq = SEQ_MHA, *head = HEAD_FC_AVG; return true;
+    case SEDX_MODEL_CONFORMER_FRAMEATT: *seq = SEQ_CONFORMER, *head = HEAD_ATT; return true;
+    case SEDX_MODEL_CONFORMER_FRAMEAVG: *seq = SEQ_CONFORMER, *head = HEAD_FC_AVG; return true;
+    default: return false;
+  }
+}
+
+bool make_model(const sedx_config& cfg, Model* m) {
+  if (!model_parts(cfg.model_type, &m->seq, &m->head)) return false;
+  m->cfg = cfg;
+  m->hw = m->seq == SEQ_CONFORMER ? CF_D : 512;
+  m->nac = (((m->head == HEAD_ATT ? 2 : 1) * cfg.classes_num + 63) / 64) * 64;
+  return true;
+}
+
+bool ignored_key(const Model& m, const std::string& k) {
+  if (m.seq != SEQ_CONFORMER) return false;
+  return k == "classifier.weight" || k == "classifier.bias" || k == "linear_emb.weight" || k == "linear_emb.bias";
+}
+
+namespace {
+
+// The Conformer encoder's tensors, once: key suffix, shape, and the member
+// that receives the tensor as it stands in the state_dict (nullptr: read by
+// prepare_weights itself — the depthwise conv and its BatchNorm1d are folded,
+// inv_freq of the three blocks is joined).  expected_params and
+// prepare_weights both walk these tables; the upload order is the tables'.
+template <typename Dst>
+struct CfTensor {
+  const char* key;
+  std::vector<int64_t> shape;
+  Dst dst;
+};
+const CfTensor<float* DevWeights::*> CF_TOP[] = {
+    {"encoder.input_layer.0.weight", {CF_D, 512}, &DevWeights::cf_in_w},
+    {"encoder.input_layer.0.bias", {CF_D}, &DevWeights::cf_in_b},
+    {"encoder.input_layer.1.weight", {CF_D}, &DevWeights::cf_in_g},
+    {"encoder.input_layer.1.bias", {CF_D}, &DevWeights::cf_in_be},
+    {"encoder.input_layer.4.pe", {1, CF_MAX_T, CF_D}, &DevWeights::cf_pe},
+};
+// under <block>ffn1.feed_forward_module. and <block>ffn2.feed_forward_module.
+const CfTensor<float* (CfBlockWeights::*)[2]> CF_FFN[] = {
+    {"0.weight", {CF_D}, &CfBlockWeights::ffn_g},        {"0.bias", {CF_D}, &CfBlockWeights::ffn_be},
+    {"1.weight", {CF_FF, CF_D}, &CfBlockWeights::ffn_w1}, {"1.bias", {CF_FF}, &CfBlockWeights::ffn_b1},
+    {"4.weight", {CF_D, CF_FF}, &CfBlockWeights::ffn_w2}, {"4.bias", {CF_D}, &CfBlockWeights::ffn_b2},
+};
+// under encoder.conformer_blocks.<b>.
+const CfTensor<float* CfBlockWeights::*> CF_BLOCK[] = {
+    {"mhsa.layer_norm.weight", {CF_D}, &CfBlockWeights::att_g},
+    {"mhsa.layer_norm.bias", {CF_D}, &CfBlockWeights::att_be},
+    {"mhsa.qkv_net.weight", {3 * CF_D, CF_D}, &CfBlockWeights::wqkv},
+    {"mhsa.o_net.weight", {CF_D, CF_D}, &CfBlockWeights::wo},
+    {"mhsa.r_net.weight", {CF_D, CF_D}, &CfBlockWeights::rnet},
+    {"mhsa.r_w_bias", {4, CF_D / 4}, &CfBlockWeights::rwb},
+    {"mhsa.r_r_bias", {4, CF_D / 4}, &CfBlockWeights::rrb},
+    {"conv.conv.0.weight", {CF_D}, &CfBlockWeights::cv_g},
+    {"conv.conv.0.bias", {CF_D}, &CfBlockWeights::cv_be},
+    {"conv.conv.1.conv.weight", {2 * CF_D, CF_D, 1}, &CfBlockWeights::pw1_w},
+    {"conv.conv.1.conv.bias", {2 * CF_D}, &CfBlockWeights::pw1_b},
+    {"conv.conv.8.conv.weight", {CF_D, CF_D, 1}, &CfBlockWeights::pw2_w},
+    {"conv.conv.8.conv.bias", {CF_D}, &CfBlockWeights::pw2_b},
+    {"norm.weight", {CF_D}, &CfBlockWeights::norm_g},
+    {"norm.bias", {CF_D}, &CfBlockWeights::norm_be},
+    {"mhsa.pos_emb.inv_freq", {CF_D / 2}, nullptr},
+    {"conv.conv.3.conv.weight", {CF_D, 1, 7}, nullptr},
+    {"conv.conv.3.conv.bias", {CF_D}, nullptr},
+    {"conv.conv.5.weight", {CF_D}, nullptr},
+    {"conv.conv.5.bias", {CF_D}, nullptr},
+    {"conv.conv.5.running_mean", {CF_D}, nullptr},
+    {"conv.conv.5.running_var", {CF_D}, nullptr},
+};
+
+std::string cf_block_key(int b) { return "encoder.conformer_blocks." + std::to_string(b) + "."; }
+std::string cf_ffn_key(int b, int f) { return cf_block_key(b) + (f ? "ffn2" : "ffn1") + ".feed_forward_module."; }
+
+void add_bn(std::map<std::string, std::vector<int64_t>>& e, const std::string& p, int64_t n) {
+  for (const char* s : {".weight", ".bias", ".running_mean", ".running_var"}) e[p + s] = {n};
+}
+
+const int CONV_CH[5] = {1, 64, 128, 256, 512};
+
+}  // namespace
+
+std::map<std::string, std::vector<int64_t>> expected_params(const Model& m) {
+  std::map<std::string, std::vector<int64_t>> e;
+  const int64_t K = m.cfg.window_size / 2 + 1;
+  e["spectrogram_extractor.stft.conv_real.weight"] = {K, 1, m.cfg.window_size};
+  e["spectrogram_extractor.stft.conv_imag.weight"] = {K, 1, m.cfg.window_size};
+  e["logmel_extractor.melW"] = {K, m.cfg.mel_bins};
+  add_bn(e, "bn0", 64);
+  for (int k = 1; k <= 4; ++k) {
+    const std::string p = "conv_block" + std::to_string(k);
+    e[p + ".conv1.weight"] = {CONV_CH[k], CONV_CH[k - 1], 3, 3};
+    e[p + ".conv2.weight"] = {CONV_CH[k], CONV_CH[k], 3, 3};
+    add_bn(e, p + ".bn1", CONV_CH[k]);
+    add_bn(e, p + ".bn2", CONV_CH[k]);
+  }
+  const int64_t C = m.cfg.classes_num;
+  if (m.head == HEAD_ATT) {
+    e["att_block.att.weight"] = {C, m.hw, 1};
+    e["att_block.att.bias"] = {C};
+    e["att_block.cla.weight"] = {C, m.hw, 1};
+    e["att_block.cla.bias"] = {C};
+    add_bn(e, "att_block.bn_att", C);   // unused in forward (models.py:161-169)
+  } else {
+    e["fc.weight"] = {C, m.hw};         // nn.Linear(512, classes_num) (models.py:247, :332, :503, :921; 144: :1500)
+    e["fc.bias"] = {C};
+  }
+  if (m.seq == SEQ_GRU) {
+    for (const char* s : {"", "_reverse"}) {
+      e[std::string("gru.weight_ih_l0") + s] = {768, 512};
+      e[std::string("gru.weight_hh_l0") + s] = {768, 256};
+      e[std::string("gru.bias_ih_l0") + s] = {768};
+      e[std::string("gru.bias_hh_l0") + s] = {768};
+    }
+  } else if (m.seq == SEQ_MHA) {
+    for (const char* n : {"w_qs", "w_ks", "w_vs", "fc"}) {
+      e[std::string("multihead.") + n + ".weight"] = {512, 512};
+      e[std::string("multihead.") + n + ".bias"] = {512};
+    }
+    e["multihead.layer_norm.weight"] = {512};   // unused in forward (models.py:853-877)
+    e["multihead.layer_norm.bias"] = {512};
+  } else if (m.seq == SEQ_CONFORMER) {
+    for (const auto& t : CF_TOP) e[t.key] = t.shape;
+    for (int b = 0; b < CF_BLOCKS; ++b) {
+      for (int f = 0; f < 2; ++f)
+        for (const auto& t : CF_FFN) e[cf_ffn_key(b, f) + t.key] = t.shape;
+      for (const auto& t : CF_BLOCK) e[cf_block_key(b) + t.key] = t.shape;
+    }
+  }
+  return e;
+}
+
+// ---- the blob -----------------------------------------------------------------
+void WeightBlob::add_bytes(void** dst, const void* src, size_t bytes) {
+  const size_t off = image.size();
+  image.resize(off + ((bytes + 255) & ~size_t(255)), 0);
+  if (bytes) std::memcpy(image.data() + off, src, bytes);
+  regions.push_back({dst, off, bytes});
+}
+
+void WeightBlob::bind(void* device_base) const {
+  for (const Region& r : regions) *r.dst = static_cast<char*>(device_base) + r.off;
+}
+
+// ---- frontend tables ----------------------------------------------------------
+namespace {
+// the FFT frontend requires conv_real/imag = Re/Im(DFT) * window (stft.py:209-217);
+// row k = 0 of conv_real is the window since DFT[n, 0] = 1
+double check_windowed_dft(const std::vector<float>& wr, const std::vector<float>& wi, int nfft) {
+  const int K = nfft / 2 + 1;
+  double maxerr = 0;
+  const int rows[6] = {1, 2, K / 3, K / 2, K - 2, K - 1};
+  for (int r : rows)
+    for (int n = 0; n < nfft; ++n) {
+      const double ang = -2.0 * M_PI * (double)((int64_t)n * r % nfft) / nfft;
+      maxerr = std::max(maxerr, std::fabs(wr[(size_t)r * nfft + n] - std::cos(ang) * wr[n]));
+      maxerr = std::max(maxerr, std::fabs(wi[(size_t)r * nfft + n] - std::sin(ang) * wr[n]));
+    }
+  return maxerr;
+}
+
+struct MelTables {
+  std::vector<float> mel_w;               // the nonzero run of every band, packed
+  std::vector<int32_t> mel_off, mel_lo;   // [65] offsets into mel_w, [64] first fft bin
+  std::vector<float> mel_tab;             // [4][16][FE16_MEL_MW]
+  int32_t mel_wmax = 0;                   // widest band rounded up to 4
+  std::vector<float> mel_mt;              // n_fft 512 only
+  int32_t mt_klo[4] = {}, mt_ns[4] = {}, mt_off[4] = {};
+};
+MelTables mel_tables(const std::vector<float>& melW, int nfft) {   // melW [nfft/2 + 1][64]
+  const int K = nfft / 2 + 1;
+  MelTables t;
+  t.mel_off.resize(65);
+  t.mel_lo.resize(64);
+  for (int m = 0; m < 64; ++m) {
+    int lo = -1, hi = -1;
+    for (int k = 0; k < K; ++k)
+      if (melW[(size_t)k * 64 + m] != 0.0f) {
+        if (lo < 0) lo = k;
+        hi = k;
+      }
+    t.mel_off[m] = (int32_t)t.mel_w.size();
+    t.mel_lo[m] = lo < 0 ? 0 : lo;
+    if (lo >= 0)
+      for (int k = lo; k <= hi; ++k) t.mel_w.push_back(melW[(size_t)k * 64 + m]);
+  }
+  t.mel_off[64] = (int32_t)t.mel_w.size();
+  // the n_fft 512 kernel's band table: slot q of lane b is band
+  // fe16_band_host(b, q), zero-padded to FE16_MEL_MW bins
+  t.mel_tab.assign((size_t)4 * 16 * FE16_MEL_MW, 0.f);
+  for (int m = 0; m < 64; ++m) t.mel_wmax = std::max(t.mel_wmax, t.mel_off[m + 1] - t.mel_off[m]);
+  t.mel_wmax = (t.mel_wmax + 3) & ~3;
+  for (int q = 0; q < 4; ++q)
+    for (int b = 0; b < 16; ++b) {
+      const int m = fe16_band_host(b, q), wd = t.mel_off[m + 1] - t.mel_off[m];
+      for (int e = 0; e < std::min(wd, FE16_MEL_MW); ++e)
+        t.mel_tab[((size_t)q * 16 + b) * FE16_MEL_MW + e] = t.mel_w[t.mel_off[m] + e];
+    }
+  if (t.mel_w.empty()) t.mel_w.push_back(0.f);
+  // the MFMA mel path's table (n_fft 512): per 16-band tile j the bin range
+  // its bands cover, in 4-bin steps: [step][4 bins][16 bands] of melW (zero
+  // outside a band, and past the last bin)
+  if (nfft == 512) {
+    for (int j = 0; j < 4; ++j) {
+      int klo = K, khi = -1;
+      for (int m = 16 * j; m < 16 * j + 16; ++m) {
+        const int wd = t.mel_off[m + 1] - t.mel_off[m];
+        if (wd <= 0) continue;
+        klo = std::min(klo, t.mel_lo[m]);
+        khi = std::max(khi, t.mel_lo[m] + wd - 1);
+      }
+      const int ns = khi < klo ? 0 : (khi - klo + 1 + 3) / 4;
+      t.mt_klo[j] = ns ? klo : 0;
+      t.mt_ns[j] = ns;
+      t.mt_off[j] = (int32_t)t.mel_mt.size();
+      for (int st = 0; st < ns; ++st)
+        for (int kk = 0; kk < 4; ++kk)
+          for (int n = 0; n < 16; ++n) {
+            const int k = klo + 4 * st + kk, m = 16 * j + n;
+            t.mel_mt.push_back(k < K ? melW[(size_t)k * 64 + m] : 0.f);
+          }
+    }
+  }
+  return t;
+}
+
+// eval-mode BatchNorm of prefix p: scale = weight / sqrt(var + 1e-5) in float64, mean, bias
+void bn_fold(const Params& P, const std::string& p, int n, std::vector<double>& sc, std::vector<float>& mu,
+             std::vector<float>& bi) {
+  const auto& g = P.at(p + ".weight").data;
+  const auto& b = P.at(p + ".bias").data;
+  const auto& m = P.at(p + ".running_mean").data;
+  const auto& v = P.at(p + ".running_var").data;
+  sc.resize(n);
+  mu.resize(n);
+  bi.resize(n);
+  for (int i = 0; i < n; ++i) {
+    sc[i] = (double)g[i] / std::sqrt((double)v[i] + 1e-5);
+    mu[i] = m[i];
+    bi[i] = b[i];
+  }
+}
+
+}  // namespace
+
+// ---- conv / linear layouts ----------------------------------------------------
+// exact direct conv (conv.hip): [Cin/4][9][khalf 2][Cout][ks 2] with channel
+// 2 ks + khalf of a 4-channel chunk (the MFMA B fragments of both k-steps are
+// one 8-byte LDS read)
+void pack_conv_exact(const double* wf, int Cin, int Cout, float* out) {
+  for (int o = 0; o < Cout; ++o)
+    for (int i = 0; i < Cin; ++i)
+      for (int t = 0; t < 9; ++t) {
+        const int chunk = i / 4, kc = i % 4, ks = kc >> 1, kh = kc & 1;
+        out[((((size_t)chunk * 9 + t) * 2 + kh) * Cout + o) * 2 + ks] = (float)wf[((size_t)o * Cin + i) * 9 + t];
+      }
+}
+
+static void split_bf16(float x, uint16_t* hi, uint16_t* lo) {
+  auto rne = [](float v) -> uint32_t {
+    uint32_t u;
+    std::memcpy(&u, &v, 4);
+    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+  };
+  const uint32_t hb = rne(x), hbits = hb << 16;
+  float hf;
+  std::memcpy(&hf, &hbits, 4);
+  *hi = (uint16_t)hb;
+  *lo = (uint16_t)rne(x - hf);
+}
+
+// 3xbf16 split pack (conv_x3.hip, linear_x3.hip): w [N][K][taps] ->
+// [N/BN][K/16][taps][BN][4 slots x 8 bf16]: a record holds 16 input channels
+// of one output channel n, hi halves in slots 0-1 and lo halves in slots 2-3,
+// slot c stored at c ^ ((n >> 2) & 3).  The linear layers are the layout with
+// a single tap.
+std::vector<uint16_t> pack_x3(const float* w, int N, int K, int taps, int BN) {
+  std::vector<uint16_t> px((size_t)N * K * taps * 2, 0);
+  for (int o = 0; o < N; ++o)
+    for (int i = 0; i < K; ++i)
+      for (int t = 0; t < taps; ++t) {
+        const int nt = o / BN, n = o % BN, chunk = i / 16, k = i % 16, sw = (n >> 2) & 3;
+        const size_t rec = ((((size_t)nt * (K / 16) + chunk) * taps + t) * BN + n) * 32;
+        split_bf16(w[((size_t)o * K + i) * taps + t], &px[rec + 8 * ((k / 8) ^ sw) + (k % 8)],
+                   &px[rec + 8 * ((2 + k / 8) ^ sw) + (k % 8)]);
+      }
+  return px;
+}
+
+// Winograd F(2x2,3x3) (conv_wino.hip): U = G g G^T per (input channel, output
+// channel) in float64 from the BN-folded weights, rounded once to fp32, packed
+// [Cin/4][16 p][2 h][Cout][2 ks] with channel 4 chunk + 2 h + ks (one 8-byte
+// LDS read gives a lane both k-steps of a position).
+void pack_conv_wino(const double* wf, int Cin, int Cout, float* Up) {
+  static const double Gm[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+  for (int o = 0; o < Cout; ++o)
+    for (int i = 0; i < Cin; ++i) {
+      const double* g = wf + ((size_t)o * Cin + i) * 9;
+      double tmp[4][3];
+      for (int a = 0; a < 4; ++a)
+        for (int y = 0; y < 3; ++y) tmp[a][y] = Gm[a][0] * g[0 * 3 + y] + Gm[a][1] * g[1 * 3 + y] + Gm[a][2] * g[2 * 3 + y];
+      const int chunk = i / 4, h = (i % 4) >> 1, ks = i & 1;
+      for (int a = 0; a < 4; ++a)
+        for (int c = 0; c < 4; ++c) {
+          const double u = tmp[a][0] * Gm[c][0] + tmp[a][1] * Gm[c][1] + tmp[a][2] * Gm[c][2];
+          const int p = 4 * a + c;
+          Up[((((size_t)chunk * 16 + p) * 2 + h) * Cout + o) * 2 + ks] = (float)u;
+        }
+    }
+}
+
+// Winograd F(4x4,3x3) (conv_wino43.hip): U = G g G^T as above, packed twice:
+// [Cout/64][Cin/4][36 p][4 k][16 m][4 nt] with output channel 64 group +
+// 16 nt + m and input channel 4 chunk + k (a chunk's slab is the LDS image;
+// lane l = 16 k + m reads its 4 channel tiles as one 16-byte word), then the
+// same values as [Cout/16][Cin/4][36 p][4 k][16 m] (16-channel items: a
+// chunk's 9 KiB slab of one channel tile).  Up: 2 Cin Cout 36 floats.
+void pack_conv_wino43(const double* wf, int Cin, int Cout, float* Up) {
+  static const double Gm[6][3] = {{1.0 / 4, 0, 0},
+                                  {-1.0 / 6, -1.0 / 6, -1.0 / 6},
+                                  {-1.0 / 6, 1.0 / 6, -1.0 / 6},
+                                  {1.0 / 24, 1.0 / 12, 1.0 / 6},
+                                  {1.0 / 24, -1.0 / 12, 1.0 / 6},
+                                  {0, 0, 1}};
+  const int nch = Cin / 4;
+  for (int o = 0; o < Cout; ++o)
+    for (int i = 0; i < Cin; ++i) {
+      const double* g = wf + ((size_t)o * Cin + i) * 9;
+      double tmp[6][3];
+      for (int a = 0; a < 6; ++a)
+        for (int y = 0; y < 3; ++y) tmp[a][y] = Gm[a][0] * g[0 * 3 + y] + Gm[a][1] * g[1 * 3 + y] + Gm[a][2] * g[2 * 3 + y];
+      const int grp = o / 64, nt = (o % 64) / 16, m = o % 16, chunk = i / 4, k = i % 4;
+      for (int a = 0; a < 6; ++a)
+        for (int c = 0; c < 6; ++c) {
+          const double u = tmp[a][0] * Gm[c][0] + tmp[a][1] * Gm[c][1] + tmp[a][2] * Gm[c][2];
+          const int p = 6 * a + c;
+          Up[(((((size_t)grp * nch + chunk) * 36 + p) * 4 + k) * 16 + m) * 4 + nt] = (float)u;
+          Up[(size_t)Cin * Cout * 36 + ((((size_t)(o / 16) * nch + chunk) * 36 + p) * 4 + k) * 16 + m] = (float)u;
+        }
+    }
+}
+
+// head projection [nac][hw] and its bias [nac], rows zero-padded to nac:
+// att | cla (row c, row C + c), or fc
+void pack_head(const Model& m, const Params& P, std::vector<float>* wac, std::vector<float>* bac) {
+  const size_t C = m.cfg.classes_num, hw = m.hw;
+  wac->assign((size_t)m.nac * hw, 0.f);
+  bac->assign(m.nac, 0.f);
+  if (m.head != HEAD_ATT) {
+    const auto& wf = P.at("fc.weight").data;
+    const auto& bf = P.at("fc.bias").data;
+    std::copy(wf.begin(), wf.end(), wac->begin());
+    std::copy(bf.begin(), bf.end(), bac->begin());
+  } else {
+    const auto& wa = P.at("att_block.att.weight").data;
+    const auto& ba = P.at("att_block.att.bias").data;
+    const auto& wc = P.at("att_block.cla.weight").data;
+    const auto& bc = P.at("att_block.cla.bias").data;
+    std::copy(wa.begin(), wa.end(), wac->begin());
+    std::copy(wc.begin(), wc.end(), wac->begin() + C * hw);
+    std::copy(ba.begin(), ba.end(), bac->begin());
+    std::copy(bc.begin(), bc.end(), bac->begin() + C);
+  }
+}
+
+// ---- everything ---------------------------------------------------------------
+namespace {
+sedx_status fail(std::string* err, sedx_status st, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  if (err) *err = buf;
+  return st;
+}
+}  // namespace
+
+sedx_status prepare_weights(const Model& m, const Params& P, DevWeights* Wp, WeightBlob* blob, GammaGeom* gamma,
+                            std::string* err) {
+  for (const auto& kv : expected_params(m))
+    if (!P.count(kv.first)) return fail(err, SEDX_EKEY, "missing key in state_dict: %s", kv.first.c_str());
+  auto get = [&](const std::string& k) -> const std::vector<float>& { return P.at(k).data; };
+  const int nfft = m.cfg.window_size;
+  const int hw = m.hw, nac = m.nac;
+  DevWeights& W = *Wp;
+  W = DevWeights();
+  *blob = WeightBlob();
+  *gamma = GammaGeom();
+  {
+    // the seven packed conv layers (exact, x3, F(2x2) and F(4x4) packs: 1 + 1 +
+    // 16/9 + 8 times the weights) are nearly all of the image
+    size_t conv = 0;
+    for (int k = 1; k <= 4; ++k) conv += (size_t)CONV_CH[k] * ((k > 1 ? CONV_CH[k - 1] : 0) + CONV_CH[k]) * 9;
+    blob->image.reserve(conv * 4 * 12 + (size_t(16) << 20));
+  }
+
+  // ---- frontend: twiddles, the window, mel tables, bn0 ----
+  const auto& wr = get("spectrogram_extractor.stft.conv_real.weight");
+  const double dft_err = check_windowed_dft(wr, get("spectrogram_extractor.stft.conv_imag.weight"), nfft);
+  if (dft_err > 1e-5)
+    return fail(err, SEDX_EINVAL, "STFT conv weights are not a windowed DFT (max err %.3g); "
+                                  "the FFT frontend cannot reproduce them", dft_err);
+  {
+    std::vector<float> tw(2 * nfft);
+    for (int k = 0; k < nfft; ++k) {
+      tw[2 * k] = (float)std::cos(-2.0 * M_PI * k / nfft);
+      tw[2 * k + 1] = (float)std::sin(-2.0 * M_PI * k / nfft);
+    }
+    blob->add(&W.twiddle, tw.data(), tw.size());
+    blob->add(&W.window, wr.data(), (size_t)nfft);
+    const MelTables mt = mel_tables(get("logmel_extractor.melW"), nfft);
+    blob->add(&W.mel_w, mt.mel_w.data(), mt.mel_w.size());
+    blob->add(&W.mel_tab, mt.mel_tab.data(), mt.mel_tab.size());
+    if (!mt.mel_mt.empty() && mt.mel_mt.size() <= (size_t)FE_MT_MAX_FLOATS) {
+      blob->add(&W.mel_mt, mt.mel_mt.data(), mt.mel_mt.size());
+      std::copy(mt.mt_klo, mt.mt_klo + 4, W.mt_klo);
+      std::copy(mt.mt_ns, mt.mt_ns + 4, W.mt_ns);
+      std::copy(mt.mt_off, mt.mt_off + 4, W.mt_off);
+      W.mt_floats = (int32_t)mt.mel_mt.size();
+    }
+    W.mel_wmax = mt.mel_wmax;
+    blob->add(&W.mel_off, mt.mel_off.data(), mt.mel_off.size());
+    blob->add(&W.mel_lo, mt.mel_lo.data(), mt.mel_lo.size());
+    std::vector<double> s0;
+    std::vector<float> mu0, bi0, sc0f(64);
+    bn_fold(P, "bn0", 64, s0, mu0, bi0);
+    for (int i = 0; i < 64; ++i) sc0f[i] = (float)s0[i];
+    blob->add(&W.bn0_scale, sc0f.data(), 64);
+    blob->add(&W.bn0_mean, mu0.data(), 64);
+    blob->add(&W.bn0_bias, bi0.data(), 64);
+  }
+
+  // ---- conv stack: BN folded into the weights in float64, then each layout ----
+  for (int k = 1; k <= 4; ++k)
+    for (int j = 1; j <= 2; ++j) {
+      const std::string p = "conv_block" + std::to_string(k);
+      const int cin = (j == 1) ? CONV_CH[k - 1] : CONV_CH[k], cout = CONV_CH[k];
+      const auto& wt = get(p + ".conv" + std::to_string(j) + ".weight");
+      std::vector<double> sc;
+      std::vector<float> mu, bi;
+      bn_fold(P, p + ".bn" + std::to_string(j), cout, sc, mu, bi);
+      std::vector<float> bias(cout);
+      for (int o = 0; o < cout; ++o) bias[o] = (float)((double)bi[o] - (double)mu[o] * sc[o]);
+      std::vector<double> wf((size_t)cout * cin * 9);
+      for (int o = 0; o < cout; ++o)
+        for (size_t q = 0; q < (size_t)cin * 9; ++q) wf[(size_t)o * cin * 9 + q] = wt[(size_t)o * cin * 9 + q] * sc[o];
+      std::vector<float> wff(wf.begin(), wf.end());   // rounded once: the direct conv1 and the x3 split read it
+      if (k == 1 && j == 1) {
+        // block 1's conv1 (Cin 1): [64][9], and [tap][64] (channel pairs adjacent)
+        std::vector<float> c1wt(9 * 64);
+        for (int o = 0; o < 64; ++o)
+          for (int t = 0; t < 9; ++t) c1wt[t * 64 + o] = wff[o * 9 + t];
+        blob->add(&W.c1_w, wff.data(), wff.size());
+        blob->add(&W.c1_wt, c1wt.data(), c1wt.size());
+        blob->add(&W.c1_b, bias.data(), bias.size());
+        const std::vector<float> zeros(std::max(ZERO_BLOCK_FLOATS, 64 * 128), 0.f);
+        blob->add(&W.zero, zeros.data(), (size_t)ZERO_BLOCK_FLOATS);   // >= Cin + 4 floats: the Winograd halo DMA steps through it
+        blob->add(&W.trash, zeros.data(), (size_t)64 * 128);
+        continue;
+      }
+      const int idx = 2 * (k - 1) + (j - 1);
+      std::vector<float> pk((size_t)cin * 9 * cout);
+      pack_conv_exact(wf.data(), cin, cout, pk.data());
+      blob->add(&W.wp[idx], pk.data(), pk.size());
+      blob->add(&W.cb[idx], bias.data(), bias.size());
+      const std::vector<uint16_t> px = pack_x3(wff.data(), cout, cin, 9, cout == 64 ? 64 : 128);
+      blob->add(&W.wx3[idx], px.data(), px.size());
+      pk.assign((size_t)cin * cout * 16, 0.f);
+      pack_conv_wino(wf.data(), cin, cout, pk.data());
+      blob->add(&W.wu[idx], pk.data(), pk.size());
+      // block 1's conv2 and blocks 2-4: the F(4x4,3x3) pack as well
+      pk.assign((size_t)2 * cin * cout * 36, 0.f);
+      pack_conv_wino43(wf.data(), cin, cout, pk.data());
+      blob->add(&W.wu43[idx], pk.data(), pk.size());
+    }
+
+  // ---- sequence layer ----
+  std::vector<float> w_ih, wqkv;   // kept for their x3 packs, which follow the head in the image
+  if (m.seq == SEQ_GRU) {
+    std::vector<float> b_ih(1536), whhT(2 * 256 * 768), whh_nat, bhh(2 * 768);
+    w_ih.resize(1536 * 512);
+    const char* sfx[2] = {"", "_reverse"};
+    for (int d = 0; d < 2; ++d) {
+      const auto& wih = get(std::string("gru.weight_ih_l0") + sfx[d]);
+      const auto& whh = get(std::string("gru.weight_hh_l0") + sfx[d]);
+      const auto& bi = get(std::string("gru.bias_ih_l0") + sfx[d]);
+      const auto& bh = get(std::string("gru.bias_hh_l0") + sfx[d]);
+      std::copy(wih.begin(), wih.end(), w_ih.begin() + (size_t)d * 768 * 512);
+      std::copy(bi.begin(), bi.end(), b_ih.begin() + d * 768);
+      std::copy(bh.begin(), bh.end(), bhh.begin() + d * 768);
+      for (int r = 0; r < 768; ++r)
+        for (int q = 0; q < 256; ++q) whhT[((size_t)d * 256 + q) * 768 + r] = whh[(size_t)r * 256 + q];
+      whh_nat.insert(whh_nat.end(), whh.begin(), whh.end());
+    }
+    blob->add(&W.w_ih, w_ih.data(), w_ih.size());
+    blob->add(&W.b_ih, b_ih.data(), b_ih.size());
+    blob->add(&W.whhT, whhT.data(), whhT.size());
+    blob->add(&W.whh, whh_nat.data(), whh_nat.size());
+    blob->add(&W.bhh, bhh.data(), bhh.size());
+  } else if (m.seq == SEQ_MHA) {
+    std::vector<float> bqkv(1536);
+    wqkv.resize(1536 * 512);
+    const char* nm[3] = {"w_qs", "w_ks", "w_vs"};
+    for (int i = 0; i < 3; ++i) {
+      const auto& ww = get(std::string("multihead.") + nm[i] + ".weight");
+      const auto& bb = get(std::string("multihead.") + nm[i] + ".bias");
+      std::copy(ww.begin(), ww.end(), wqkv.begin() + (size_t)i * 512 * 512);
+      std::copy(bb.begin(), bb.end(), bqkv.begin() + i * 512);
+    }
+    blob->add(&W.wqkv, wqkv.data(), wqkv.size());
+    blob->add(&W.bqkv, bqkv.data(), bqkv.size());
+    blob->add(&W.wfc, get("multihead.fc.weight").data(), (size_t)512 * 512);
+    blob->add(&W.bfc, get("multihead.fc.bias").data(), (size_t)512);
+  }
+
+  std::vector<float> wac, bac;
+  pack_head(m, P, &wac, &bac);
+  blob->add(&W.wac, wac.data(), wac.size());
+  blob->add(&W.bac, bac.data(), bac.size());
+
+  // ---- x3 packs of the linear layers ----
+  auto add_x3 = [&](void** dst, const float* w, int N, int BN) {
+    const std::vector<uint16_t> px = pack_x3(w, N, 512, 1, BN);
+    blob->add(dst, px.data(), px.size());
+  };
+  if (m.seq == SEQ_GRU) {
+    add_x3(&W.w_ih_x3, w_ih.data(), 1536, 128);
+  } else if (m.seq == SEQ_MHA) {
+    add_x3(&W.wqkv_x3, wqkv.data(), 1536, 128);
+    add_x3(&W.wfc_x3, get("multihead.fc.weight").data(), 512, 128);
+  }
+  if (hw == 512) add_x3(&W.wac_x3, wac.data(), nac, 64);   // the 144-wide projection runs fp32 in every mode
+
+  // ---- Conformer encoder: the state_dict's own tensors (the tables above),
+  // except the depthwise conv with its BatchNorm1d folded in (eval mode, eps 1e-5) ----
+  if (m.seq == SEQ_CONFORMER) {
+    auto up = [&](float** dst, const std::string& k) {
+      const auto& v = get(k);
+      blob->add(dst, v.data(), v.size());
+    };
+    for (const auto& t : CF_TOP) up(&(W.*t.dst), t.key);
+    std::vector<float> inv_freq;
+    for (int b = 0; b < CF_BLOCKS; ++b) {
+      const std::string p = cf_block_key(b);
+      CfBlockWeights& c = W.cf[b];
+      for (int f = 0; f < 2; ++f)
+        for (const auto& t : CF_FFN) up(&(c.*t.dst)[f], cf_ffn_key(b, f) + t.key);
+      for (const auto& t : CF_BLOCK)
+        if (t.dst) up(&(c.*t.dst), p + t.key);
+      const auto& fr = get(p + "mhsa.pos_emb.inv_freq");
+      inv_freq.insert(inv_freq.end(), fr.begin(), fr.end());
+      std::vector<double> sc;
+      std::vector<float> mu, bi;
+      bn_fold(P, p + "conv.conv.5", CF_D, sc, mu, bi);
+      const auto& dw = get(p + "conv.conv.3.conv.weight");   // [144][1][7]
+      const auto& db = get(p + "conv.conv.3.conv.bias");
+      std::vector<float> dw_wt(7 * CF_D), dw_b(CF_D);
+      for (int ch = 0; ch < CF_D; ++ch) {
+        for (int t = 0; t < 7; ++t) dw_wt[t * CF_D + ch] = (float)((double)dw[ch * 7 + t] * sc[ch]);
+        dw_b[ch] = (float)(((double)db[ch] - (double)mu[ch]) * sc[ch] + (double)bi[ch]);
+      }
+      blob->add(&c.dw_wt, dw_wt.data(), dw_wt.size());
+      blob->add(&c.dw_b, dw_b.data(), dw_b.size());
+    }
+    blob->add(&W.cf_inv_freq, inv_freq.data(), inv_freq.size());
+  }
+
+  // ---- gammatone tables (float64, numpy operation order: gamma_weights.cpp) ----
+  if (m.cfg.feature_type == SEDX_FEATURE_GAMMA) {
+    // fft_gtgram (fftweight.py:151-152) + gtgram_strides (gtgram.py:23-40)
+    const double fs = m.cfg.sample_rate;
+    const double win_t = (double)m.cfg.window_size / fs, hop_t = (double)m.cfg.hop_size / fs;
+    const int nfft_g = (int)std::pow(2.0, std::ceil(std::log2(2 * win_t * fs)));
+    auto rhaz = [](double x) { return (x > 0 ? 1.0 : (x < 0 ? -1.0 : 0.0)) * std::floor(std::fabs(x) + 0.5); };
+    if (nfft_g != 512 && nfft_g != 1024 && nfft_g != 2048)
+      return fail(err, SEDX_EINVAL, "gammatone nfft %d unsupported", nfft_g);
+    gamma->nfft = nfft_g;
+    gamma->nwin = (int)rhaz(win_t * fs);
+    gamma->hop = (int)rhaz(hop_t * fs);
+    std::vector<double> g_tw, g_win, g_wT;
+    gamma_tables(fs, nfft_g, gamma->nwin, 64, m.cfg.fmin, g_wT, gamma_kp(nfft_g), g_tw, g_win);
+    blob->add(&W.g_twiddle, g_tw.data(), g_tw.size());
+    blob->add(&W.g_window, g_win.data(), g_win.size());
+    blob->add(&W.g_weightsT, g_wT.data(), g_wT.size());
+  }
+  return SEDX_OK;
+}
+
+}  // namespace sedx

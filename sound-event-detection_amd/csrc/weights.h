@@ -1,0 +1,185 @@
+// Host side of the weight contract between the state_dict and the kernels:
+// what a model expects, the device weight table and the packed layouts
+// (weights.cpp, gamma_weights.cpp).  Plain C++: no HIP header, so the packing
+// builds and runs without a GPU (tests/native/asan_driver.cpp).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/sedx.h"
+
+namespace sedx {
+
+// ---- constants shared with the kernels ------------------------------------
+// logmel512_kernel: lane b of a frame's 16-lane row sums mel bands b, 31 - b,
+// 32 + b, 63 - b (slots q = 0..3, balanced widths) from a zero-padded table
+constexpr int FE16_MEL_MW = 36;
+constexpr int FE_MT_MAX_FLOATS = 8192;    // MFMA mel table limit (32 KB of LDS)
+inline int fe16_band_host(int b, int q) { return q == 0 ? b : q == 1 ? 31 - b : q == 2 ? 32 + b : 63 - b; }
+// floats in the handle's device zero block (the halo DMA's source for pixels
+// outside the clip; the Winograd DMA walks it by up to Cin + 4 floats)
+constexpr int ZERO_BLOCK_FLOATS = 1024;
+// Conformer encoder (conformer.hip)
+constexpr int CF_D = 144;        // adim
+constexpr int CF_FF = 576;       // eunits
+constexpr int CF_BLOCKS = 3;     // elayers
+constexpr int CF_MAX_T = 5000;   // rows of the positional table pe (PositionalEncoding max_len)
+
+// ---- the model ------------------------------------------------------------
+// a model = the CNN trunk, then a sequence layer, then a head
+enum SeqKind { SEQ_NONE = 0, SEQ_GRU = 1, SEQ_MHA = 2, SEQ_CONFORMER = 3 };
+enum HeadKind { HEAD_ATT = 0, HEAD_FC_AVG = 1, HEAD_FC_MAX = 2 };
+
+struct Tensor {
+  std::vector<int64_t> shape;
+  std::vector<float> data;
+};
+using Params = std::map<std::string, Tensor>;
+
+// what sedx_create derives from the config
+struct Model {
+  sedx_config cfg{};
+  int seq = SEQ_GRU;   // what follows the CNN trunk
+  int head = HEAD_ATT; // the head that reads its output
+  int hw = 512;        // width of the head's input: 512, or 144 after the Conformer encoder
+  int nac = 64;        // rows of the head projection: att|cla (2C) or fc (C), rounded up to 64
+};
+// cfg -> Model (seq, head, hw, nac); false for an unknown model_type
+bool make_model(const sedx_config& cfg, Model* m);
+// keys of modules the Conformer models build and never call at inference
+// (models.py:1290-1300, :1505-1515): accepted with any shape, not stored
+bool ignored_key(const Model& m, const std::string& k);
+// every state_dict key the model reads, with its shape
+std::map<std::string, std::vector<int64_t>> expected_params(const Model& m);
+
+// ---- the device weight table ----------------------------------------------
+// one ConformerBlock (conformer_block.py:8-24); every matrix in its
+// state_dict layout [out][in]
+struct CfBlockWeights {
+  float* ffn_g[2] = {};    // ffn1 / ffn2: LayerNorm weight, bias [144]
+  float* ffn_be[2] = {};
+  float* ffn_w1[2] = {};   // [576][144]
+  float* ffn_b1[2] = {};
+  float* ffn_w2[2] = {};   // [144][576]
+  float* ffn_b2[2] = {};
+  float* att_g = nullptr;  // mhsa.layer_norm
+  float* att_be = nullptr;
+  float* wqkv = nullptr;   // [432][144]
+  float* wo = nullptr;     // [144][144]
+  float* rnet = nullptr;   // [144][144]
+  float* rwb = nullptr;    // [4][36]
+  float* rrb = nullptr;
+  float* cv_g = nullptr;   // conv module's LayerNorm
+  float* cv_be = nullptr;
+  float* pw1_w = nullptr;  // [288][144]
+  float* pw1_b = nullptr;
+  float* dw_wt = nullptr;  // [7][144]: depthwise taps x BN scale, tap-major
+  float* dw_b = nullptr;   // [144]: folded bias
+  float* pw2_w = nullptr;  // [144][144]
+  float* pw2_b = nullptr;
+  float* norm_g = nullptr; // the block's final LayerNorm
+  float* norm_be = nullptr;
+};
+
+struct DevWeights {
+  float* twiddle = nullptr;   // [n_fft][2] exp(-2 pi i m / n_fft)
+  float* window = nullptr;
+  float* mel_w = nullptr;
+  float* mel_tab = nullptr;   // logmel512_kernel's per-(slot, lane) band weights
+  float* mel_mt = nullptr;    // logmel512_kernel's MFMA mel table (FrontendParams::mel_mt)
+  int32_t mt_klo[4] = {}, mt_ns[4] = {}, mt_off[4] = {}, mt_floats = 0;
+  int32_t mel_wmax = 0;
+  int32_t* mel_off = nullptr;
+  int32_t* mel_lo = nullptr;
+  float* bn0_scale = nullptr;
+  float* bn0_mean = nullptr;
+  float* bn0_bias = nullptr;
+  float* c1_w = nullptr;
+  float* c1_wt = nullptr;
+  float* c1_b = nullptr;
+  float* zero = nullptr;   // ZERO_BLOCK_FLOATS zeros (LDS-DMA source of out-of-clip halo pixels)
+  float* trash = nullptr;  // 32 KB write-only scratch (the Winograd kernel's dummy / out-of-range stores)
+  float* wp[8] = {};    // packed conv weights: block k conv j -> index 2(k-1)+(j-1); [0] unused
+  float* cb[8] = {};    // folded biases
+  void* wx3[8] = {};    // split bf16 hi/lo packs for conv3x3_x3 (same indices)
+  float* wu[8] = {};    // Winograd U = G g G^T packs for conv3x3_wino (same indices)
+  float* wu43[8] = {};  // F(4x4,3x3) U packs for conv3x3_wino43 (block 1's conv2: 1, blocks 2-4: 2..7)
+  float* w_ih = nullptr;   // [1536][512]
+  float* b_ih = nullptr;   // [1536]
+  float* whhT = nullptr;   // [2][256][768]
+  float* whh = nullptr;    // [2][768][256] (cooperative recurrence)
+  float* bhh = nullptr;    // [2][768]
+  float* wqkv = nullptr;   // [1536][512]
+  float* bqkv = nullptr;
+  float* wfc = nullptr;    // [512][512]
+  float* bfc = nullptr;
+  float* wac = nullptr;    // [nac][hw]
+  float* bac = nullptr;
+  // Conformer encoder (fp32 in every mode)
+  float* cf_in_w = nullptr;      // [144][512]
+  float* cf_in_b = nullptr;
+  float* cf_in_g = nullptr;      // input layer's LayerNorm
+  float* cf_in_be = nullptr;
+  float* cf_pe = nullptr;        // [5000][144] (the state_dict's buffer)
+  float* cf_inv_freq = nullptr;  // [3][72]
+  CfBlockWeights cf[CF_BLOCKS];
+  // x3 (split bf16) packs of the linear weights for linear_x3.hip
+  void* w_ih_x3 = nullptr;
+  void* wqkv_x3 = nullptr;
+  void* wfc_x3 = nullptr;
+  void* wac_x3 = nullptr;
+  // gamma
+  double* g_twiddle = nullptr;   // [nfft][2]
+  double* g_window = nullptr;
+  double* g_weightsT = nullptr;  // [gamma_kp(nfft)][64] ERB weights (fft_weights)
+};
+
+// The host image of the one device allocation that holds every packed weight.
+// add() copies its source at once, at the next 256-byte offset, and remembers
+// the pointer to set; bind() sets every such pointer once the image's device
+// address is known.  No source has to outlive its add().
+struct WeightBlob {
+  struct Region {
+    void** dst;
+    size_t off, bytes;
+  };
+  std::vector<char> image;
+  std::vector<Region> regions;
+  template <typename D, typename T>
+  void add(D** dst, const T* src, size_t n) {
+    add_bytes(reinterpret_cast<void**>(dst), src, n * sizeof(T));
+  }
+  void add_bytes(void** dst, const void* src, size_t bytes);
+  void bind(void* device_base) const;
+};
+
+// ---- packed layouts (weights.cpp) -------------------------------------------
+// wf = BN-folded weights [Cout][Cin][9] in float64 for the three conv packers
+void pack_conv_exact(const double* wf, int Cin, int Cout, float* out);    // out: Cin * 9 * Cout floats
+void pack_conv_wino(const double* wf, int Cin, int Cout, float* U);       // U: Cin * Cout * 16 floats
+void pack_conv_wino43(const double* wf, int Cin, int Cout, float* U);     // U: 2 * Cin * Cout * 36 floats
+// w [N][K][taps] fp32 -> split-bf16 pack for conv_x3.hip (taps 9) and linear_x3.hip (taps 1):
+// x = hi + lo + (dropped), hi = bf16(x), lo = bf16(x - hi), both round-to-nearest-even
+std::vector<uint16_t> pack_x3(const float* w, int N, int K, int taps, int BN);
+
+void pack_head(const Model& m, const Params& P, std::vector<float>* wac, std::vector<float>* bac);   // [nac][hw], [nac]
+
+// gammatone tables (gamma_weights.cpp); gamma_kp: bins nfft / 2 + 1 padded to a multiple of 32
+inline int gamma_kp(int nfft) { return ((nfft / 2 + 1) + 31) / 32 * 32; }
+// host: ERB weights [kp][nfilts] (zero rows past nfft/2), twiddles [2 nfft], window [nfft]
+void gamma_tables(double fs, int nfft, int nwin, int nfilts, double fmin, std::vector<double>& weightsT,
+                  int kp, std::vector<double>& twiddle, std::vector<double>& window);
+struct GammaGeom {
+  int nfft = 0, nwin = 0, hop = 0;
+};
+
+// Everything sedx_finalize_weights uploads: checks that params holds every key
+// of expected_params(m), fills the image, records where every pointer of *W
+// goes (WeightBlob::bind sets them) and sets W's scalar fields.
+sedx_status prepare_weights(const Model& m, const Params& params, DevWeights* W, WeightBlob* blob,
+                            GammaGeom* gamma, std::string* err);
+
+}  // namespace sedx

@@ -7,15 +7,24 @@
 //    and seeded random byte flips of the valid images;
 //  * sedx_events (the quirk-exact vad of utils/vad.py) over random and edge
 //    series: all-on, all-off, single frames at both ends, negative low
-//    thresholds, capacity too small.
-// Any memory error or undefined behaviour aborts the process (non-zero exit).
+//    thresholds, capacity too small;
+//  * the weight packing (csrc/weights.cpp): every packed layout read back the
+//    way its kernel addresses it (the staging copy into LDS, then the lane's
+//    fragment read), the split-bf16 bit patterns, the Winograd U values, and
+//    prepare_weights whole for every model on a synthetic state_dict.
+// Any memory error, undefined behaviour or failed check aborts the process
+// (non-zero exit).
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <random>
+#include <string>
 #include <vector>
 
 #include "../../include/sedx.h"
+#include "../../sound-event-detection_amd/csrc/weights.h"
 
 namespace {
 
@@ -85,6 +94,439 @@ int parse_all_prefixes(const std::vector<uint8_t>& img, int* ok) {
   return n;
 }
 
+// ---- weight packing (csrc/weights.cpp) ---------------------------------------
+#define CHECK(cond, ...)                                    \
+  do {                                                      \
+    if (!(cond)) {                                          \
+      std::fprintf(stderr, "check failed: %s: ", #cond);    \
+      std::fprintf(stderr, __VA_ARGS__);                    \
+      std::fprintf(stderr, "\n");                           \
+      std::abort();                                         \
+    }                                                       \
+  } while (0)
+
+using namespace sedx;
+
+std::vector<double> random_wf(int Cin, int Cout, std::mt19937& rng) {
+  std::normal_distribution<double> nd(0.0, 0.1);
+  std::vector<double> wf((size_t)Cout * Cin * 9);
+  for (auto& v : wf) v = nd(rng);
+  return wf;
+}
+// every element of a pack was read exactly once: the pack holds nothing else
+void all_once(const std::vector<uint8_t>& seen, const char* what) {
+  for (size_t i = 0; i < seen.size(); ++i) CHECK(seen[i] == 1, "%s: element %zu read %d times", what, i, seen[i]);
+}
+
+// conv.hip (conv3x3_kernel): chunk c of channel block n0 is staged by 16-byte
+// DMAs, LDS float L = 256 u + 4 lane <- wp[9 KC Cout c + 2 n0 + 2 Cout row + 4
+// (lane % LPR)], row = L / (2 BN); the 32x32x2 MFMA's B fragment of a lane
+// (khalf, n) at tap t is the float2 at t KC BN + (khalf BN + n) 2: (.x, .y) =
+// k-steps 0, 1, and the A side pairs k-step ks with channel 2 ks + khalf
+void check_exact(int Cin, int Cout, std::mt19937& rng) {
+  const int KC = 4, BN = Cout % 128 == 0 ? 128 : Cout % 64 == 0 ? 64 : Cout;
+  const std::vector<double> wf = random_wf(Cin, Cout, rng);
+  std::vector<float> pk((size_t)Cin * 9 * Cout);
+  pack_conv_exact(wf.data(), Cin, Cout, pk.data());
+  std::vector<uint8_t> seen(pk.size(), 0);
+  for (int o = 0; o < Cout; ++o)
+    for (int i = 0; i < Cin; ++i)
+      for (int t = 0; t < 9; ++t) {
+        const int chunk = i / KC, ks = (i % KC) / 2, khalf = (i % KC) % 2, n0 = o / BN * BN, n = o % BN;
+        const int L = t * KC * BN + (khalf * BN + n) * 2 + ks;
+        const int row = L / (2 * BN), col = L % (2 * BN);
+        const size_t g = (size_t)9 * KC * Cout * chunk + 2 * n0 + (size_t)row * 2 * Cout + col;
+        CHECK(g < pk.size(), "exact %dx%d", Cin, Cout);
+        CHECK(pk[g] == (float)wf[((size_t)o * Cin + i) * 9 + t], "exact %dx%d o %d i %d t %d", Cin, Cout, o, i, t);
+        ++seen[g];
+      }
+  all_once(seen, "exact pack");
+}
+
+// round-to-nearest-even bf16 of a finite float, by the remainder
+uint16_t bf16_rne(float x) {
+  uint32_t u;
+  std::memcpy(&u, &x, 4);
+  uint32_t hi = u >> 16;
+  const uint32_t rem = u & 0xFFFFu;
+  if (rem > 0x8000u || (rem == 0x8000u && (hi & 1u))) ++hi;
+  return (uint16_t)hi;
+}
+float bf16_value(uint16_t b) {
+  const uint32_t u = (uint32_t)b << 16;
+  float f;
+  std::memcpy(&f, &u, 4);
+  return f;
+}
+float from_bits(uint32_t u) {
+  float f;
+  std::memcpy(&f, &u, 4);
+  return f;
+}
+
+// conv_x3.hip: stage (nb, chunk, ky) = 3 BN 4 uint4 copied as they lie from
+// wp[((nb nchunks + chunk) 3 + ky) 3 BN 4 ..]; the fragment of lane (h, n) at
+// tap (ky, kx) is uint4 kx BN 4 + n 4 + (h ^ s) (hi) and + ((2 + h) ^ s) (lo),
+// s = (n >> 2) & 3; its 8 bf16 are input channels 16 chunk + 8 h + e.
+// linear_x3.hip: chunk kc (32 k) = 2 BN 4 uint4 from Wp[nb (K / 16) BN 4 + kc
+// 2 BN 4 ..]; the fragment of k-step ks is uint4 (ks BN + n) 4 + (h ^ s) / + ((2 + h) ^ s).
+void check_x3(int N, int K, int taps, int BN, std::mt19937& rng) {
+  std::normal_distribution<float> nd(0.f, 0.1f);
+  std::vector<float> w((size_t)N * K * taps);
+  for (auto& v : w) v = nd(rng);
+  // edges: zero, bf16-exact (lo == 0), exact ties (to even: down, then up), a negative tie
+  const float edges[] = {0.f, -0.f, 1.5f, from_bits(0x3F808000u), from_bits(0x3F818000u), from_bits(0xBF808000u),
+                         from_bits(0x3F80FFFFu)};
+  for (size_t e = 0; e < sizeof(edges) / sizeof(edges[0]); ++e) {
+    w[e] = edges[e];                          // first output channel
+    w[w.size() - 1 - 13 * e] = edges[e];      // last ones: the other swizzles and halves
+    w[(w.size() / 2 + 29 * e) % w.size()] = edges[e];
+  }
+  CHECK(bf16_rne(edges[3]) == 0x3F80 && bf16_rne(edges[4]) == 0x3F82 && bf16_rne(edges[2]) == 0x3FC0, "tie rule");
+  const std::vector<uint16_t> px = pack_x3(w.data(), N, K, taps, BN);
+  CHECK(px.size() == w.size() * 2, "x3 size");
+  std::vector<uint8_t> seen(px.size(), 0);
+  int sw_seen = 0;
+  for (int o = 0; o < N; ++o)
+    for (int i = 0; i < K; ++i)
+      for (int t = 0; t < taps; ++t) {
+        const int nb = o / BN, n = o % BN, s = (n >> 2) & 3, h = (i % 16) / 8, e = i % 8;
+        size_t u4;
+        if (taps == 9) {
+          const int nchunks = K / 16, chunk = i / 16, ky = t / 3, kx = t % 3;
+          u4 = (((size_t)nb * nchunks + chunk) * 3 + ky) * (3 * BN * 4) + (size_t)kx * BN * 4 + n * 4;
+        } else {
+          const int kc = i / 32, ks = (i % 32) / 16;
+          u4 = (size_t)nb * (K / 16) * BN * 4 + (size_t)kc * (2 * BN * 4) + (size_t)(ks * BN + n) * 4;
+        }
+        const size_t ihi = 8 * (u4 + (h ^ s)) + e, ilo = 8 * (u4 + ((2 + h) ^ s)) + e;
+        CHECK(ihi < px.size() && ilo < px.size(), "x3 index");
+        const float x = w[((size_t)o * K + i) * taps + t];
+        const uint16_t hi = bf16_rne(x), lo = bf16_rne(x - bf16_value(hi));
+        CHECK(px[ihi] == hi && px[ilo] == lo, "x3 N %d K %d taps %d o %d i %d t %d: %04x %04x vs %04x %04x", N, K,
+              taps, o, i, t, px[ihi], px[ilo], hi, lo);
+        ++seen[ihi];
+        ++seen[ilo];
+        sw_seen |= 1 << s;
+      }
+  CHECK(sw_seen == 15, "x3: all four swizzles");
+  all_once(seen, "x3 pack");
+}
+
+// (G g G^T)[a][c] in float64, rounded once to fp32: g [3][3] row-major, G [n][3]
+void ggt(const double* g, const double (*G)[3], int n, float* out) {
+  double tmp[6][3];
+  for (int a = 0; a < n; ++a)
+    for (int y = 0; y < 3; ++y) tmp[a][y] = G[a][0] * g[0 * 3 + y] + G[a][1] * g[1 * 3 + y] + G[a][2] * g[2 * 3 + y];
+  for (int a = 0; a < n; ++a)
+    for (int c = 0; c < n; ++c) out[a * n + c] = (float)(tmp[a][0] * G[c][0] + tmp[a][1] * G[c][1] + tmp[a][2] * G[c][2]);
+}
+const double G22[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+const double G43[6][3] = {{1.0 / 4, 0, 0},          {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
+                          {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6},  {0, 0, 1}};
+
+// conv_wino.hip: chunk c of channel group n0 (NCH = 32 or 64 channels) is
+// staged like the exact slab, LDS float L <- U[64 Cout c + 2 n0 + 2 Cout row +
+// col], row = L / (2 NCH); the fragment of lane (khalf, n) at position p is
+// the float2 at 4 NCH p + 2 NCH khalf + 2 n, (.x, .y) = k-steps 0, 1 = input
+// channels 2 khalf, 2 khalf + 1 of the chunk (the halo's float2 of that lane)
+void check_wino(int Cin, int Cout, int NCH, std::mt19937& rng) {
+  const std::vector<double> wf = random_wf(Cin, Cout, rng);
+  std::vector<float> U((size_t)Cin * Cout * 16);
+  pack_conv_wino(wf.data(), Cin, Cout, U.data());
+  std::vector<uint8_t> seen(U.size(), 0);
+  for (int o = 0; o < Cout; ++o)
+    for (int i = 0; i < Cin; ++i) {
+      float want[16];
+      ggt(&wf[((size_t)o * Cin + i) * 9], G22, 4, want);
+      const int chunk = i / 4, khalf = (i % 4) / 2, ks = i % 2, n0 = o / NCH * NCH, n = o % NCH;
+      for (int p = 0; p < 16; ++p) {
+        const int L = 4 * NCH * p + 2 * NCH * khalf + 2 * n + ks;
+        const int row = L / (2 * NCH), col = L % (2 * NCH);
+        const size_t g = (size_t)64 * Cout * chunk + 2 * n0 + (size_t)row * 2 * Cout + col;
+        CHECK(g < U.size(), "wino index");
+        CHECK(U[g] == want[p], "wino %dx%d o %d i %d p %d", Cin, Cout, o, i, p);
+        ++seen[g];
+      }
+    }
+  all_once(seen, "F(2x2) pack");
+}
+
+// conv_wino43.hip: the slab of (64-channel group g, chunk c) = 36 x 4 x 64
+// floats copied as they lie from U[(g nch + c) 9216 ..]; lane l = 16 k + m
+// reads position p as the 4 floats at 256 p + 4 l: output channels 64 g + 16 nt
+// + m, nt = 0..3, input channel 4 c + k.  The 16-channel items read the second
+// pack, at Cin Cout 36 floats: slab (g16, c) at (g16 nch + c) 2304, the lane's
+// float at 64 p + l.
+void check_wino43(int Cin, int Cout, std::mt19937& rng) {
+  const std::vector<double> wf = random_wf(Cin, Cout, rng);
+  std::vector<float> U((size_t)2 * Cin * Cout * 36);
+  pack_conv_wino43(wf.data(), Cin, Cout, U.data());
+  std::vector<uint8_t> seen(U.size(), 0);
+  const int nch = Cin / 4;
+  int nt_seen = 0;
+  for (int o = 0; o < Cout; ++o)
+    for (int i = 0; i < Cin; ++i) {
+      float want[36];
+      ggt(&wf[((size_t)o * Cin + i) * 9], G43, 6, want);
+      const int c = i / 4, k = i % 4, m = o % 16, lane = 16 * k + m, nt = o % 64 / 16;
+      for (int p = 0; p < 36; ++p) {
+        const size_t g4 = ((size_t)(o / 64) * nch + c) * 9216 + 256 * p + 4 * lane + nt;
+        const size_t g1 = (size_t)Cin * Cout * 36 + ((size_t)(o / 16) * nch + c) * 2304 + 64 * p + lane;
+        CHECK(g4 < (size_t)Cin * Cout * 36 && g1 < U.size(), "wino43 index");
+        CHECK(U[g4] == want[p] && U[g1] == want[p], "wino43 %dx%d o %d i %d p %d", Cin, Cout, o, i, p);
+        ++seen[g4];
+        ++seen[g1];
+      }
+      nt_seen |= 1 << nt;
+    }
+  CHECK(nt_seen == 15, "wino43: nt 0..3");
+  all_once(seen, "F(4x4) packs");
+}
+
+// a synthetic state_dict of the model's expected shapes: random tensors
+// (positive variances), a Hann-window DFT for the STFT, a triangular mel
+// matrix.  only: a key prefix to keep (nullptr: every key)
+Params synth_params(const Model& m, uint32_t seed, const char* only = nullptr, const char* only2 = nullptr) {
+  Params P;
+  std::mt19937 rng(seed);
+  std::normal_distribution<float> nd(0.f, 0.1f);
+  for (const auto& kv : expected_params(m)) {
+    const std::string& key = kv.first;
+    if (only && key.rfind(only, 0) != 0 && key.rfind(only2, 0) != 0) continue;
+    Tensor t;
+    t.shape = kv.second;
+    size_t n = 1;
+    for (int64_t d : t.shape) n *= (size_t)d;
+    t.data.resize(n);
+    const bool var = key.size() > 11 && key.compare(key.size() - 11, 11, "running_var") == 0;
+    for (auto& v : t.data) v = var ? std::fabs(nd(rng)) + 0.5f : nd(rng);
+    P[key] = std::move(t);
+  }
+  if (only) return P;
+  const int N = m.cfg.window_size, K = N / 2 + 1;
+  auto& wr = P.at("spectrogram_extractor.stft.conv_real.weight").data;
+  auto& wi = P.at("spectrogram_extractor.stft.conv_imag.weight").data;
+  for (int k = 0; k < K; ++k)
+    for (int n = 0; n < N; ++n) {
+      const double win = 0.5 - 0.5 * std::cos(2.0 * M_PI * n / N), ang = 2.0 * M_PI * ((int64_t)k * n % N) / N;
+      wr[(size_t)k * N + n] = (float)(std::cos(ang) * win);
+      wi[(size_t)k * N + n] = (float)(-std::sin(ang) * win);
+    }
+  auto& mel = P.at("logmel_extractor.melW").data;   // [K][64]: band m a triangle around bin (m + 1) (K - 1) / 65
+  const double step = (K - 1) / 65.0;
+  for (int k = 0; k < K; ++k)
+    for (int b = 0; b < 64; ++b) {
+      const double v = 1.0 - std::fabs(k - (b + 1) * step) / step;
+      mel[(size_t)k * 64 + b] = v > 0 ? (float)v : 0.f;
+    }
+  return P;
+}
+
+struct PtrWant {
+  const char* name;
+  const void* p;
+  bool want;
+};
+// every pointer of the table, with whether this model's forward reads it
+std::vector<PtrWant> pointer_table(const Model& m, const DevWeights& W) {
+  const bool gru = m.seq == SEQ_GRU, mha = m.seq == SEQ_MHA, cf = m.seq == SEQ_CONFORMER;
+  const bool gam = m.cfg.feature_type == SEDX_FEATURE_GAMMA;
+  std::vector<PtrWant> t = {
+      {"twiddle", W.twiddle, true},     {"window", W.window, true},       {"mel_w", W.mel_w, true},
+      {"mel_tab", W.mel_tab, true},     {"mel_mt", W.mel_mt, m.cfg.window_size == 512},
+      {"mel_off", W.mel_off, true},     {"mel_lo", W.mel_lo, true},       {"bn0_scale", W.bn0_scale, true},
+      {"bn0_mean", W.bn0_mean, true},   {"bn0_bias", W.bn0_bias, true},   {"c1_w", W.c1_w, true},
+      {"c1_wt", W.c1_wt, true},         {"c1_b", W.c1_b, true},           {"zero", W.zero, true},
+      {"trash", W.trash, true},         {"w_ih", W.w_ih, gru},            {"b_ih", W.b_ih, gru},
+      {"whhT", W.whhT, gru},            {"whh", W.whh, gru},              {"bhh", W.bhh, gru},
+      {"wqkv", W.wqkv, mha},            {"bqkv", W.bqkv, mha},            {"wfc", W.wfc, mha},
+      {"bfc", W.bfc, mha},              {"wac", W.wac, true},             {"bac", W.bac, true},
+      {"cf_in_w", W.cf_in_w, cf},       {"cf_in_b", W.cf_in_b, cf},       {"cf_in_g", W.cf_in_g, cf},
+      {"cf_in_be", W.cf_in_be, cf},     {"cf_pe", W.cf_pe, cf},           {"cf_inv_freq", W.cf_inv_freq, cf},
+      {"w_ih_x3", W.w_ih_x3, gru},      {"wqkv_x3", W.wqkv_x3, mha},      {"wfc_x3", W.wfc_x3, mha},
+      {"wac_x3", W.wac_x3, !cf},        {"g_twiddle", W.g_twiddle, gam},  {"g_window", W.g_window, gam},
+      {"g_weightsT", W.g_weightsT, gam},
+  };
+  for (int i = 0; i < 8; ++i) {
+    t.push_back({"wp", W.wp[i], i > 0});
+    t.push_back({"cb", W.cb[i], i > 0});
+    t.push_back({"wx3", W.wx3[i], i > 0});
+    t.push_back({"wu", W.wu[i], i > 0});
+    t.push_back({"wu43", W.wu43[i], i > 0});
+  }
+  for (const CfBlockWeights& c : W.cf) {
+    for (int f = 0; f < 2; ++f)
+      for (const float* p : {c.ffn_g[f], c.ffn_be[f], c.ffn_w1[f], c.ffn_b1[f], c.ffn_w2[f], c.ffn_b2[f]})
+        t.push_back({"cf.ffn", p, cf});
+    for (const float* p : {c.att_g, c.att_be, c.wqkv, c.wo, c.rnet, c.rwb, c.rrb, c.cv_g, c.cv_be, c.pw1_w, c.pw1_b,
+                           c.dw_wt, c.dw_b, c.pw2_w, c.pw2_b, c.norm_g, c.norm_be})
+      t.push_back({"cf", p, cf});
+  }
+  return t;
+}
+// the table above names every pointer member: a member added to DevWeights
+// without a row here changes this size
+static_assert(sizeof(DevWeights) == sizeof(void*) * (39 + 5 * 8 + CF_BLOCKS * 29) + 14 * sizeof(int32_t),
+              "pointer_table lists every DevWeights pointer");
+
+Model model_of(int model_type, int classes, int window, int feature) {
+  sedx_config cfg{};
+  cfg.model_type = model_type;
+  cfg.feature_type = feature;
+  cfg.sample_rate = 16000;
+  cfg.window_size = window;
+  cfg.hop_size = 160;
+  cfg.mel_bins = 64;
+  cfg.fmin = 50.f;
+  cfg.fmax = 7000.f;
+  cfg.classes_num = classes;
+  Model m;
+  CHECK(make_model(cfg, &m), "model %d", model_type);
+  return m;
+}
+
+// rows of the head projection against the state_dict: att row c at c, cla row
+// c at C + c (fc: row c at c), zeros after
+void check_head_rows(const Model& m, const Params& P, const float* wac, const float* bac) {
+  const int C = m.cfg.classes_num;
+  const bool att = m.head == HEAD_ATT;
+  for (int r = 0; r < m.nac; ++r) {
+    const Tensor* w = nullptr;
+    const Tensor* b = nullptr;
+    int c = r;
+    if (att && r < 2 * C) {
+      w = &P.at(r < C ? "att_block.att.weight" : "att_block.cla.weight");
+      b = &P.at(r < C ? "att_block.att.bias" : "att_block.cla.bias");
+      c = r < C ? r : r - C;
+    } else if (!att && r < C) {
+      w = &P.at("fc.weight");
+      b = &P.at("fc.bias");
+    }
+    CHECK(bac[r] == (b ? b->data[c] : 0.f), "head bias row %d", r);
+    for (int j = 0; j < m.hw; ++j)
+      CHECK(wac[(size_t)r * m.hw + j] == (w ? w->data[(size_t)c * m.hw + j] : 0.f), "head row %d col %d", r, j);
+  }
+}
+
+// prepare_weights on a whole synthetic state_dict
+void check_prepare(int model_type, int window, int feature, int classes = 25) {
+  const Model m = model_of(model_type, classes, window, feature);
+  const Params P = synth_params(m, 100 + model_type);
+  DevWeights W;
+  WeightBlob blob;
+  GammaGeom gg;
+  std::string err;
+  const sedx_status st = prepare_weights(m, P, &W, &blob, &gg, &err);
+  CHECK(st == SEDX_OK, "model %d window %d: %s", model_type, window, err.c_str());
+  // regions: 256-byte aligned, disjoint, inside the image, one per pointer
+  size_t end = 0;
+  for (const auto& r : blob.regions) {
+    CHECK(r.off % 256 == 0 && r.off >= end && r.bytes > 0 && r.off + r.bytes <= blob.image.size(), "region at %zu", r.off);
+    end = r.off + r.bytes;
+  }
+  for (const PtrWant& e : pointer_table(m, W)) CHECK(e.p == nullptr, "%s set before bind", e.name);
+  blob.bind(blob.image.data());   // the image stands in for the device allocation
+  size_t set = 0;
+  for (const PtrWant& e : pointer_table(m, W)) {
+    CHECK((e.p != nullptr) == e.want, "model %d window %d: pointer %s", model_type, window, e.name);
+    set += e.p != nullptr;
+  }
+  CHECK(set == blob.regions.size(), "%zu pointers, %zu regions", set, blob.regions.size());
+  for (const auto& r : blob.regions) CHECK(*r.dst == blob.image.data() + r.off, "bind");
+  CHECK((W.mt_floats != 0) == (window == 512), "mt_floats %d at window %d", W.mt_floats, window);
+  CHECK((gg.nfft != 0) == (feature == SEDX_FEATURE_GAMMA), "gamma geometry");
+  // through the table, as block 1's conv2 reads it (check_exact's addressing
+  // at BN = 64): the BN-folded weight and bias
+  const auto& wt = P.at("conv_block1.conv2.weight").data;
+  for (int o = 0; o < 64; ++o) {
+    const double sc = (double)P.at("conv_block1.bn2.weight").data[o] /
+                      std::sqrt((double)P.at("conv_block1.bn2.running_var").data[o] + 1e-5);
+    CHECK(W.cb[1][o] == (float)((double)P.at("conv_block1.bn2.bias").data[o] -
+                                (double)P.at("conv_block1.bn2.running_mean").data[o] * sc), "bias %d", o);
+    for (int i = 0; i < 64; ++i)
+      for (int t = 0; t < 9; ++t) {
+        const int L = t * 4 * 64 + ((i % 2) * 64 + o) * 2 + (i % 4) / 2;
+        CHECK(W.wp[1][(size_t)9 * 4 * 64 * (i / 4) + L] == (float)(wt[((size_t)o * 64 + i) * 9 + t] * sc), "wp[1]");
+      }
+  }
+  // the head in the image, and its x3 pack as linear_x3.hip reads it at N =
+  // nac, BN = 64 (check_x3's addressing)
+  check_head_rows(m, P, W.wac, W.bac);
+  if (W.wac_x3) {
+    const uint16_t* px = static_cast<const uint16_t*>(W.wac_x3);
+    for (int o = 0; o < m.nac; ++o)
+      for (int i = 0; i < 512; ++i) {
+        const int nb = o / 64, n = o % 64, s = (n >> 2) & 3, h = (i % 16) / 8, e = i % 8, kc = i / 32, ks = (i % 32) / 16;
+        const size_t u4 = (size_t)nb * 32 * 64 * 4 + (size_t)kc * (2 * 64 * 4) + (size_t)(ks * 64 + n) * 4;
+        const float x = W.wac[(size_t)o * 512 + i];
+        const uint16_t hi = bf16_rne(x), lo = bf16_rne(x - bf16_value(hi));
+        CHECK(px[8 * (u4 + (h ^ s)) + e] == hi && px[8 * (u4 + ((2 + h) ^ s)) + e] == lo, "wac_x3 row %d col %d", o, i);
+      }
+  }
+}
+
+// head rows over the class counts at which nac steps (one trunk: heads only)
+void check_heads() {
+  for (int model_type : {SEDX_MODEL_CNN_FRAMEATT, SEDX_MODEL_CNN_FRAMEAVG, SEDX_MODEL_CONFORMER_FRAMEATT})
+    for (int C : {1, 32, 33, 64, 65, 256}) {
+      const Model m = model_of(model_type, C, 512, SEDX_FEATURE_LOGMEL);
+      const bool att = m.head == HEAD_ATT;
+      const int rows = att ? 2 * C : C;
+      CHECK(m.nac == (rows + 63) / 64 * 64 && m.nac >= rows && m.nac % 64 == 0, "nac %d for %d rows", m.nac, rows);
+      if (att) CHECK(m.nac == (C <= 32 ? 64 : C <= 64 ? 128 : C <= 96 ? 192 : 512), "AttBlock nac %d at C %d", m.nac, C);
+      else CHECK(m.nac == (C <= 64 ? 64 : C <= 128 ? 128 : 256), "fc nac %d at C %d", m.nac, C);
+      const Params P = synth_params(m, 7 * C, "att_block.", "fc.");
+      std::vector<float> wac, bac;
+      pack_head(m, P, &wac, &bac);
+      CHECK(wac.size() == (size_t)m.nac * m.hw && bac.size() == (size_t)m.nac, "head size");
+      check_head_rows(m, P, wac.data(), bac.data());
+    }
+}
+
+void check_errors() {
+  const Model m = model_of(SEDX_MODEL_GRU_FRAMEATT, 25, 512, SEDX_FEATURE_LOGMEL);
+  Params P = synth_params(m, 5);
+  DevWeights W;
+  WeightBlob blob;
+  GammaGeom gg;
+  std::string err;
+  Params Q = P;
+  Q.erase("gru.bias_hh_l0_reverse");
+  CHECK(prepare_weights(m, Q, &W, &blob, &gg, &err) == SEDX_EKEY, "missing key status");
+  CHECK(err == "missing key in state_dict: gru.bias_hh_l0_reverse", "missing key message: %s", err.c_str());
+  P.at("spectrogram_extractor.stft.conv_imag.weight").data[2 * 512 + 7] += 1e-3f;
+  CHECK(prepare_weights(m, P, &W, &blob, &gg, &err) == SEDX_EINVAL, "perturbed STFT status");
+  CHECK(err.rfind("STFT conv weights are not a windowed DFT (max err ", 0) == 0 &&
+            err.find("the FFT frontend cannot reproduce them") != std::string::npos, "STFT message: %s", err.c_str());
+}
+
+int check_weights() {
+  std::mt19937 rng(4321);
+  int n = 0;
+  check_exact(4, 2, rng), ++n;
+  check_exact(8, 128, rng), ++n;
+  check_exact(64, 64, rng), ++n;
+  check_x3(64, 16, 1, 64, rng), ++n;
+  check_x3(128, 32, 1, 128, rng), ++n;
+  check_x3(64, 16, 9, 64, rng), ++n;
+  check_x3(256, 32, 9, 128, rng), ++n;
+  check_wino(4, 32, 32, rng), ++n;
+  check_wino(8, 64, 32, rng), ++n;
+  check_wino(8, 64, 64, rng), ++n;
+  check_wino43(8, 64, rng), ++n;
+  check_wino43(16, 128, rng), ++n;
+  for (int model_type = 0; model_type <= 8; ++model_type) check_prepare(model_type, 512, SEDX_FEATURE_LOGMEL), ++n;
+  check_prepare(SEDX_MODEL_GRU_FRAMEATT, 512, SEDX_FEATURE_GAMMA), ++n;
+  check_prepare(SEDX_MODEL_CNN_FRAMEAVG, 256, SEDX_FEATURE_LOGMEL), ++n;
+  check_prepare(SEDX_MODEL_CNN_FRAMEAVG, 1024, SEDX_FEATURE_LOGMEL), ++n;
+  // nac 128 through the whole path (the head's x3 pack at two column blocks)
+  check_prepare(SEDX_MODEL_CNN_FRAMEATT, 512, SEDX_FEATURE_LOGMEL, 33), ++n;
+  check_prepare(SEDX_MODEL_CNN_FRAMEAVG, 512, SEDX_FEATURE_LOGMEL, 65), ++n;
+  check_heads(), ++n;
+  check_errors(), n += 2;
+  return n;
+}
 }  // namespace
 
 int main() {
@@ -151,6 +593,8 @@ int main() {
         }
     }
   }
-  std::printf("asan_driver: %d wav_parse cases (%d accepted), %d vad cases: clean\n", cases, ok, vad_cases);
+  const int weight_checks = check_weights();
+  std::printf("asan_driver: %d wav_parse cases (%d accepted), %d vad cases, %d weight-pack checks: clean\n", cases,
+              ok, vad_cases, weight_checks);
   return 0;
 }

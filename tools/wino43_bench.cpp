@@ -12,12 +12,11 @@
 #include <vector>
 #include "../sound-event-detection_amd/csrc/sedx_internal.h"
 
-namespace sedx {
-void pack_conv_wino43(const double* wf, int Cin, int Cout, float* U);
 #ifdef SEDX_W43_STAMPS
+namespace sedx {
 void w43_stamps_rw(unsigned long long* h, bool reset);
-#endif
 }
+#endif
 
 struct Layer { const char* name; int B, T, F, cin, cout, epi; bool full; };
 

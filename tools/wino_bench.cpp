@@ -50,12 +50,7 @@ int main(int argc, char** argv) {
     for (auto& v : w) v = (double)(float)(nd(rng) * ws);
     for (auto& v : bias) v = 0.1f * nd(rng);
     std::vector<float> wp((size_t)l.cin * 9 * l.cout), U((size_t)l.cin * l.cout * 16);
-    for (int o = 0; o < l.cout; ++o)
-      for (int i = 0; i < l.cin; ++i)
-        for (int t = 0; t < 9; ++t) {
-          const int chunk = i / 4, kc = i % 4, ks = kc >> 1, kh = kc & 1;
-          wp[((((size_t)chunk * 9 + t) * 2 + kh) * l.cout + o) * 2 + ks] = (float)w[((size_t)o * l.cin + i) * 9 + t];
-        }
+    sedx::pack_conv_exact(w.data(), l.cin, l.cout, wp.data());
     sedx::pack_conv_wino(w.data(), l.cin, l.cout, U.data());
     hipMemcpy(d_in, in.data(), nin * 4, hipMemcpyHostToDevice);
     hipMemcpy(d_bias, bias.data(), l.cout * 4, hipMemcpyHostToDevice);
