@@ -280,7 +280,7 @@ def sample_pixels(B, T, Fq, n, seed=0):
 # ---------------------------------------------------------------------------
 # F(4x4,3x3) launch regimes
 # ---------------------------------------------------------------------------
-# the seven launches of run_body (csrc/api.cpp, `layers[7]`): which pooled length
+# the seven launches of the forward plan (csrc/plan.cpp, `ForwardPlan::layers`): which pooled length
 # (T >> shift) they see, F, Cout and whether the epilogue is the 2 x 2 pool
 W43_LAYERS = ((0, 64, 64, True), (1, 32, 128, False), (1, 32, 128, True), (2, 16, 256, False),
               (2, 16, 256, True), (3, 8, 512, False), (3, 8, 512, False))
@@ -298,7 +298,7 @@ def w43_launch(layer, B, T, ncu):
     are outside this restatement."""
     shift, Fq, cout, pool = W43_LAYERS[layer]
     Tl = T
-    for _ in range(shift):                       # api.cpp geometry_from_T (T1, T2, T3)
+    for _ in range(shift):                       # plan.cpp geometry_from_T (T1, T2, T3)
         Tl //= 2
     rows = 2 * (Tl // 2) if pool else Tl         # conv_wino43.hip `rows`, launch_w43_f :1105 / launch_w43_g :1024
     trows = (rows + 3) // 4                      # `trows` :1025
@@ -314,7 +314,7 @@ def w43_launch(layer, B, T, ncu):
     resident = ncu // 8 * 8                                                     # `resident` :1034
     per = (nitems + 1) // 2                      # `per`, SEDX_W43_ITEMS = 2 (:1035)
     nwg = min(nitems, max(8, resident, _ceil8(per)))                            # `nwg` :1036
-    sched = B >= 8                               # api.cpp run_body `w43`, `w43_sched`
+    sched = B >= 8                               # plan.cpp plan_forward `claims`
     claim = sched and nitems > 2 * resident and resident >= 8                   # `claim` :1041
     if claim:
         nwg = resident                                                          # `if (claim) nwg = resident` :1042

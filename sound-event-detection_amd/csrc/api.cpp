@@ -20,6 +20,15 @@
 
 using namespace sedx;
 
+// one forward's stage-boundary events: events 0..10 bound stages 0..10 (stage
+// i = [i, i + 1]) except stage 0 = [0, 12] (frontend) and stage 11 = [12, 1]
+// (pipeline wait): event 12 is recorded after the frontend, before the
+// cross-stream wait
+struct EvSet {
+  hipEvent_t ev[SEDX_N_STAGES + 1] = {};
+  bool rec[SEDX_N_STAGES + 1] = {};
+};
+
 // the model (cfg, seq, head, hw, nac: sedx_create, weights.h) and its state
 struct sedx_handle : sedx::Model {
   int device = 0;
@@ -28,53 +37,30 @@ struct sedx_handle : sedx::Model {
   std::map<std::string, std::vector<int64_t>> expected;
   bool finalized = false;
   void* blob = nullptr;      // single device allocation for all packed weights
-  size_t blob_bytes = 0;
   DevWeights w;
-  bool pad100 = false;       // framewise padded to a multiple of 100 (Cnn_9layers_Gru_FrameAtt, models.py:678-681)
   bool emb_cla = false;      // d_embedding is cla [B][C][T3] (models.py:683-686, :459), else the head's input transposed
-  int g_nfft = 0, g_nwin = 0, g_hop = 0;
+  int g_nfft = 0, g_hop = 0;   // gammatone FFT size and hop (prepare_weights)
   void* ws = nullptr;        // cached workspace
   size_t ws_bytes = 0;
-  // optional per-stage timing (sedx_set_profiling): events at stage boundaries
-  int precision = SEDX_PRECISION_WINOGRAD;   // GEMM arithmetic (sedx_set_precision; the default is fp32 Winograd)
-  int gru_kernel = SEDX_GRU_KERNEL_AUTO;   // sedx_set_tuning
-  int gru_handoff = SEDX_GRU_HANDOFF_AUTO;
-  int wino_block1 = 2;                     // SEDX_TUNE_WINO_BLOCK1 (2: conv1 inside the Winograd launch)
-  int mel_mfma = 0;                        // SEDX_TUNE_MEL_MFMA (measured slower: opt-in)
-  unsigned gru_spin = 1u << 24;            // SEDX_TUNE_GRU_SPIN: bound of every GRU hand-off spin (polls)
-  int wino_order = 1;                      // SEDX_TUNE_WINO_ORDER (4 x 8 rounds on the 512-channel layers)
-  int wino_f43 = 2;                        // SEDX_TUNE_WINO_F43 (2: blocks 1-4 as F(4x4,3x3), 1: blocks 2-4)
-  int gamma_spec = 0;                      // SEDX_TUNE_GAMMA_SPEC
+  Tuning tune;               // sedx_set_precision / sedx_set_tuning / sedx_set_pipelined (plan.h)
   // sedx_set_capture: copy one stage's output of every later forward
   int cap_stage = -1;
   float* cap_buf = nullptr;
   size_t cap_bytes = 0;
-  int profiling = 0;          // 0 off, 1 last forward, 2 accumulate
-  // sedx_set_pipelined: conv stacks of successive forwards run in issue order
-  // (each waits for the previous one's conv-done event), whatever streams
-  // they are issued on, so the sequence + head of batch i overlap the conv
-  // stack of batch i+1 instead of two conv stacks sharing the chip
-  bool pipelined = false;
-  bool pipe_conv1_first = false;           // sedx_set_pipelined(h, 2): block 1's conv1 before the wait
-  bool conv_done_recorded = false;
+  bool conv_done_recorded = false;   // sedx_set_pipelined
   hipEvent_t conv_done = nullptr;
   // host-mapped word the GRU kernel ORs a failure code into when a bounded
   // hand-off spin times out (that forward's outputs are NaN); the next
   // forward / sedx_stage_times turns it into SEDX_EHIP
   unsigned* gru_err_host = nullptr;
   unsigned* gru_err_dev = nullptr;
-  // events 0..10 bound stages 0..10 (stage i = [i, i + 1]) except stage 0 =
-  // [0, 12] (frontend) and stage 11 = [12, 1] (pipeline wait): event 12 is
-  // recorded after the frontend, before the cross-stream wait
-  hipEvent_t ev[SEDX_N_STAGES + 1] = {};
-  bool ev_recorded[SEDX_N_STAGES + 1] = {};
-  // profiling mode 2 (accumulate): every forward takes its own event set from
-  // this pool, so forwards in flight on different streams time independently;
-  // sedx_stage_times folds the used sets into per-stage sums and averages
-  struct EvSet {
-    hipEvent_t ev[SEDX_N_STAGES + 1] = {};
-    bool rec[SEDX_N_STAGES + 1] = {};
-  };
+  // optional per-stage timing (sedx_set_profiling): mark() records into
+  // ev_cur, which is ev_last in mode 1.  Mode 2 (accumulate): every forward
+  // takes its own set from the pool, so forwards in flight on different
+  // streams time independently; sedx_stage_times folds the used sets into
+  // per-stage sums and averages
+  int profiling = 0;          // 0 off, 1 last forward, 2 accumulate
+  EvSet ev_last;
   std::vector<EvSet> ev_pool;
   size_t ev_used = 0;
   EvSet* ev_cur = nullptr;
@@ -82,66 +68,63 @@ struct sedx_handle : sedx::Model {
   int64_t acc_n[SEDX_N_STAGES] = {};
 };
 
-
 namespace {
-// mode 2: sums the elapsed times of every used event set, frees the pool
-// the events bounding stage i (see sedx_handle::ev)
+// the events bounding stage i (see EvSet)
 inline int stage_begin(int i) { return i == 11 ? 12 : i; }
 inline int stage_end(int i) { return i == 0 ? 12 : i == 11 ? 1 : i + 1; }
 static_assert(SEDX_N_STAGES == 12, "stage event map");
 
+// elapsed ms of stage i in set e, once its end event completed; *recorded =
+// false (and *ms untouched) when the set does not hold both events
+hipError_t stage_ms(const EvSet& e, int i, float* ms, bool* recorded) {
+  const int a = stage_begin(i), b = stage_end(i);
+  *recorded = e.rec[a] && e.rec[b];
+  if (!*recorded) return hipSuccess;
+  const hipError_t st = hipEventSynchronize(e.ev[b]);
+  return st != hipSuccess ? st : hipEventElapsedTime(ms, e.ev[a], e.ev[b]);
+}
+
+// mode 2: sums the elapsed times of every used event set, frees the pool
 void fold_ev_pool(sedx_handle* h) {
-  for (size_t k = 0; k < h->ev_used; ++k) {
-    auto& e = h->ev_pool[k];
+  for (size_t k = 0; k < h->ev_used; ++k)
     for (int i = 0; i < SEDX_N_STAGES; ++i) {
-      const int a = stage_begin(i), b = stage_end(i);
-      if (!e.rec[a] || !e.rec[b]) continue;
       float v = 0.f;
-      if (hipEventSynchronize(e.ev[b]) == hipSuccess && hipEventElapsedTime(&v, e.ev[a], e.ev[b]) == hipSuccess) {
+      bool rec = false;
+      if (stage_ms(h->ev_pool[k], i, &v, &rec) == hipSuccess && rec) {
         h->acc_ms[i] += v;
         ++h->acc_n[i];
       }
     }
-  }
   h->ev_used = 0;
   h->ev_cur = nullptr;
 }
 
 inline void mark(sedx_handle* h, int i, hipStream_t s) {
   if (!h->profiling) return;
-  if (h->profiling == 2) {
-    if (i == 0) {                       // a forward starts: next event set
-      if (h->ev_used == 4096) fold_ev_pool(h);
-      if (h->ev_used == h->ev_pool.size()) {
-        h->ev_pool.emplace_back();
-        for (auto& e : h->ev_pool.back().ev)
-          if (hipEventCreate(&e) != hipSuccess) e = nullptr;
-      }
-      h->ev_cur = &h->ev_pool[h->ev_used++];
-      for (auto& r : h->ev_cur->rec) r = false;
+  if (h->profiling == 2 && i == 0) {    // a forward starts: next event set
+    if (h->ev_used == 4096) fold_ev_pool(h);
+    if (h->ev_used == h->ev_pool.size()) {
+      h->ev_pool.emplace_back();
+      for (auto& e : h->ev_pool.back().ev)
+        if (hipEventCreate(&e) != hipSuccess) e = nullptr;
     }
-    if (h->ev_cur && h->ev_cur->ev[i]) {
-      (void)hipEventRecord(h->ev_cur->ev[i], s);
-      h->ev_cur->rec[i] = true;
-    }
-    return;
+    h->ev_cur = &h->ev_pool[h->ev_used++];
+    for (auto& r : h->ev_cur->rec) r = false;
   }
-  if (h->ev[i]) {
-    (void)hipEventRecord(h->ev[i], s);
-    h->ev_recorded[i] = true;
+  EvSet* e = h->ev_cur;
+  if (e && e->ev[i]) {
+    (void)hipEventRecord(e->ev[i], s);
+    e->rec[i] = true;
   }
 }
-}  // namespace
 
-namespace {
-
-sedx_status fail(sedx_handle* h, sedx_status st, const char* fmt, ...) {
+sedx_status fail(const sedx_handle* h, sedx_status st, const char* fmt, ...) {
   char buf[512];
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(buf, sizeof(buf), fmt, ap);
   va_end(ap);
-  if (h) h->err = buf;
+  if (h) const_cast<sedx_handle*>(h)->err = buf;   // the const queries set sedx_last_error's message too
   return st;
 }
 
@@ -189,6 +172,21 @@ sedx_status check_async_error(sedx_handle* h) {
   return SEDX_OK;
 }
 
+// what every forward checks before it looks at its arguments
+sedx_status preflight(sedx_handle* h) {
+  if (!h) return SEDX_EINVAL;
+  if (!h->finalized) return fail(h, SEDX_ESTATE, "weights not finalised");
+  return check_async_error(h);
+}
+
+// the geometry the size queries answer for: L_or_T = samples (logmel) or frames (gamma)
+sedx_status query_geometry(const sedx_handle* h, int64_t L_or_T, Geometry* g) {
+  *g = geometry_from_T(*h, h->cfg.feature_type == SEDX_FEATURE_GAMMA ? L_or_T : conv_T(*h, L_or_T));
+  if (seq_too_long(*h, g->T3))
+    return fail(h, SEDX_EINVAL, "%lld sequence frames: the Conformer encoder holds %d", (long long)g->T3, CF_MAX_T);
+  return SEDX_OK;
+}
+
 struct DeviceGuard {
   int prev = -1;
   explicit DeviceGuard(int dev) {
@@ -200,76 +198,6 @@ struct DeviceGuard {
     if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
   }
 };
-
-int64_t conv_T(const sedx_handle* h, int64_t L) { return L / h->cfg.hop_size + 1; }
-
-// the Conformer encoder's positional table has CF_MAX_T rows; the reference
-// fails on a longer sequence too (embedding.py:30: the add does not broadcast)
-bool seq_too_long(const sedx_handle* h, int64_t T3) { return h->seq == SEQ_CONFORMER && T3 > CF_MAX_T; }
-
-struct Geometry {
-  int64_t T, T1, T2, T3, fw_len, out_frames;
-};
-
-Geometry geometry_from_T(const sedx_handle* h, int64_t T) {
-  Geometry g;
-  g.T = T;
-  g.T1 = T / 2;
-  g.T2 = g.T1 / 2;
-  g.T3 = g.T2 / 2;
-  g.fw_len = 8 * g.T3;
-  g.out_frames = g.fw_len;
-  // pad_framewise_output(roundup) models.py:678-681: Cnn_9layers_Gru_FrameAtt
-  // (Cnn_9layers_Gru_FrameAvg returns the 8 T3 frames, :551) and the two
-  // Conformer models (:1359-1360, :1571-1572)
-  if (h->pad100 && g.fw_len != 1000)
-    g.out_frames = (g.fw_len % 100 == 0) ? g.fw_len : g.fw_len + 100 - g.fw_len % 100;
-  return g;
-}
-
-// workspace layout (floats), 256-B aligned regions
-struct WsLayout {
-  size_t x0, bufA, bufB, sched, total_bytes;
-};
-
-size_t align_up(size_t x) { return (x + 63) & ~size_t(63); }
-
-bool wino_block1_on(const sedx_handle* h) { return h->precision == SEDX_PRECISION_WINOGRAD && h->wino_block1; }
-
-WsLayout ws_layout(const sedx_handle* h, int64_t B, const Geometry& g) {
-  WsLayout l;
-  size_t off = 0;
-  l.x0 = off;
-  off += align_up((size_t)B * g.T * 64);
-  // A: the zero-bordered bn0 output (block 1 is one fused launch in both
-  // modes: conv1's 64-channel activation never exists), then the conv1
-  // outputs of blocks 2-4, then the head scratch
-  size_t a = block1_pad_floats((int)B, (int)g.T);
-  if (wino_block1_on(h) && (h->wino_block1 == 1 || h->wino_f43 == 2))
-    a = std::max(a, (size_t)B * g.T * 64 * 64);   // conv1's activation
-  a = std::max(a, (size_t)B * g.T1 * 32 * 128);
-  a = std::max(a, (size_t)B * g.T2 * 16 * 256);
-  a = std::max(a, (size_t)B * g.T3 * 8 * 512);
-  // head scratch (after the conv stack): G/QKV + H + O + logits
-  a = std::max(a, (size_t)B * g.T3 * (1536 + 512 + 512 + h->nac) + 4 * 64 +
-                      gru_coop_workspace_bytes((int)B) / sizeof(float) + 64);
-  // Conformer encoder scratch: x, LayerNorm(x), the widest hidden (576), the
-  // attention / depthwise output, r and r_k of the 3 blocks, the logits
-  if (h->seq == SEQ_CONFORMER)
-    a = std::max(a, (size_t)B * g.T3 * (3 * CF_D + CF_FF + h->nac) + 2 * CF_BLOCKS * (size_t)g.T3 * CF_D + 8 * 64);
-  l.bufA = off;
-  off += align_up(a);
-  size_t b = (size_t)B * g.T1 * 32 * 64;
-  b = std::max(b, (size_t)B * g.T2 * 16 * 128);
-  b = std::max(b, (size_t)B * g.T3 * 8 * 256);
-  b = std::max(b, (size_t)B * g.T3 * 512);
-  l.bufB = off;
-  off += align_up(b);
-  l.sched = off;                                  // 7 conv launches x CONV_SCHED_INTS claim counters
-  off += align_up(7 * CONV_SCHED_INTS);
-  l.total_bytes = off * sizeof(float);
-  return l;
-}
 
 sedx_status get_ws(sedx_handle* h, size_t need, void* user, size_t user_bytes, float** out) {
   if (user) {
@@ -289,115 +217,127 @@ sedx_status get_ws(sedx_handle* h, size_t need, void* user, size_t user_bytes, f
   return SEDX_OK;
 }
 
-// CNN + head on X0 [B][T][64] already in workspace
-sedx_status run_body(sedx_handle* h, int64_t B, const Geometry& g, float* ws, const WsLayout& l,
-                     float* d_fw, float* d_clip, float* d_emb, hipStream_t s) {
+// the log-mel frontend of plan p's items into its X0: n_win windows of
+// sig_len samples per clip at win_start (device; nullptr: one, at 0)
+void run_logmel(sedx_handle* h, const ForwardPlan& p, float* ws, const float* audio, const int16_t* audio_i16,
+                int64_t clip_stride, int64_t n_clips, int n_win, const int64_t* win_start, int64_t clip_len,
+                int64_t sig_len, hipStream_t s) {
   const DevWeights& w = h->w;
-  float* X0 = ws + l.x0;
-  float* A = ws + l.bufA;
-  float* P = ws + l.bufB;
-  const int iB = (int)B;
+  FrontendParams f{};
+  f.audio = audio;
+  f.audio_i16 = audio_i16;
+  f.clip_stride = clip_stride;
+  f.n_clips = (int32_t)n_clips;
+  f.n_win = n_win;
+  f.win_start = win_start;
+  f.clip_len = clip_len;
+  f.sig_len = sig_len;
+  f.T = (int32_t)p.g.T;
+  f.hop = h->cfg.hop_size;
+  f.twiddle = reinterpret_cast<const float2*>(w.twiddle);
+  f.window = w.window;
+  f.mel_w = w.mel_w;
+  f.mel_tab = w.mel_tab;
+  f.mel_mt = h->tune.mel_mfma ? w.mel_mt : nullptr;   // the MFMA mel table (nullptr when the host did not build one)
+  for (int j = 0; j < 4; ++j) {
+    f.mt_klo[j] = w.mt_klo[j];
+    f.mt_ns[j] = w.mt_ns[j];
+    f.mt_off[j] = w.mt_off[j];
+  }
+  f.mt_floats = w.mt_floats;
+  f.mel_wmax = w.mel_wmax;
+  f.mel_off = w.mel_off;
+  f.mel_lo = w.mel_lo;
+  f.bn_scale = w.bn0_scale;
+  f.bn_mean = w.bn0_mean;
+  f.bn_bias = w.bn0_bias;
+  f.out = ws + p.x0.off;
+  launch_logmel(f, h->cfg.window_size, s);
+}
+
+// CNN + head on X0 [B][T][64] already in the workspace: every kernel choice
+// and every pointer comes from the plan
+sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_fw, float* d_clip, float* d_emb,
+                     hipStream_t s) {
+  const DevWeights& w = h->w;
+  const Tuning& t = h->tune;
+  const Geometry& g = p.g;
+  const int64_t B = p.B;
+  const int iB = (int)B, M = p.M, T3 = (int)g.T3;
+  float* X0 = ws + p.x0.off;
+  float* A = ws + p.A.off;
+  int* sched = reinterpret_cast<int*>(ws + p.sched.off);
   // the cross-stream wait for the previous forward's conv stack comes before
   // the b1c1 stage event, so stage 1 times only this forward's work
   mark(h, 12, s);   // the frontend's end: the wait below is stage 11, not the frontend's
-  const bool x3 = h->precision == SEDX_PRECISION_X3;
-  int* sched = reinterpret_cast<int*>(ws + l.sched);
-  const bool wb1 = wino_block1_on(h);
-  // winograd with F(4x4,3x3): block 1 (one launch) and blocks 2-4 keep their
-  // activations in the chunk-of-4 layout [B][C/4][T][F][4] (dense halo DMA)
-  const bool c4 = h->precision == SEDX_PRECISION_WINOGRAD && h->wino_f43 && wb1 && h->wino_block1 == 2;
-  // Winograd block 1: 1 = conv1's activation [B][T][64][64] into A by its
-  // own launch; 2 = conv1 inside the Winograd launch (reads X0 itself).
-  // F(4x4,3x3) block 1 (wino_f43 2): conv1 by its own launch in both (2: in
-  // the chunk-of-4 layout), then the F(4x4,3x3) conv2
-  const bool b1_43 = wb1 && h->wino_f43 == 2;
   // block 1's first launch (conv1 / the zero-bordered copy of X0): before
   // the pipelined wait with sedx_set_pipelined(h, 2) — an HBM-bound launch
   // that may then overlap the previous forward's compute-bound conv tail —
   // else after it (stage 1)
   auto block1_first = [&]() {
-    if (b1_43 && c4)
-      launch_conv1_c4(X0, iB, (int)g.T, w.c1_w, w.c1_b, A, s);
-    else if (wb1 && (h->wino_block1 == 1 || b1_43))
-      launch_conv1_nhwc(X0, iB, (int)g.T, w.c1_w, w.c1_b, A, s);
-    else if (!wb1)
-      launch_pad_x0(X0, iB, (int)g.T, A, s);
+    switch (p.block1) {
+      case B1_CONV1C4_F43: launch_conv1_c4(X0, iB, (int)g.T, w.c1_w, w.c1_b, A, s); break;
+      case B1_CONV1_F23:
+      case B1_CONV1_F43: launch_conv1_nhwc(X0, iB, (int)g.T, w.c1_w, w.c1_b, A, s); break;
+      case B1_PAD_EXACT:
+      case B1_PAD_X3: launch_pad_x0(X0, iB, (int)g.T, A, s); break;
+      case B1_F23_FUSED: break;   // conv1 inside the stage-2 launch
+    }
   };
-  // claim counters of the x3 launches and of the F(4x4,3x3) launches (the
-  // workspace comes from the caller: zeroed once per forward, ahead of the
-  // pipelined wait — this forward's memory only).  Below 8 clips the
-  // F(4x4,3x3) launches get no counters (the static item order, same
-  // outputs) and the forward no memset: one fill launch less on the
-  // one-clip latency path
-  const bool w43 = h->precision == SEDX_PRECISION_WINOGRAD && h->wino_f43 && B >= 8;
-  int* const w43_sched = w43 ? sched : nullptr;
-  if (x3 || w43) HIP_TRY(h, hipMemsetAsync(sched, 0, 7 * CONV_SCHED_INTS * sizeof(int), s));
-  const bool first_early = h->pipelined && h->pipe_conv1_first;
+  // the claim counters (the workspace comes from the caller): zeroed once per
+  // forward, ahead of the pipelined wait — this forward's memory only
+  if (p.claims) HIP_TRY(h, hipMemsetAsync(sched, 0, 7 * CONV_SCHED_INTS * sizeof(int), s));
+  const bool first_early = t.pipelined && t.pipe_conv1_first;
   if (first_early) block1_first();
-  if (h->pipelined && h->conv_done_recorded) HIP_TRY(h, hipStreamWaitEvent(s, h->conv_done, 0));
+  if (t.pipelined && h->conv_done_recorded) HIP_TRY(h, hipStreamWaitEvent(s, h->conv_done, 0));
   mark(h, 1, s);
   capture(h, 0, X0, (size_t)B * g.T * 64, s);
-  // block 1 as one launch in both modes: conv1 computed inside conv2's halo
-  // staging (the b1c1 stage is just the zero-bordered copy of the bn0 output)
   if (!first_early) block1_first();
-  struct L {
-    const float* in;
-    int T, F, cin, cout, idx, epi;
-    float* out;
-  };
-  const L layers[7] = {{A, (int)g.T, 64, 64, 64, 1, EPI_POOL2, P},
-                       {P, (int)g.T1, 32, 64, 128, 2, EPI_STORE, A},
-                       {A, (int)g.T1, 32, 128, 128, 3, EPI_POOL2, P},
-                       {P, (int)g.T2, 16, 128, 256, 4, EPI_STORE, A},
-                       {A, (int)g.T2, 16, 256, 256, 5, EPI_POOL2, P},
-                       {P, (int)g.T3, 8, 256, 512, 6, EPI_STORE, A},
-                       {A, (int)g.T3, 8, 512, 512, 7, EPI_FMEAN, P}};
   for (int i = 0; i < 7; ++i) {
-    const L& c = layers[i];
+    const ConvLayer& c = p.layers[i];
+    const int k = i + 1;   // the layer's weights
+    float* in = ws + c.in;
+    float* out = ws + c.out;
+    int* claim = p.claims ? sched + i * CONV_SCHED_INTS : nullptr;
     mark(h, 2 + i, s);
-    if (x3 && i == 0)
-      launch_block1_fused_x3(nullptr, iB, c.T, A, w.c1_wt, w.c1_b, w.wx3[c.idx], w.cb[c.idx], c.out,
-                             sched, s);
-    else if (i == 0 && b1_43)
-      launch_conv3x3_wino43(A, iB, c.T, 64, 64, 64, w.wu43[c.idx], w.cb[c.idx], c.out, EPI_POOL2, w.trash, s,
-                            h->wino_order, c4, 0, w43_sched);
-    else if (i == 0 && wb1 && h->wino_block1 == 2)
-      launch_block1_wino(X0, iB, c.T, w.c1_w, w.c1_b, w.wu[c.idx], w.cb[c.idx], c.out, w.zero, w.trash, s, c4);
-    else if (i == 0 && wb1)
-      launch_conv3x3_wino(A, iB, c.T, 64, 64, 64, w.wu[c.idx], w.cb[c.idx], c.out, EPI_POOL2, w.zero, w.trash, s);
-    else if (i == 0)
-      launch_block1_exact(A, iB, c.T, w.c1_w, w.c1_b, w.wp[c.idx], w.cb[c.idx], c.out, w.zero, s);
-    else if (x3)
-      launch_conv3x3_x3(c.in, iB, c.T, c.F, c.cin, c.cout, w.wx3[c.idx], w.cb[c.idx], c.out, c.epi,
-                        sched + i * CONV_SCHED_INTS, s);
-    else if (h->precision == SEDX_PRECISION_WINOGRAD && h->wino_f43)
-      launch_conv3x3_wino43(c.in, iB, c.T, c.F, c.cin, c.cout, w.wu43[c.idx], w.cb[c.idx], c.out, c.epi, w.trash, s,
-                            h->wino_order, c4, 0, w43 ? sched + i * CONV_SCHED_INTS : nullptr);
-    else if (h->precision == SEDX_PRECISION_WINOGRAD)
-      launch_conv3x3_wino(c.in, iB, c.T, c.F, c.cin, c.cout, w.wu[c.idx], w.cb[c.idx], c.out, c.epi, w.zero, w.trash,
-                          s, h->wino_order);
+    // block 1 as one launch: conv1 computed inside conv2's halo staging (the
+    // b1c1 stage is just the zero-bordered copy of the bn0 output), or conv2
+    // on conv1's activation
+    const Block1Form b1 = p.block1;
+    if (i == 0 && b1 == B1_PAD_X3)
+      launch_block1_fused_x3(nullptr, iB, c.T, in, w.c1_wt, w.c1_b, w.wx3[k], w.cb[k], out, claim, s);
+    else if (i == 0 && b1 == B1_F23_FUSED)
+      launch_block1_wino(in, iB, c.T, w.c1_w, w.c1_b, w.wu[k], w.cb[k], out, w.zero, w.trash, s, p.c4);
+    else if (i == 0 && b1 == B1_CONV1_F23)
+      launch_conv3x3_wino(in, iB, c.T, c.F, c.cin, c.cout, w.wu[k], w.cb[k], out, c.epi, w.zero, w.trash, s);
+    else if (i == 0 && b1 == B1_PAD_EXACT)
+      launch_block1_exact(in, iB, c.T, w.c1_w, w.c1_b, w.wp[k], w.cb[k], out, w.zero, s);
+    else if (i == 0 || p.family == CONV_WINO43)   // B1_CONV1_F43, B1_CONV1C4_F43: conv2 on conv1's activation
+      launch_conv3x3_wino43(in, iB, c.T, c.F, c.cin, c.cout, w.wu43[k], w.cb[k], out, c.epi, w.trash, s,
+                            t.wino_order, p.c4, 0, claim);
+    else if (p.family == CONV_X3)
+      launch_conv3x3_x3(in, iB, c.T, c.F, c.cin, c.cout, w.wx3[k], w.cb[k], out, c.epi, claim, s);
+    else if (p.family == CONV_WINO)
+      launch_conv3x3_wino(in, iB, c.T, c.F, c.cin, c.cout, w.wu[k], w.cb[k], out, c.epi, w.zero, w.trash, s,
+                          t.wino_order);
     else
-      launch_conv3x3(c.in, iB, c.T, c.F, c.cin, c.cout, w.wp[c.idx], w.cb[c.idx], c.out, c.epi, w.zero, s);
-    const size_t px = c.epi == EPI_STORE ? (size_t)c.T * c.F : c.epi == EPI_POOL2 ? (size_t)(c.T / 2) * (c.F / 2)
-                                                                                   : (size_t)c.T;
-    if (c4 && c.epi != EPI_FMEAN) {
-      const int To = c.epi == EPI_POOL2 ? c.T / 2 : c.T, Fo = c.epi == EPI_POOL2 ? c.F / 2 : c.F;
-      capture_c4(h, 2 + i, c.out, B, To, Fo, c.cout, s);
-    } else {
-      capture(h, 2 + i, c.out, (size_t)B * px * c.cout, s);
-    }
+      launch_conv3x3(in, iB, c.T, c.F, c.cin, c.cout, w.wp[k], w.cb[k], out, c.epi, w.zero, s);
+    if (p.c4 && c.epi != EPI_FMEAN)
+      capture_c4(h, 2 + i, out, B, c.To, c.Fo, c.cout, s);
+    else
+      capture(h, 2 + i, out, (size_t)B * c.To * c.Fo * c.cout, s);
   }
   mark(h, 9, s);
-  if (h->pipelined) {
+  if (t.pipelined) {
     HIP_TRY(h, hipEventRecord(h->conv_done, s));
     h->conv_done_recorded = true;
   }
-  float* S = P;                                   // [B][T3][512]
-  const int M = (int)(B * g.T3);
-  float* G = A;                                   // [M][1536]
-  float* Hs = A + align_up((size_t)M * 1536);     // [M][512]
-  float* O = Hs + align_up((size_t)M * 512);      // [M][512]
-  float* LG = O + align_up((size_t)M * 512);      // [M][nac] (the Conformer branch places its own)
+  const bool x3 = t.precision == SEDX_PRECISION_X3;
+  float* S = ws + p.P.off;                        // [B][T3][512]
+  float* G = ws + p.G.off;
+  float* Hs = ws + p.Hs.off;
+  float* O = ws + p.O.off;
+  float* LG = ws + p.LG.off;
   // GEMMs: x3 split-bf16 MFMA in x3 mode, fp32 MFMA in exact mode
   auto linear = [&](const float* a, const float* wf, void* wx, int n, int bn, const float* bias, float* c,
                     int act) {
@@ -410,17 +350,13 @@ sedx_status run_body(sedx_handle* h, int64_t B, const Geometry& g, float* ws, co
   // layer: no projection, no recurrence / MHA launch) the stage-8 buffer itself
   const float* HI = h->seq == SEQ_NONE ? S : Hs;
   if (h->seq == SEQ_CONFORMER) {
-    // fp32 in every precision mode.  In A: x [M][144] (updated in place by
-    // the residual epilogues), LayerNorm(x), the hidden [M][<= 576], the
-    // attention / depthwise output, r | r_k [3][T3][144], the logits
-    const int T3 = (int)g.T3;
-    float* X = A;
-    float* Xn = X + align_up((size_t)M * CF_D);
-    float* Hb = Xn + align_up((size_t)M * CF_D);
-    float* AV = Hb + align_up((size_t)M * CF_FF);
-    float* Rr = AV + align_up((size_t)M * CF_D);
-    float* RK = Rr + align_up((size_t)CF_BLOCKS * T3 * CF_D);
-    LG = RK + align_up((size_t)CF_BLOCKS * T3 * CF_D);
+    // fp32 in every precision mode; x is updated in place by the residual epilogues
+    float* X = ws + p.X.off;
+    float* Xn = ws + p.Xn.off;
+    float* Hb = ws + p.Hb.off;
+    float* AV = ws + p.AV.off;
+    float* Rr = ws + p.Rr.off;
+    float* RK = ws + p.RK.off;
     const size_t nx = (size_t)M * CF_D;
     // r and r_k = r_net(r) of every block: on device, every forward
     launch_cf_relpos(w.cf_inv_freq, T3, CF_BLOCKS, Rr, s);
@@ -459,32 +395,14 @@ sedx_status run_body(sedx_handle* h, int64_t B, const Geometry& g, float* ws, co
     HI = X;
   } else if (h->seq == SEQ_GRU) {
     linear(S, w.w_ih, w.w_ih_x3, 1536, 128, w.b_ih, G, 0);
-    if (h->gru_kernel == SEDX_GRU_KERNEL_SIMPLE)
-      launch_gru(G, iB, (int)g.T3, w.whhT, w.bhh, Hs, s);
+    if (p.gru_variant < 0)
+      launch_gru(G, iB, T3, w.whhT, w.bhh, Hs, s);
     else
-      launch_gru_coop(G, iB, (int)g.T3, w.whh, w.bhh, Hs, LG + align_up((size_t)M * h->nac), !x3,
-                      h->gru_handoff == SEDX_GRU_HANDOFF_AUTO || h->gru_handoff == SEDX_GRU_HANDOFF_LOCAL,
-                      h->gru_kernel == SEDX_GRU_KERNEL_TAG16 ? 0 : h->gru_kernel == SEDX_GRU_KERNEL_TAG8 ? 1
-                      : h->gru_kernel == SEDX_GRU_KERNEL_COOP16 ? 3
-                      : h->gru_kernel == SEDX_GRU_KERNEL_KSPLIT ? 4
-                      : h->gru_kernel == SEDX_GRU_KERNEL_PAIR ? 5
-                      // AUTO: 16 slices (half the recurrence's serial product); on a
-                      // pipelined handle dealt over every XCD (SPREAD, below): beside
-                      // the next batch's conv stack the shorter recurrence then costs
-                      // it less than the 8-slice kernel's half-size footprint
-                      // (12,238-12,303 vs 11,886-11,923 clips/s, profiles/r05za_*)
-                      : h->gru_kernel == SEDX_GRU_KERNEL_AUTO ? 3 : 2,
-                      h->gru_err_dev, h->gru_spin, s,
-                      // AUTO on a pipelined handle: the recurrence runs beside the
-                      // next batch's conv stack, whose items are dealt to the 8
-                      // XCDs evenly — slices on one XCD cost that XCD a quarter
-                      // of its CUs and the whole launch waits for it (b1c2 0.61
-                      // vs 0.51 ms in the timed region, profiles/r05t_*)
-                      h->gru_handoff == SEDX_GRU_HANDOFF_SPREAD ||
-                          (h->gru_handoff == SEDX_GRU_HANDOFF_AUTO && h->pipelined));
+      launch_gru_coop(G, iB, T3, w.whh, w.bhh, Hs, ws + p.gru.off, !x3, p.gru_fast, p.gru_variant, h->gru_err_dev,
+                      (unsigned)t.gru_spin, s, p.gru_spread);
   } else if (h->seq == SEQ_MHA) {
     linear(S, w.wqkv, w.wqkv_x3, 1536, 128, w.bqkv, G, 0);
-    launch_mha(G, iB, (int)g.T3, O, s);
+    launch_mha(G, iB, T3, O, s);
     linear(O, w.wfc, w.wfc_x3, 512, 128, w.bfc, Hs, 1);
   }
   capture(h, 9, HI, (size_t)M * h->hw, s);
@@ -495,134 +413,14 @@ sedx_status run_body(sedx_handle* h, int64_t B, const Geometry& g, float* ws, co
   else
     linear(HI, w.wac, w.wac_x3, h->nac, 64, w.bac, LG, 0);
   if (h->head == HEAD_ATT)
-    launch_att_head(LG, iB, (int)g.T3, h->cfg.classes_num, h->nac, (int)g.out_frames, d_fw, d_clip,
+    launch_att_head(LG, iB, T3, h->cfg.classes_num, h->nac, (int)g.out_frames, d_fw, d_clip,
                     h->emb_cla ? d_emb : nullptr, s);
   else
-    launch_fc_head(LG, iB, (int)g.T3, h->cfg.classes_num, h->nac, h->head == HEAD_FC_MAX, d_fw, d_clip, s,
+    launch_fc_head(LG, iB, T3, h->cfg.classes_num, h->nac, h->head == HEAD_FC_MAX, d_fw, d_clip, s,
                    (int)g.out_frames);
-  if (!h->emb_cla && d_emb) launch_transpose_btd(HI, iB, (int)g.T3, h->hw, d_emb, s);
+  if (!h->emb_cla && d_emb) launch_transpose_btd(HI, iB, T3, h->hw, d_emb, s);
   mark(h, 11, s);
   return launch_status(h);
-}
-
-// -------- windowed drivers (predict.py:297-349 / main_strong.py:786-835) --------
-// windows fed to the model as one batch: consecutive windows of one length
-// (every predict.py window; main_strong's full windows, then each window
-// that runs past the 10 s padded clip on its own)
-struct WinGroup {
-  int w0 = 0, nw = 0;
-  int64_t len = 0;
-  Geometry g{};
-};
-struct WinGeom {
-  WindowLoop loop;
-  int n_win = 0;
-  int64_t full_len = 0;     // samples of a full window (sample_duration * sr)
-  int64_t clip_len = 0;     // samples backing each clip (beyond: pad_truncate zeros)
-  int64_t step = 0;         // int(100 * overlap_value)
-  int sd = 0;
-  std::vector<WinGroup> groups;
-  MergePlan plan;
-};
-
-sedx_status window_geometry(const sedx_handle* h, int64_t L_clip, const sedx_window_spec* spec, bool avg,
-                            WinGeom* wg) {
-  sedx_handle* hm = const_cast<sedx_handle*>(h);
-  if (!spec) return fail(hm, SEDX_EINVAL, "null window spec");
-  const int sr = h->cfg.sample_rate;
-  if (const char* why = window_loop(sr, L_clip, *spec, &wg->loop)) return fail(hm, SEDX_EINVAL, "%s", why);
-  // int(100 * overlap_value) in float64 (utilities.py:406, :426)
-  const double stepd = 100.0 * spec->overlap_value;
-  if (!(std::fabs(stepd) < 1e9)) return fail(hm, SEDX_EINVAL, "overlap_value out of range");
-  wg->step = (int64_t)stepd;
-  wg->sd = spec->sample_duration;
-  wg->n_win = (int)wg->loop.start.size();
-  wg->full_len = (int64_t)spec->sample_duration * sr;
-  wg->clip_len = spec->driver == SEDX_DRIVER_MAIN_STRONG ? std::min<int64_t>(L_clip, (int64_t)sr * 10) : L_clip;
-  wg->groups.clear();
-  std::vector<int64_t> frames(wg->n_win);
-  for (int w = 0; w < wg->n_win; ++w) {
-    const int64_t len = wg->loop.len[w];
-    // the model raises on these windows: STFT reflect padding needs more
-    // than n_fft/2 samples (stft.py:237), the third 2x2 pool one frame
-    // (models.py:139)
-    if (len <= h->cfg.window_size / 2)
-      return fail(hm, SEDX_EINVAL, "window %d has %lld samples: too short for the STFT's reflect padding", w,
-                  (long long)len);
-    if (wg->groups.empty() || wg->groups.back().len != len) {
-      WinGroup g;
-      g.w0 = w;
-      g.len = len;
-      g.g = geometry_from_T(h, conv_T(h, len));
-      if (g.g.T3 < 1) return fail(hm, SEDX_EINVAL, "window %d too short for the CNN", w);
-      if (seq_too_long(h, g.g.T3))
-        return fail(hm, SEDX_EINVAL, "window %d gives %lld sequence frames: the Conformer encoder holds %d", w,
-                    (long long)g.g.T3, CF_MAX_T);
-      wg->groups.push_back(g);
-    }
-    ++wg->groups.back().nw;
-    frames[w] = wg->groups.back().g.out_frames;
-  }
-  if (const char* why = build_merge_plan(frames, wg->step, wg->sd, avg, &wg->plan))
-    return fail(hm, SEDX_EINVAL, "%s", why);
-  return SEDX_OK;
-}
-
-// per-call device area after the model workspace: per-window framewise and
-// clipwise outputs, vote thresholds, then the tables (window starts, output
-// bases, merge plan), all at 256-B aligned float offsets
-struct WinLayout {
-  size_t model_bytes = 0;             // max over the groups' ws_layout
-  std::vector<size_t> fw_off, clip_off;   // per group, floats from the area start
-  size_t vthr = 0, tables = 0, table_bytes = 0, total_bytes = 0;
-  size_t t_start = 0, t_wb = 0, t_wcs = 0, t_off = 0, t_src = 0, t_div = 0;   // byte offsets in the tables
-};
-
-WinLayout win_layout(const sedx_handle* h, int64_t n_clips, const WinGeom& wg) {
-  WinLayout l;
-  const int64_t C = h->cfg.classes_num;
-  for (const auto& g : wg.groups) l.model_bytes = std::max(l.model_bytes, ws_layout(h, n_clips * g.nw, g.g).total_bytes);
-  size_t off = l.model_bytes / sizeof(float);
-  for (const auto& g : wg.groups) {
-    l.fw_off.push_back(off);
-    off += align_up((size_t)n_clips * g.nw * g.g.out_frames * C);
-  }
-  for (const auto& g : wg.groups) {
-    l.clip_off.push_back(off);
-    off += align_up((size_t)n_clips * g.nw * C);
-  }
-  l.vthr = off;
-  off += align_up(2 * (size_t)C);
-  l.tables = off;
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  size_t b = 0;
-  l.t_start = b; b += al(8 * (size_t)wg.n_win);
-  l.t_wb = b;    b += al(8 * (size_t)wg.n_win);
-  l.t_wcs = b;   b += al(8 * (size_t)wg.n_win);
-  l.t_off = b;   b += al(4 * ((size_t)wg.plan.N + 1));
-  l.t_src = b;   b += al(8 * wg.plan.src.size());
-  l.t_div = b;   b += al(4 * (size_t)wg.plan.N);
-  l.table_bytes = b;
-  l.total_bytes = off * sizeof(float) + b;
-  return l;
-}
-
-// the MFMA mel table (nullptr when the host did not build one)
-void set_mel_mt(FrontendParams& p, const DevWeights& w, int on) {
-  p.mel_mt = on ? w.mel_mt : nullptr;
-  for (int j = 0; j < 4; ++j) {
-    p.mt_klo[j] = w.mt_klo[j];
-    p.mt_ns[j] = w.mt_ns[j];
-    p.mt_off[j] = w.mt_off[j];
-  }
-  p.mt_floats = w.mt_floats;
-}
-
-template <typename T>
-T* carve(char*& p, size_t n) {
-  T* r = reinterpret_cast<T*>(p);
-  p += (n * sizeof(T) + 255) & ~size_t(255);
-  return r;
 }
 
 }  // namespace
@@ -643,7 +441,7 @@ sedx_status sedx_set_precision(sedx_handle* h, int32_t mode) {
   if (!h) return SEDX_EINVAL;
   if (mode != SEDX_PRECISION_EXACT && mode != SEDX_PRECISION_X3 && mode != SEDX_PRECISION_WINOGRAD)
     return fail(h, SEDX_EINVAL, "unknown precision mode %d", mode);
-  h->precision = mode;
+  h->tune.precision = mode;
   return SEDX_OK;
 }
 
@@ -671,48 +469,24 @@ sedx_status sedx_set_capture(sedx_handle* h, int32_t stage, float* d_buf, size_t
 
 sedx_status sedx_set_tuning(sedx_handle* h, int32_t knob, int32_t value) {
   if (!h) return SEDX_EINVAL;
-  switch (knob) {
-    case SEDX_TUNE_GRU_KERNEL:
-      if (value != SEDX_GRU_KERNEL_COOP && value != SEDX_GRU_KERNEL_SIMPLE && value != SEDX_GRU_KERNEL_TAG16 &&
-          value != SEDX_GRU_KERNEL_TAG8 && value != SEDX_GRU_KERNEL_COOP16 && value != SEDX_GRU_KERNEL_AUTO &&
-          value != SEDX_GRU_KERNEL_KSPLIT && value != SEDX_GRU_KERNEL_PAIR)
-        break;
-      h->gru_kernel = value;
-      return SEDX_OK;
-    case SEDX_TUNE_GRU_HANDOFF:
-      if (value != SEDX_GRU_HANDOFF_AUTO && value != SEDX_GRU_HANDOFF_GLOBAL && value != SEDX_GRU_HANDOFF_SPREAD &&
-          value != SEDX_GRU_HANDOFF_LOCAL)
-        break;
-      h->gru_handoff = value;
-      return SEDX_OK;
-    case SEDX_TUNE_WINO_BLOCK1:
-      if (value != 0 && value != 1 && value != 2) break;
-      h->wino_block1 = value;
-      return SEDX_OK;
-    case SEDX_TUNE_MEL_MFMA:
-      if (value != 0 && value != 1) break;
-      h->mel_mfma = value;
-      return SEDX_OK;
-    case SEDX_TUNE_GRU_SPIN:
-      if (value < 0) break;
-      h->gru_spin = (unsigned)value;
-      return SEDX_OK;
-    case SEDX_TUNE_WINO_ORDER:
-      if (value < 0 || value > 2) break;
-      h->wino_order = value;
-      return SEDX_OK;
-    case SEDX_TUNE_GAMMA_SPEC:
-      if (value != 0 && value != 1) break;
-      h->gamma_spec = value;
-      return SEDX_OK;
-    case SEDX_TUNE_WINO_F43:
-      if (value < 0 || value > 2) break;
-      h->wino_f43 = value;
-      return SEDX_OK;
-    default:
-      return fail(h, SEDX_EINVAL, "unknown tuning knob %d", (int)knob);
+  static const struct {
+    int knob, lo, hi;   // every value in [lo, hi] is one the header names
+    int Tuning::*field;
+  } knobs[] = {{SEDX_TUNE_GRU_KERNEL, SEDX_GRU_KERNEL_COOP, SEDX_GRU_KERNEL_PAIR, &Tuning::gru_kernel},
+               {SEDX_TUNE_GRU_HANDOFF, SEDX_GRU_HANDOFF_AUTO, SEDX_GRU_HANDOFF_LOCAL, &Tuning::gru_handoff},
+               {SEDX_TUNE_WINO_BLOCK1, 0, 2, &Tuning::wino_block1},
+               {SEDX_TUNE_MEL_MFMA, 0, 1, &Tuning::mel_mfma},
+               {SEDX_TUNE_GRU_SPIN, 0, INT32_MAX, &Tuning::gru_spin},
+               {SEDX_TUNE_WINO_ORDER, 0, 2, &Tuning::wino_order},
+               {SEDX_TUNE_GAMMA_SPEC, 0, 1, &Tuning::gamma_spec},
+               {SEDX_TUNE_WINO_F43, 0, 2, &Tuning::wino_f43}};
+  for (const auto& k : knobs) {
+    if (k.knob != knob) continue;
+    if (value < k.lo || value > k.hi) return fail(h, SEDX_EINVAL, "bad value %d for tuning knob %d", (int)value, (int)knob);
+    h->tune.*k.field = value;
+    return SEDX_OK;
   }
-  return fail(h, SEDX_EINVAL, "bad value %d for tuning knob %d", (int)value, (int)knob);
+  return fail(h, SEDX_EINVAL, "unknown tuning knob %d", (int)knob);
 }
 
 sedx_status sedx_check_error(sedx_handle* h) {
@@ -734,7 +508,6 @@ sedx_status sedx_create(const sedx_config* cfg, int device, sedx_handle** out) {
   sedx_handle* h = new sedx_handle();
   static_cast<Model&>(*h) = m;
   h->device = device;
-  h->pad100 = cfg->model_type == SEDX_MODEL_GRU_FRAMEATT || m.seq == SEQ_CONFORMER;
   h->emb_cla = m.head == HEAD_ATT && m.seq != SEQ_MHA && m.seq != SEQ_CONFORMER;
   h->expected = expected_params(m);
   *out = h;
@@ -745,7 +518,7 @@ void sedx_destroy(sedx_handle* h) {
   if (!h) return;
   {
     DeviceGuard g(h->device);
-    for (auto& e : h->ev)
+    for (auto& e : h->ev_last.ev)
       if (e) (void)hipEventDestroy(e);
     for (auto& set : h->ev_pool)
       for (auto& e : set.ev)
@@ -791,12 +564,10 @@ sedx_status sedx_finalize_weights(sedx_handle* h) {
     h->w = DevWeights();
   }
   HIP_TRY(h, hipMalloc(&h->blob, blob.image.size()));
-  h->blob_bytes = blob.image.size();
   HIP_TRY(h, hipMemcpy(h->blob, blob.image.data(), blob.image.size(), hipMemcpyHostToDevice));
   blob.bind(h->blob);   // sets w's pointers
   h->w = w;
   h->g_nfft = gg.nfft;
-  h->g_nwin = gg.nwin;
   h->g_hop = gg.hop;
   if (!h->gru_err_host) {
     void* p = nullptr;
@@ -813,10 +584,10 @@ sedx_status sedx_finalize_weights(sedx_handle* h) {
 
 sedx_status sedx_set_profiling(sedx_handle* h, int32_t on) {
   if (!h) return SEDX_EINVAL;
-  DeviceGuard dg(h->device);
-  if (on && !h->ev[0])
-    for (auto& e : h->ev) HIP_TRY(h, hipEventCreate(&e));
   if (on < 0 || on > 2) return fail(h, SEDX_EINVAL, "profiling mode %d (0 off, 1 last forward, 2 accumulate)", (int)on);
+  DeviceGuard dg(h->device);
+  if (on && !h->ev_last.ev[0])
+    for (auto& e : h->ev_last.ev) HIP_TRY(h, hipEventCreate(&e));
   if (h->profiling == 2) fold_ev_pool(h);
   // mode 2: event sets for the first 64 forwards up front, so a timed loop
   // does not create events on the host while it issues work
@@ -825,9 +596,9 @@ sedx_status sedx_set_profiling(sedx_handle* h, int32_t on) {
     for (auto& e : h->ev_pool.back().ev) HIP_TRY(h, hipEventCreate(&e));
   }
   h->profiling = on;
-  for (auto& r : h->ev_recorded) r = false;
+  for (auto& r : h->ev_last.rec) r = false;
   h->ev_used = 0;
-  h->ev_cur = nullptr;
+  h->ev_cur = on == 1 ? &h->ev_last : nullptr;   // mode 2: mark() takes a set per forward
   for (int i = 0; i < SEDX_N_STAGES; ++i) {
     h->acc_ms[i] = 0.0;
     h->acc_n[i] = 0;
@@ -837,11 +608,11 @@ sedx_status sedx_set_profiling(sedx_handle* h, int32_t on) {
 
 sedx_status sedx_set_pipelined(sedx_handle* h, int32_t on) {
   if (!h) return SEDX_EINVAL;
+  if (on < 0 || on > 2) return fail(h, SEDX_EINVAL, "sedx_set_pipelined: on must be 0, 1 or 2");
   DeviceGuard dg(h->device);
   if (on && !h->conv_done) HIP_TRY(h, hipEventCreateWithFlags(&h->conv_done, hipEventDisableTiming));
-  if (on < 0 || on > 2) return fail(h, SEDX_EINVAL, "sedx_set_pipelined: on must be 0, 1 or 2");
-  h->pipelined = on != 0;
-  h->pipe_conv1_first = on == 2;
+  h->tune.pipelined = on != 0;
+  h->tune.pipe_conv1_first = on == 2;
   h->conv_done_recorded = false;
   return SEDX_OK;
 }
@@ -852,23 +623,18 @@ sedx_status sedx_stage_times(sedx_handle* h, float* ms, int32_t capacity, int32_
   if (!h->profiling) return fail(h, SEDX_ESTATE, "profiling is off");
   DeviceGuard dg(h->device);
   if (sedx_status e = check_async_error(h)) return e;
-  if (h->profiling == 2) {
-    fold_ev_pool(h);
-    for (int i = 0; i < SEDX_N_STAGES; ++i) {
-      if (i < capacity) ms[i] = h->acc_n[i] ? (float)(h->acc_ms[i] / (double)h->acc_n[i]) : 0.f;
+  if (h->profiling == 2) fold_ev_pool(h);
+  for (int i = 0; i < SEDX_N_STAGES; ++i) {
+    float v = 0.f;
+    bool rec = false;
+    if (h->profiling == 2) {
+      v = h->acc_n[i] ? (float)(h->acc_ms[i] / (double)h->acc_n[i]) : 0.f;
       h->acc_ms[i] = 0.0;
       h->acc_n[i] = 0;
+    } else if (i < capacity) {
+      HIP_TRY(h, stage_ms(h->ev_last, i, &v, &rec));
     }
-    return SEDX_OK;
-  }
-  for (int i = 0; i < SEDX_N_STAGES && i < capacity; ++i) {
-    float v = 0.f;
-    const int a = stage_begin(i), b = stage_end(i);
-    if (h->ev_recorded[a] && h->ev_recorded[b]) {
-      HIP_TRY(h, hipEventSynchronize(h->ev[b]));
-      HIP_TRY(h, hipEventElapsedTime(&v, h->ev[a], h->ev[b]));
-    }
-    ms[i] = v;
+    if (i < capacity) ms[i] = v;
   }
   return SEDX_OK;
 }
@@ -876,11 +642,8 @@ sedx_status sedx_stage_times(sedx_handle* h, float* ms, int32_t capacity, int32_
 sedx_status sedx_output_geometry(const sedx_handle* h, int64_t L_or_T, int64_t* out_frames,
                                  int64_t* seq_len) {
   if (!h || !out_frames || !seq_len) return SEDX_EINVAL;
-  const int64_t T = (h->cfg.feature_type == SEDX_FEATURE_GAMMA) ? L_or_T : conv_T(h, L_or_T);
-  const Geometry g = geometry_from_T(h, T);
-  if (seq_too_long(h, g.T3))
-    return fail(const_cast<sedx_handle*>(h), SEDX_EINVAL, "%lld sequence frames: the Conformer encoder holds %d",
-                (long long)g.T3, CF_MAX_T);
+  Geometry g;
+  if (sedx_status st = query_geometry(h, L_or_T, &g)) return st;
   *out_frames = g.out_frames;
   *seq_len = g.T3;
   return SEDX_OK;
@@ -888,21 +651,25 @@ sedx_status sedx_output_geometry(const sedx_handle* h, int64_t L_or_T, int64_t* 
 
 sedx_status sedx_workspace_size(const sedx_handle* h, int64_t B, int64_t L_or_T, size_t* bytes) {
   if (!h || !bytes || B <= 0) return SEDX_EINVAL;
-  const int64_t T = (h->cfg.feature_type == SEDX_FEATURE_GAMMA) ? L_or_T : conv_T(h, L_or_T);
-  const Geometry g = geometry_from_T(h, T);
-  if (seq_too_long(h, g.T3))
-    return fail(const_cast<sedx_handle*>(h), SEDX_EINVAL, "%lld sequence frames: the Conformer encoder holds %d",
-                (long long)g.T3, CF_MAX_T);
-  *bytes = ws_layout(h, B, g).total_bytes;
+  Geometry g;
+  if (sedx_status st = query_geometry(h, L_or_T, &g)) return st;
+  ForwardPlan p;
+  plan_forward(*h, h->tune, B, g.T, &p);   // the size of a shape no forward runs is still answered
+  *bytes = p.total_bytes;
   return SEDX_OK;
+}
+
+// the plan of B items of T frames (or why the forward refuses them) and its workspace
+static sedx_status plan_and_workspace(sedx_handle* h, int64_t B, int64_t T, void* d_workspace,
+                                      size_t workspace_bytes, ForwardPlan* p, float** ws) {
+  if (const char* why = plan_forward(*h, h->tune, B, T, p)) return fail(h, SEDX_EINVAL, "%s", why);
+  return get_ws(h, p->total_bytes, d_workspace, workspace_bytes, ws);
 }
 
 static sedx_status forward_wave(sedx_handle* h, const float* d_wave, const int16_t* d_wave16, int64_t B,
                                 int64_t L, float* d_framewise, float* d_clipwise, float* d_embedding,
                                 void* d_workspace, size_t workspace_bytes, void* stream) {
-  if (!h) return SEDX_EINVAL;
-  if (!h->finalized) return fail(h, SEDX_ESTATE, "weights not finalised");
-  if (sedx_status e = check_async_error(h)) return e;
+  if (sedx_status e = preflight(h)) return e;
   if (h->cfg.feature_type != SEDX_FEATURE_LOGMEL)
     return fail(h, SEDX_EINVAL, "gamma models take features: use sedx_forward_features");
   if ((!d_wave && !d_wave16) || !d_framewise || !d_clipwise || B <= 0)
@@ -911,43 +678,14 @@ static sedx_status forward_wave(sedx_handle* h, const float* d_wave, const int16
   if (L <= n2)
     return fail(h, SEDX_EINVAL, "input of %lld samples is too short for reflect padding of %d",
                 (long long)L, n2);
-  const Geometry g = geometry_from_T(h, conv_T(h, L));
-  if (g.T3 < 1) return fail(h, SEDX_EINVAL, "input too short for the 3 pooling stages");
-  if (seq_too_long(h, g.T3))
-    return fail(h, SEDX_EINVAL, "%lld sequence frames: the Conformer encoder holds %d", (long long)g.T3, CF_MAX_T);
-  if (B * g.T > INT32_MAX / 64) return fail(h, SEDX_EINVAL, "batch too large");
   DeviceGuard dg(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const WsLayout l = ws_layout(h, B, g);
+  ForwardPlan p;
   float* ws = nullptr;
-  sedx_status st = get_ws(h, l.total_bytes, d_workspace, workspace_bytes, &ws);
-  if (st != SEDX_OK) return st;
-  FrontendParams p{};
-  p.audio = d_wave;
-  p.audio_i16 = d_wave16;
-  p.clip_stride = L;
-  p.n_clips = (int32_t)B;
-  p.n_win = 1;
-  p.win_start = nullptr;
-  p.clip_len = L;
-  p.sig_len = L;
-  p.T = (int32_t)g.T;
-  p.hop = h->cfg.hop_size;
-  p.twiddle = reinterpret_cast<const float2*>(h->w.twiddle);
-  p.window = h->w.window;
-  p.mel_w = h->w.mel_w;
-  p.mel_tab = h->w.mel_tab;
-  set_mel_mt(p, h->w, h->mel_mfma);
-  p.mel_wmax = h->w.mel_wmax;
-  p.mel_off = h->w.mel_off;
-  p.mel_lo = h->w.mel_lo;
-  p.bn_scale = h->w.bn0_scale;
-  p.bn_mean = h->w.bn0_mean;
-  p.bn_bias = h->w.bn0_bias;
-  p.out = ws + l.x0;
+  if (sedx_status st = plan_and_workspace(h, B, conv_T(*h, L), d_workspace, workspace_bytes, &p, &ws)) return st;
   mark(h, 0, s);
-  launch_logmel(p, h->cfg.window_size, s);
-  return run_body(h, B, g, ws, l, d_framewise, d_clipwise, d_embedding, s);
+  run_logmel(h, p, ws, d_wave, d_wave16, L, B, 1, nullptr, L, L, s);
+  return run_body(h, p, ws, d_framewise, d_clipwise, d_embedding, s);
 }
 
 sedx_status sedx_forward(sedx_handle* h, const float* d_wave, int64_t B, int64_t L,
@@ -969,33 +707,23 @@ sedx_status sedx_forward_i16(sedx_handle* h, const int16_t* d_wave, int64_t B, i
 sedx_status sedx_forward_features(sedx_handle* h, const float* d_feat, int64_t B, int64_t T,
                                   float* d_framewise, float* d_clipwise, float* d_embedding,
                                   void* d_workspace, size_t workspace_bytes, void* stream) {
-  if (!h) return SEDX_EINVAL;
-  if (!h->finalized) return fail(h, SEDX_ESTATE, "weights not finalised");
-  if (sedx_status e = check_async_error(h)) return e;
+  if (sedx_status e = preflight(h)) return e;
   if (!d_feat || !d_framewise || !d_clipwise || B <= 0 || T <= 0)
     return fail(h, SEDX_EINVAL, "null pointer or empty batch");
-  const Geometry g = geometry_from_T(h, T);
-  if (g.T3 < 1) return fail(h, SEDX_EINVAL, "input too short for the 3 pooling stages");
-  if (seq_too_long(h, g.T3))
-    return fail(h, SEDX_EINVAL, "%lld sequence frames: the Conformer encoder holds %d", (long long)g.T3, CF_MAX_T);
   DeviceGuard dg(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const WsLayout l = ws_layout(h, B, g);
+  ForwardPlan p;
   float* ws = nullptr;
-  sedx_status st = get_ws(h, l.total_bytes, d_workspace, workspace_bytes, &ws);
-  if (st != SEDX_OK) return st;
+  if (sedx_status st = plan_and_workspace(h, B, T, d_workspace, workspace_bytes, &p, &ws)) return st;
   mark(h, 0, s);
-  launch_features_bn0(d_feat, (int)B, (int)T, h->w.bn0_scale, h->w.bn0_mean, h->w.bn0_bias,
-                      ws + l.x0, s);
-  return run_body(h, B, g, ws, l, d_framewise, d_clipwise, d_embedding, s);
+  launch_features_bn0(d_feat, (int)B, (int)T, h->w.bn0_scale, h->w.bn0_mean, h->w.bn0_bias, ws + p.x0.off, s);
+  return run_body(h, p, ws, d_framewise, d_clipwise, d_embedding, s);
 }
 
 sedx_status sedx_gamma_features(sedx_handle* h, const float* d_audio, int64_t B, int64_t L,
                                 float* d_feat, int64_t* T_out, void* d_workspace,
                                 size_t workspace_bytes, void* stream) {
-  if (!h) return SEDX_EINVAL;
-  if (!h->finalized) return fail(h, SEDX_ESTATE, "weights not finalised");
-  if (sedx_status e = check_async_error(h)) return e;
+  if (sedx_status e = preflight(h)) return e;
   if (h->cfg.feature_type != SEDX_FEATURE_GAMMA)
     return fail(h, SEDX_EINVAL, "handle was not created with feature_type=gamma");
   if (L < h->g_nfft) return fail(h, SEDX_EINVAL, "clip shorter than the gammatone FFT");
@@ -1011,7 +739,6 @@ sedx_status sedx_gamma_features(sedx_handle* h, const float* d_audio, int64_t B,
   float* ws = nullptr;
   sedx_status st = get_ws(h, need, d_workspace, workspace_bytes, &ws);
   if (st != SEDX_OK) return st;
-  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
   char* base = reinterpret_cast<char*>(ws);
   GammaParams p{};
   p.audio = d_audio;
@@ -1026,23 +753,22 @@ sedx_status sedx_gamma_features(sedx_handle* h, const float* d_audio, int64_t B,
   p.window = h->w.g_window;
   p.weightsT = h->w.g_weightsT;
   p.mag = reinterpret_cast<double*>(base);
-  base += al((size_t)B * T * p.kp * sizeof(double));
+  base += align256((size_t)B * T * p.kp * sizeof(double));
   p.db = reinterpret_cast<double*>(base);
-  base += al((size_t)B * 64 * T * sizeof(double));
+  base += align256((size_t)B * 64 * T * sizeof(double));
   p.mm = reinterpret_cast<unsigned long long*>(base);
   p.out = d_feat;
-  launch_gamma(p, s, h->gamma_spec);
+  launch_gamma(p, s, h->tune.gamma_spec);
   return launch_status(h);
 }
 
 sedx_status sedx_gamma_workspace_size(const sedx_handle* h, int64_t B, int64_t L, size_t* bytes) {
   if (!h) return SEDX_EINVAL;
-  sedx_handle* hm = const_cast<sedx_handle*>(h);   // sedx_last_error's message only
-  if (!bytes || B <= 0) return fail(hm, SEDX_EINVAL, "null size pointer or empty batch");
+  if (!bytes || B <= 0) return fail(h, SEDX_EINVAL, "null size pointer or empty batch");
   if (h->cfg.feature_type != SEDX_FEATURE_GAMMA)
-    return fail(hm, SEDX_EINVAL, "handle was not created with feature_type=gamma");
-  if (!h->finalized) return fail(hm, SEDX_ESTATE, "weights not finalised");
-  if (L < h->g_nfft) return fail(hm, SEDX_EINVAL, "clip shorter than the gammatone FFT");
+    return fail(h, SEDX_EINVAL, "handle was not created with feature_type=gamma");
+  if (!h->finalized) return fail(h, SEDX_ESTATE, "weights not finalised");
+  if (L < h->g_nfft) return fail(h, SEDX_EINVAL, "clip shorter than the gammatone FFT");
   *bytes = gamma_workspace_bytes(B, 1 + (L - h->g_nfft) / h->g_hop, h->g_nfft);
   return SEDX_OK;
 }
@@ -1053,9 +779,9 @@ sedx_status sedx_gamma_workspace_size(const sedx_handle* h, int64_t B, int64_t L
   try {                                                                                     \
     body                                                                                    \
   } catch (const std::bad_alloc&) {                                                         \
-    return fail(const_cast<sedx_handle*>(h), SEDX_ENOMEM, "host allocation failed (merge plan)"); \
+    return fail(h, SEDX_ENOMEM, "host allocation failed (merge plan)");                     \
   } catch (...) {                                                                           \
-    return fail(const_cast<sedx_handle*>(h), SEDX_EINVAL, "host-side failure building the window plan"); \
+    return fail(h, SEDX_EINVAL, "host-side failure building the window plan");              \
   }
 
 sedx_status sedx_window_geometry(const sedx_handle* h, int64_t L_clip, const sedx_window_spec* spec,
@@ -1064,8 +790,8 @@ sedx_status sedx_window_geometry(const sedx_handle* h, int64_t L_clip, const sed
   SEDX_HOST_TRY(h, {
     WinGeom wg;
     // the plan of the forward the spec names: avg_merge rejects a zero step
-    sedx_status st = window_geometry(h, L_clip, spec, spec && spec->vote == 0, &wg);
-    if (st != SEDX_OK) return st;
+    if (const char* why = window_geometry(*h, L_clip, spec, spec && spec->vote == 0, &wg))
+      return fail(h, SEDX_EINVAL, "%s", why);
     if (n_windows) *n_windows = wg.n_win;
     if (window_samples) *window_samples = wg.full_len;
     if (merged_frames) *merged_frames = wg.plan.N;
@@ -1078,17 +804,15 @@ sedx_status sedx_window_geometry(const sedx_handle* h, int64_t L_clip, const sed
 static sedx_status forward_windows_impl(sedx_handle* h, const float* d_audio, int64_t n_clips, int64_t L_clip,
                                         const sedx_window_spec* spec, const double* h_vote_thres, float* d_merged,
                                         void* d_workspace, size_t workspace_bytes, void* stream) {
-  if (!h) return SEDX_EINVAL;
-  if (!h->finalized) return fail(h, SEDX_ESTATE, "weights not finalised");
-  if (sedx_status e = check_async_error(h)) return e;
+  if (sedx_status e = preflight(h)) return e;
   if (h->cfg.feature_type != SEDX_FEATURE_LOGMEL)
     return fail(h, SEDX_EINVAL, "windowed inference needs a logmel model");
   if (!d_audio || !d_merged || n_clips <= 0) return fail(h, SEDX_EINVAL, "null pointer or empty batch");
   if (spec && spec->vote != 0 && h_vote_thres == nullptr)
     return fail(h, SEDX_EINVAL, "spec.vote = 1: call sedx_forward_windows_vote");
   WinGeom wg;
-  sedx_status st = window_geometry(h, L_clip, spec, h_vote_thres == nullptr, &wg);
-  if (st != SEDX_OK) return st;
+  if (const char* why = window_geometry(*h, L_clip, spec, h_vote_thres == nullptr, &wg))
+    return fail(h, SEDX_EINVAL, "%s", why);
   // the frontend and conv launches index items with 32-bit sizes (as forward_wave)
   for (const auto& g : wg.groups)
     if (n_clips > INT32_MAX / g.nw || n_clips * g.nw * g.g.T > INT32_MAX / 64)
@@ -1097,10 +821,9 @@ static sedx_status forward_windows_impl(sedx_handle* h, const float* d_audio, in
     return fail(h, SEDX_EINVAL, "merged output too large");
   DeviceGuard dg(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const WinLayout wl = win_layout(h, n_clips, wg);
+  const WinLayout wl = win_layout(*h, h->tune, n_clips, wg);
   float* ws = nullptr;
-  st = get_ws(h, wl.total_bytes, d_workspace, workspace_bytes, &ws);
-  if (st != SEDX_OK) return st;
+  if (sedx_status st = get_ws(h, wl.total_bytes, d_workspace, workspace_bytes, &ws)) return st;
   const int C = h->cfg.classes_num;
   // tables: built on the host, one copy (the host vector is consumed by the
   // call: pageable-source hipMemcpyAsync stages it before returning)
@@ -1135,32 +858,10 @@ static sedx_status forward_windows_impl(sedx_handle* h, const float* d_audio, in
   mark(h, 0, s);
   for (size_t gi = 0; gi < wg.groups.size(); ++gi) {
     const WinGroup& g = wg.groups[gi];
-    const WsLayout l = ws_layout(h, n_clips * g.nw, g.g);
-    FrontendParams p{};
-    p.audio = d_audio;
-    p.clip_stride = L_clip;
-    p.n_clips = (int32_t)n_clips;
-    p.n_win = g.nw;
-    p.win_start = d_start + g.w0;
-    p.clip_len = wg.clip_len;
-    p.sig_len = g.len;
-    p.T = (int32_t)g.g.T;
-    p.hop = h->cfg.hop_size;
-    p.twiddle = reinterpret_cast<const float2*>(h->w.twiddle);
-    p.window = h->w.window;
-    p.mel_w = h->w.mel_w;
-    p.mel_tab = h->w.mel_tab;
-    set_mel_mt(p, h->w, h->mel_mfma);
-    p.mel_wmax = h->w.mel_wmax;
-    p.mel_off = h->w.mel_off;
-    p.mel_lo = h->w.mel_lo;
-    p.bn_scale = h->w.bn0_scale;
-    p.bn_mean = h->w.bn0_mean;
-    p.bn_bias = h->w.bn0_bias;
-    p.out = ws + l.x0;
-    launch_logmel(p, h->cfg.window_size, s);
-    st = run_body(h, n_clips * g.nw, g.g, ws, l, ws + wl.fw_off[gi], ws + wl.clip_off[gi], nullptr, s);
-    if (st != SEDX_OK) return st;
+    ForwardPlan p;
+    if (const char* why = plan_forward(*h, h->tune, n_clips * g.nw, g.g.T, &p)) return fail(h, SEDX_EINVAL, "%s", why);
+    run_logmel(h, p, ws, d_audio, nullptr, L_clip, n_clips, g.nw, d_start + g.w0, wg.clip_len, g.len, s);
+    if (sedx_status st = run_body(h, p, ws, ws + wl.fw_off[gi], ws + wl.clip_off[gi], nullptr, s)) return st;
   }
   MergeArgs a{};
   a.fw = ws + wl.model_bytes / sizeof(float);
@@ -1183,9 +884,9 @@ sedx_status sedx_window_workspace_size(const sedx_handle* h, int64_t n_clips, in
   if (!h || !bytes || n_clips <= 0) return SEDX_EINVAL;
   SEDX_HOST_TRY(h, {
     WinGeom wg;
-    sedx_status st = window_geometry(h, L_clip, spec, spec && spec->vote == 0, &wg);
-    if (st != SEDX_OK) return st;
-    *bytes = win_layout(h, n_clips, wg).total_bytes;
+    if (const char* why = window_geometry(*h, L_clip, spec, spec && spec->vote == 0, &wg))
+      return fail(h, SEDX_EINVAL, "%s", why);
+    *bytes = win_layout(*h, h->tune, n_clips, wg).total_bytes;
     return SEDX_OK;
   })
 }
@@ -1240,13 +941,12 @@ sedx_status sedx_events_device(const float* d_x, int64_t n_clips, int64_t T, int
   hipStream_t s = static_cast<hipStream_t>(stream);
   // per-class parameters -> one packed block in the workspace, one copy
   // (f32 high: the mode-0 compare is float32)
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
   char* p = static_cast<char*>(d_workspace);
   int64_t* counts = reinterpret_cast<int64_t*>(p);
-  p += al(n_clips * C * 8);
+  p += align256(n_clips * C * 8);
   int64_t* slots = reinterpret_cast<int64_t*>(p);
-  p += al(n_clips * C * events_slot_cap(T) * 8);
-  const size_t o_hi = 0, o_lo = al(C * 4), o_ns = o_lo + al(C * 8), o_salt = o_ns + al(C * 8);
+  p += align256(n_clips * C * events_slot_cap(T) * 8);
+  const size_t o_hi = 0, o_lo = align256(C * 4), o_ns = o_lo + align256(C * 8), o_salt = o_ns + align256(C * 8);
   std::vector<char> blob(o_salt + C * 8, 0);
   for (int64_t k = 0; k < C; ++k) {
     reinterpret_cast<float*>(blob.data() + o_hi)[k] = high_thres ? (float)high_thres[k] : 0.f;
@@ -1291,8 +991,7 @@ sedx_status sedx_segment_counts_device(const float* d_x, int64_t n_clips, int64_
     return segment_fail("segment counts: workspace too small: %zu < %zu bytes", workspace_bytes, need);
   hipStream_t s = static_cast<hipStream_t>(stream);
   // thresholds and per-class parameters -> one packed block in the workspace, one copy
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t o_hi = 0, o_lo = al(V * C * 8), o_ns = 2 * al(V * C * 8), o_salt = o_ns + al(C * 8);
+  const size_t o_hi = 0, o_lo = align256(V * C * 8), o_ns = 2 * o_lo, o_salt = o_ns + align256(C * 8);
   std::vector<char> blob(o_salt + C * 8, 0);
   std::memcpy(blob.data() + o_hi, high, V * C * 8);
   std::memcpy(blob.data() + o_lo, low, V * C * 8);

@@ -146,13 +146,11 @@ __global__ __launch_bounds__(64 * CAL_WAVES) void segment_counts_kernel(CalibArg
   }
 }
 
-size_t al256(size_t b) { return (b + 255) & ~size_t(255); }
-
 }  // namespace
 
 size_t calib_workspace_bytes(int64_t C, int64_t V) {
   // hi f64 [V][C] + lo f64 [V][C] + n_smooth [C] + n_salt [C], 256-B aligned pieces
-  return 2 * al256(V * C * 8) + 2 * al256(C * 8);
+  return 2 * align256(V * C * 8) + 2 * align256(C * 8);
 }
 
 int64_t calib_max_frames() { return CAL_MAX_WORDS * 64; }

@@ -794,7 +794,7 @@ static void launch_x3(const float* in, int B, int T, int Cin, int Cout, const ui
 }
 
 // Shapes: Cin a multiple of 32 (the unit stream pairs chunks), Cout a
-// multiple of the n-tile; api.cpp routes only such layers here.
+// multiple of the n-tile; the forward plan's layer table (plan.cpp) holds only such layers.
 void launch_conv3x3_x3(const float* in, int B, int T, int F, int Cin, int Cout, const void* wp,
                        const float* bias, float* out, int epi, int* sched, hipStream_t s) {
   const uint4* w = static_cast<const uint4*>(wp);
@@ -843,8 +843,6 @@ void launch_block1_fused_x3(const float* x0, int B, int T, float* xpad, const fl
     launch_x3_epi<64, 64, EPI_POOL2, true>(xpad, B, T, 64, 64, static_cast<const uint4*>(wp), bias, out,
                                            sched, s, w1, b1);
 }
-
-size_t block1_pad_floats(int B, int T) { return (size_t)B * (T + 2) * 66; }
 
 #ifdef SEDX_CONV_STAMPS
 void conv_stamps_rw(unsigned long long* out8, bool reset) {

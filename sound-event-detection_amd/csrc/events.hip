@@ -164,8 +164,7 @@ int64_t events_slot_cap(int64_t T) { return T / 2 + 2; }
 size_t events_workspace_bytes(int64_t n_series, int64_t T, int64_t C) {
   // counts [n_series] i64 + slots [n_series][T/2+2] int2 + hi f32 [C] + lo f64 [C]
   // + n_smooth [C] + n_salt [C], 256-B aligned pieces
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  return al(n_series * 8) + al(n_series * events_slot_cap(T) * 8) + al(C * 4) + 3 * al(C * 8);
+  return align256(n_series * 8) + align256(n_series * events_slot_cap(T) * 8) + align256(C * 4) + 3 * align256(C * 8);
 }
 
 int64_t events_max_frames() { return EV_MAX_WORDS * 64; }

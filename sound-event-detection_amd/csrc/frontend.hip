@@ -1211,9 +1211,8 @@ __global__ __launch_bounds__(256) void gamma_quant_kernel(GammaParams p) {
 }
 
 size_t gamma_workspace_bytes(int64_t B, int64_t T, int nfft) {
-  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-  return al((size_t)B * T * gamma_kp(nfft) * sizeof(double)) + al((size_t)B * 64 * T * sizeof(double)) +
-         al((size_t)B * 2 * sizeof(unsigned long long));
+  return align256((size_t)B * T * gamma_kp(nfft) * sizeof(double)) + align256((size_t)B * 64 * T * sizeof(double)) +
+         align256((size_t)B * 2 * sizeof(unsigned long long));
 }
 
 template <int NFFT>

@@ -1165,14 +1165,12 @@ __global__ __launch_bounds__(512) void gru_pair_kernel(const float* __restrict__
 #undef GRU_PSTAMP
 }
 
-size_t gru_coop_workspace_bytes(int B) {
-  (void)B;
-  // sync block, then the exchange space: 32-clip kernel 8 pairs x 2 parities
-  // x 32 x 256 floats; tagged kernel 8 pairs x 2 parities x 16 x 256 granules
-  // (the same 512 KB)
-  static_assert((size_t)8 * 2 * 16 * 256 * 8 == (size_t)8 * 2 * 32 * 256 * 4, "exchange space");
-  return ((sizeof(GruSync) + 255) & ~size_t(255)) + (size_t)8 * 2 * 32 * 256 * 4;
-}
+// gru_coop_workspace_bytes (plan.h): sync block, then the exchange space:
+// 32-clip kernel 8 pairs x 2 parities x 32 x 256 floats; tagged kernel 8 pairs
+// x 2 parities x 16 x 256 granules (the same 512 KB)
+static_assert((size_t)8 * 2 * 16 * 256 * 8 == (size_t)8 * 2 * 32 * 256 * 4, "exchange space");
+static_assert(gru_coop_workspace_bytes(0) == align256(sizeof(GruSync)) + (size_t)8 * 2 * 32 * 256 * 4,
+              "plan.h's byte count of the sync block");
 
 template <int NS>
 static void launch_gru_tag(const float* G, int B, int T, const float* whh, const float* bhh, float* H, GruSync* sync,
@@ -1195,7 +1193,7 @@ void launch_gru_coop(const float* G, int B, int T, const float* whh, const float
   const int sp = spread ? 1 : 0;
   if (spread) allow_fast = false;
   GruSync* sync = static_cast<GruSync*>(ws);
-  const size_t sync_bytes = (sizeof(GruSync) + 255) & ~size_t(255);
+  const size_t sync_bytes = align256(sizeof(GruSync));
   float* X = reinterpret_cast<float*>(static_cast<char*>(ws) + sync_bytes);
   const bool valu = exact && B <= GRU_VALU_CLIPS;
   if (exact && !valu && variant == 4) {   // K-split hand-off, 16 slices

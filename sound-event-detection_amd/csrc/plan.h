@@ -1,0 +1,170 @@
+// The host's plan of one forward: its geometry, which kernel runs each conv
+// layer and the recurrence, and where everything lives in the workspace.
+// api.cpp launches from it and sizes the workspace by it, so what a forward
+// writes and what sedx_workspace_size asks for cannot drift apart.  Also the
+// windowed drivers' loop, merge plan (windows.cpp) and device-area layout.
+// Plain C++: no HIP header, so the plans build and run without a GPU
+// (tests/native/asan_driver.cpp).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "../../include/sedx.h"
+#include "weights.h"
+
+namespace sedx {
+
+// every workspace region starts on a 256-byte boundary
+constexpr size_t align256(size_t bytes) { return (bytes + 255) & ~size_t(255); }
+// the one carve: `bytes` at the aligned end of what was carved so far
+inline size_t carve(size_t& end, size_t bytes) {
+  const size_t at = end;
+  end = at + align256(bytes);
+  return at;
+}
+
+// ---- launch contracts the plan shares with the kernels ----------------------
+enum ConvEpi { EPI_STORE = 0, EPI_POOL2 = 1, EPI_FMEAN = 2 };
+constexpr int CONV_SCHED_INTS = 256;   // per conv launch: 8 tile-claim counters, 128 B apart
+// the zero-bordered bn0 output [B][T+2][66] (launch_pad_x0)
+constexpr size_t block1_pad_floats(int B, int T) { return (size_t)B * (T + 2) * 66; }
+// launch_gru_coop's scratch: the 256-byte aligned sync block (gru.hip asserts
+// its size), then the exchange space of 8 pairs x 2 parities x 32 x 256 floats
+constexpr size_t gru_coop_workspace_bytes(int /*B*/) { return 10240 + (size_t)8 * 2 * 32 * 256 * 4; }
+
+// ---- geometry ---------------------------------------------------------------
+struct Geometry {
+  int64_t T, T1, T2, T3, fw_len, out_frames;
+};
+inline int64_t conv_T(const Model& m, int64_t L) { return L / m.cfg.hop_size + 1; }
+// the Conformer encoder's positional table has CF_MAX_T rows; the reference
+// fails on a longer sequence too (embedding.py:30: the add does not broadcast)
+inline bool seq_too_long(const Model& m, int64_t T3) { return m.seq == SEQ_CONFORMER && T3 > CF_MAX_T; }
+Geometry geometry_from_T(const Model& m, int64_t T);
+
+// ---- what the handle's setters store ----------------------------------------
+struct Tuning {
+  int precision = SEDX_PRECISION_WINOGRAD;   // GEMM arithmetic (sedx_set_precision; the default is fp32 Winograd)
+  int gru_kernel = SEDX_GRU_KERNEL_AUTO;     // sedx_set_tuning
+  int gru_handoff = SEDX_GRU_HANDOFF_AUTO;
+  int wino_block1 = 2;                       // SEDX_TUNE_WINO_BLOCK1 (2: conv1 inside the Winograd launch)
+  int wino_f43 = 2;                          // SEDX_TUNE_WINO_F43 (2: blocks 1-4 as F(4x4,3x3), 1: blocks 2-4)
+  int wino_order = 1;                        // SEDX_TUNE_WINO_ORDER (4 x 8 rounds on the 512-channel layers)
+  int mel_mfma = 0;                          // SEDX_TUNE_MEL_MFMA (measured slower: opt-in)
+  int gamma_spec = 0;                        // SEDX_TUNE_GAMMA_SPEC
+  int gru_spin = 1 << 24;                    // SEDX_TUNE_GRU_SPIN: bound of every GRU hand-off spin (polls)
+  // sedx_set_pipelined: conv stacks of successive forwards run in issue order
+  // (each waits for the previous one's conv-done event), whatever streams
+  // they are issued on, so the sequence + head of batch i overlap the conv
+  // stack of batch i+1 instead of two conv stacks sharing the chip
+  bool pipelined = false;
+  bool pipe_conv1_first = false;             // sedx_set_pipelined(h, 2): block 1's first launch before the wait
+};
+
+// ---- the plan ---------------------------------------------------------------
+struct Region {
+  size_t off = 0, floats = 0;   // floats from the workspace start
+};
+// block 1 = a first launch into A (none for F23_FUSED, which reads X0), then the stage-2 launch
+enum Block1Form {
+  B1_PAD_EXACT,     // launch_pad_x0 + launch_block1_exact (exact; Winograd with SEDX_TUNE_WINO_BLOCK1 0)
+  B1_PAD_X3,        // launch_pad_x0 + launch_block1_fused_x3
+  B1_F23_FUSED,     // launch_block1_wino: conv1 inside the F(2x2,3x3) launch
+  B1_CONV1_F23,     // launch_conv1_nhwc + launch_conv3x3_wino
+  B1_CONV1_F43,     // launch_conv1_nhwc + launch_conv3x3_wino43
+  B1_CONV1C4_F43,   // launch_conv1_c4 + launch_conv3x3_wino43 in the chunk-of-4 layout
+};
+enum ConvFamily { CONV_EXACT, CONV_X3, CONV_WINO, CONV_WINO43 };   // layers 2-7
+struct ConvLayer {
+  int T, F, cin, cout, epi;
+  int To, Fo;       // the output's rows and columns ([B][To][Fo][cout]; EPI_FMEAN: Fo = 1)
+  size_t in, out;   // float offsets in the workspace
+};
+struct ForwardPlan {
+  Geometry g{};
+  int64_t B = 0;
+  int M = 0;                       // B * T3: rows of the sequence / head GEMMs
+  Block1Form block1 = B1_PAD_EXACT;
+  ConvFamily family = CONV_EXACT;
+  // winograd with F(4x4,3x3): block 1 and blocks 2-4 keep their activations
+  // in the chunk-of-4 layout [B][C/4][T][F][4] (dense halo DMA)
+  bool c4 = false;
+  // claim counters zeroed once per forward and passed to the conv launches:
+  // always in x3; F(4x4,3x3) from 8 clips (below: the static item order, same
+  // outputs, and no memset: one fill launch less on the one-clip latency path)
+  bool claims = false;
+  ConvLayer layers[7] = {};        // stages 2-8
+  // launch_gru_coop's variant (-1: launch_gru, SEDX_GRU_KERNEL_SIMPLE), allow_fast, spread
+  int gru_variant = 2;
+  bool gru_fast = false, gru_spread = false;
+  Region x0, A, P, sched;          // bn0 output, the two activation buffers, 7 x CONV_SCHED_INTS counters
+  // inside A once the conv stack is done: G/QKV [M][1536], H [M][512], O
+  // [M][512], the logits [M][nac] and the cooperative recurrence's scratch ...
+  Region G, Hs, O, LG, gru;
+  // ... or the Conformer encoder's x [M][144], LayerNorm(x), the hidden [M][576],
+  // the attention / depthwise output, r and r_k [3][T3][144] (and LG)
+  Region X, Xn, Hb, AV, Rr, RK;
+  size_t total_bytes = 0;
+  char reject[96] = {};            // plan_forward's reason
+};
+// The plan of B items of T frames.  Always filled (the size queries answer for
+// shapes no forward runs); returns why a forward rejects the shape, else nullptr.
+const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, ForwardPlan* p);
+
+// ---- windowed drivers (windows.cpp) ------------------------------------------
+// loop control of predict.py:297-338 / main_strong.py:786-832: the sample
+// offset of every window and the samples fed to the model for it
+struct WindowLoop {
+  std::vector<int64_t> start, len;
+};
+// nullptr on success, else why the reference's loop raises / never ends
+const char* window_loop(int sample_rate, int64_t L_clip, const sedx_window_spec& sp, WindowLoop* out);
+// utilities.merge replayed window by window on index lists, then avg_merge's
+// divisors: merged frame f = left fold, in order, of the values with packed
+// ids src[off[f] .. off[f+1]) (window w, frame t -> win_base[w] + t), divided
+// by div[f] when div[f] > 1.
+struct MergePlan {
+  int64_t N = 0;
+  std::vector<int32_t> win_base;   // [n_win + 1]
+  std::vector<int32_t> off;        // [N + 1]
+  std::vector<int32_t> src;
+  std::vector<int32_t> div;        // [N]
+};
+const char* build_merge_plan(const std::vector<int64_t>& frames, int64_t step, int sample_duration, bool avg,
+                             MergePlan* plan);
+
+// windows fed to the model as one batch: consecutive windows of one length
+// (every predict.py window; main_strong's full windows, then each window
+// that runs past the 10 s padded clip on its own)
+struct WinGroup {
+  int w0 = 0, nw = 0;
+  int64_t len = 0;
+  Geometry g{};
+};
+struct WinGeom {
+  WindowLoop loop;
+  int n_win = 0;
+  int64_t full_len = 0;     // samples of a full window (sample_duration * sr)
+  int64_t clip_len = 0;     // samples backing each clip (beyond: pad_truncate zeros)
+  int64_t step = 0;         // int(100 * overlap_value)
+  int sd = 0;
+  std::vector<WinGroup> groups;
+  MergePlan plan;
+  char reject[128] = {};    // window_geometry's reason
+};
+// nullptr, or why the spec / clip length is refused (SEDX_EINVAL)
+const char* window_geometry(const Model& m, int64_t L_clip, const sedx_window_spec* spec, bool avg, WinGeom* wg);
+
+// per-call device area after the model workspace: per-window framewise and
+// clipwise outputs, vote thresholds, then the tables (window starts, output
+// bases, merge plan), all at 256-B aligned offsets
+struct WinLayout {
+  size_t model_bytes = 0;                 // max over the groups' plans
+  std::vector<size_t> fw_off, clip_off;   // per group, floats from the area start
+  size_t vthr = 0, tables = 0, table_bytes = 0, total_bytes = 0;
+  size_t t_start = 0, t_wb = 0, t_wcs = 0, t_off = 0, t_src = 0, t_div = 0;   // byte offsets in the tables
+};
+WinLayout win_layout(const Model& m, const Tuning& t, int64_t n_clips, const WinGeom& wg);
+
+}  // namespace sedx

@@ -19,8 +19,11 @@
 #include <vector>
 
 #include "../../include/sedx.h"
-// the host side of the weight contract: the constants the packing shares with
-// the kernels, DevWeights, and every packed layout (weights.cpp)
+// the host side of the contracts, plain C++: weights.h (the constants the
+// packing shares with the kernels, DevWeights, every packed layout) and
+// plan.h (ConvEpi, CONV_SCHED_INTS, block1_pad_floats,
+// gru_coop_workspace_bytes, align256, the forward plan, the window drivers' plans)
+#include "plan.h"
 #include "weights.h"
 
 namespace sedx {
@@ -93,8 +96,6 @@ void launch_pad_x0(const float* x0, int B, int T, float* xpad, hipStream_t s);
 void launch_block1_exact(const float* xpad, int B, int T, const float* w1, const float* b1, const float* wp,
                          const float* bias, float* out, const float* zero16, hipStream_t s);
 
-enum ConvEpi { EPI_STORE = 0, EPI_POOL2 = 1, EPI_FMEAN = 2 };
-constexpr int CONV_SCHED_INTS = 256;   // per conv launch: 8 tile-claim counters, 128 B apart
 // 3x3 conv (pad 1) + folded BN + ReLU (+ epilogue), implicit GEMM on fp32 MFMA.
 //  in [B][T][F][Cin] -> EPI_STORE: [B][T][F][Cout], EPI_POOL2: [B][T/2][F/2][Cout],
 //  EPI_FMEAN: [B][T][Cout].  wp = pack_conv_exact's [Cin/4][9][2][Cout][2] (channel 2 ks + khalf;
@@ -277,7 +278,6 @@ void launch_conv3x3_x3(const float* in, int B, int T, int F, int Cin, int Cout, 
 // computed while its halo is staged (conv_x3.hip)
 void launch_block1_fused_x3(const float* x0, int B, int T, float* xpad, const float* w1, const float* b1,
                             const void* wp, const float* bias, float* out, int* sched, hipStream_t s);
-size_t block1_pad_floats(int B, int T);
 
 // ---- sequence / head ------------------------------------------------------
 // C[M][N] = act(A[M][K] . W[N][K]^T + bias[N]);  act: 0 none, 1 relu
@@ -295,8 +295,7 @@ void launch_gru(const float* G, int B, int T, const float* whhT, const float* bh
 
 // Cooperative bi-GRU recurrence (8 workgroups per (32-clip group, direction)
 // exchanging h slices each step).  whh = W_hh [2][768][256] (natural layout);
-// ws >= gru_coop_workspace_bytes(B) bytes of device scratch (counters + exchange).
-size_t gru_coop_workspace_bytes(int B);
+// ws >= gru_coop_workspace_bytes(B) (plan.h) bytes of device scratch (counters + exchange).
 // exact: fp32 MFMA (else the x3 bf16 split); allow_fast: XCD-local hand-off
 // when the placement allows it (else always the global protocol).
 // host_err (nullable): host-mapped word OR-ed with the failure code when a
@@ -353,26 +352,7 @@ void launch_cf_relattn(const float* QKV, int B, int T, const float* rk, const fl
 void launch_cf_glu_dwconv(const float* Y, int B, int T, const float* wt, const float* bf, float* Z, hipStream_t s);
 
 // ---- windowed drivers (windows.cpp) ---------------------------------------
-// loop control of predict.py:297-338 / main_strong.py:786-832: the sample
-// offset of every window and the samples fed to the model for it
-struct WindowLoop {
-  std::vector<int64_t> start, len;
-};
-// nullptr on success, else why the reference's loop raises / never ends
-const char* window_loop(int sample_rate, int64_t L_clip, const sedx_window_spec& sp, WindowLoop* out);
-// utilities.merge replayed window by window on index lists, then avg_merge's
-// divisors: merged frame f = left fold, in order, of the values with packed
-// ids src[off[f] .. off[f+1]) (window w, frame t -> win_base[w] + t), divided
-// by div[f] when div[f] > 1.
-struct MergePlan {
-  int64_t N = 0;
-  std::vector<int32_t> win_base;   // [n_win + 1]
-  std::vector<int32_t> off;        // [N + 1]
-  std::vector<int32_t> src;
-  std::vector<int32_t> div;        // [N]
-};
-const char* build_merge_plan(const std::vector<int64_t>& frames, int64_t step, int sample_duration, bool avg,
-                             MergePlan* plan);
+// the loop and the merge plan: WindowLoop, MergePlan, window_loop, build_merge_plan (plan.h)
 // GPU merge of every clip by one plan.  Window w of clip c has its framewise
 // output at fw + wb[w] + c * wcs[w] (floats, frames of C classes); the plan's
 // tables (off, src as (window, frame) int2, div) live in device memory.

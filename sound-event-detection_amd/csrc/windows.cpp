@@ -22,7 +22,7 @@
 #include <vector>
 
 #include "../../include/sedx.h"
-#include "sedx_internal.h"
+#include "plan.h"
 
 namespace sedx {
 

@@ -11,7 +11,11 @@
 //  * the weight packing (csrc/weights.cpp): every packed layout read back the
 //    way its kernel addresses it (the staging copy into LDS, then the lane's
 //    fragment read), the split-bf16 bit patterns, the Winograd U values, and
-//    prepare_weights whole for every model on a synthetic state_dict.
+//    prepare_weights whole for every model on a synthetic state_dict;
+//  * the forward and window plans (csrc/plan.cpp): over models, precisions,
+//    knobs, batch sizes and lengths, every workspace region aligned, disjoint
+//    and large enough for what its launch writes by the contracts of
+//    sedx_internal.h, and the kernel choices against literal tables.
 // Any memory error, undefined behaviour or failed check aborts the process
 // (non-zero exit).
 #include <cmath>
@@ -24,6 +28,7 @@
 #include <vector>
 
 #include "../../include/sedx.h"
+#include "../../sound-event-detection_amd/csrc/plan.h"
 #include "../../sound-event-detection_amd/csrc/weights.h"
 
 namespace {
@@ -527,6 +532,185 @@ int check_weights() {
   check_errors(), n += 2;
   return n;
 }
+
+// ---- forward and window plans (csrc/plan.cpp) ---------------------------------
+struct Span {
+  const char* name;
+  size_t off, floats;   // float units
+};
+Span span(const char* name, const Region& r) { return Span{name, r.off, r.floats}; }
+// every span 256-byte aligned and inside [lo, hi) floats, no two overlapping
+void check_spans(const std::vector<Span>& v, size_t lo, size_t hi, const char* what) {
+  for (size_t i = 0; i < v.size(); ++i) {
+    CHECK(v[i].off * 4 % 256 == 0, "%s: %s at float %zu is not 256-byte aligned", what, v[i].name, v[i].off);
+    CHECK(v[i].off >= lo && v[i].off + v[i].floats <= hi, "%s: %s [%zu, +%zu) outside [%zu, %zu)", what, v[i].name,
+          v[i].off, v[i].floats, lo, hi);
+    for (size_t j = 0; j < i; ++j)
+      CHECK(v[i].off + v[i].floats <= v[j].off || v[j].off + v[j].floats <= v[i].off, "%s: %s overlaps %s", what,
+            v[i].name, v[j].name);
+  }
+}
+
+// one plan against the launch contracts of sedx_internal.h: the extents below
+// are what the kernels write, restated here, not what plan.cpp reserved
+void check_plan(const Model& m, const Tuning& t, int64_t B, int64_t T) {
+  ForwardPlan p;
+  const char* why = plan_forward(m, t, B, T, &p);
+  const int64_t T1 = T / 2, T2 = T1 / 2, T3 = T2 / 2;
+  const bool cf = m.seq == SEQ_CONFORMER;
+  const char* want_why = T3 < 1 ? "input too short" : cf && T3 > 5000 ? "the Conformer encoder holds 5000" : B * T > INT32_MAX / 64 ? "batch too large" : nullptr;
+  CHECK((why == nullptr) == (want_why == nullptr), "B %lld T %lld: %s", (long long)B, (long long)T, why ? why : "accepted");
+  if (why) CHECK(std::strstr(why, want_why) != nullptr, "B %lld T %lld: reason '%s'", (long long)B, (long long)T, why);
+  CHECK(p.g.T == T && p.g.T1 == T1 && p.g.T2 == T2 && p.g.T3 == T3 && p.B == B && p.M == (int)(B * T3), "geometry");
+  // the block-1 form, the layout flag and the family for (precision, SEDX_TUNE_WINO_BLOCK1, SEDX_TUNE_WINO_F43)
+  static const Block1Form wino_form[3][3] = {{B1_PAD_EXACT, B1_PAD_EXACT, B1_PAD_EXACT},
+                                            {B1_CONV1_F23, B1_CONV1_F23, B1_CONV1_F43},
+                                            {B1_F23_FUSED, B1_F23_FUSED, B1_CONV1C4_F43}};
+  static const bool wino_c4[3][3] = {{false, false, false}, {false, false, false}, {false, true, true}};
+  static const ConvFamily wino_family[3] = {CONV_WINO, CONV_WINO43, CONV_WINO43};
+  const bool wino = t.precision == SEDX_PRECISION_WINOGRAD, x3 = t.precision == SEDX_PRECISION_X3;
+  const Block1Form form = wino ? wino_form[t.wino_block1][t.wino_f43] : x3 ? B1_PAD_X3 : B1_PAD_EXACT;
+  const ConvFamily family = wino ? wino_family[t.wino_f43] : x3 ? CONV_X3 : CONV_EXACT;
+  CHECK(p.block1 == form && p.c4 == (wino && wino_c4[t.wino_block1][t.wino_f43]) && p.family == family,
+        "precision %d block1 %d f43 %d: form %d c4 %d family %d", t.precision, t.wino_block1, t.wino_f43, p.block1, p.c4, p.family);
+  CHECK(p.claims == (x3 || (family == CONV_WINO43 && B >= 8)), "claims at B %lld", (long long)B);
+  // top level: disjoint, aligned, inside the byte count
+  const size_t total = p.total_bytes / 4;
+  CHECK(p.total_bytes % 256 == 0, "total");
+  check_spans({span("x0", p.x0), span("A", p.A), span("P", p.P), span("sched", p.sched)}, 0, total, "workspace");
+  // what the launches write
+  const size_t uB = (size_t)B, M = uB * T3, nac = (size_t)m.nac;
+  CHECK(p.x0.floats >= uB * T * 64, "x0");                                   // launch_logmel / launch_features_bn0
+  CHECK(p.sched.floats >= 7 * 256, "sched");                                 // 7 launches x CONV_SCHED_INTS
+  const size_t first = form == B1_F23_FUSED ? 0 : form == B1_PAD_EXACT || form == B1_PAD_X3 ? uB * (T + 2) * 66 : uB * T * 64 * 64;
+  CHECK(first <= p.A.floats, "block 1's first launch: %zu floats into A of %zu", first, p.A.floats);
+  struct Row { int64_t T; int F, cin, cout, epi; };
+  const Row rows[7] = {{T, 64, 64, 64, EPI_POOL2},    {T1, 32, 64, 128, EPI_STORE},  {T1, 32, 128, 128, EPI_POOL2},
+                       {T2, 16, 128, 256, EPI_STORE}, {T2, 16, 256, 256, EPI_POOL2}, {T3, 8, 256, 512, EPI_STORE},
+                       {T3, 8, 512, 512, EPI_FMEAN}};
+  for (int i = 0; i < 7; ++i) {
+    const ConvLayer& c = p.layers[i];
+    const Row& r = rows[i];
+    CHECK(c.T == r.T && c.F == r.F && c.cin == r.cin && c.cout == r.cout && c.epi == r.epi, "layer %d", i);
+    const Region& out = i % 2 ? p.A : p.P;
+    CHECK(c.out == out.off && c.in == (i % 2 ? p.P.off : i == 0 && form == B1_F23_FUSED ? p.x0.off : p.A.off), "layer %d buffers", i);
+    const int64_t To = r.epi == EPI_POOL2 ? r.T / 2 : r.T, Fo = r.epi == EPI_POOL2 ? r.F / 2 : r.epi == EPI_FMEAN ? 1 : r.F;
+    CHECK(c.To == To && c.Fo == Fo, "layer %d output %d x %d", i, c.To, c.Fo);
+    const size_t ext = uB * To * Fo * r.cout;   // [B][To][Fo][Cout]; EPI_FMEAN: [B][T][Cout]
+    CHECK(ext <= out.floats, "layer %d writes %zu floats into %zu", i, ext, out.floats);
+  }
+  // after the conv stack, inside A (P still holds the stage-8 output)
+  const size_t a0 = p.A.off, a1 = p.A.off + p.A.floats;
+  if (cf) {
+    check_spans({span("X", p.X), span("Xn", p.Xn), span("Hb", p.Hb), span("AV", p.AV), span("Rr", p.Rr), span("RK", p.RK),
+                 span("LG", p.LG)}, a0, a1, "Conformer scratch");
+    CHECK(p.X.floats >= M * 144 && p.Xn.floats >= M * 144 && p.AV.floats >= M * 144, "encoder activations");
+    CHECK(p.Hb.floats >= M * 576, "hidden: the widest of ffn 576, qkv 432, pw1 288");
+    CHECK(p.Rr.floats >= (size_t)3 * T3 * 144 && p.RK.floats >= (size_t)3 * T3 * 144, "r, r_k");
+  } else {
+    check_spans({span("G", p.G), span("Hs", p.Hs), span("O", p.O), span("LG", p.LG), span("gru", p.gru)}, a0, a1, "head scratch");
+    CHECK(p.G.floats >= M * 1536 && p.Hs.floats >= M * 512 && p.O.floats >= M * 512, "G, H, O");
+    // gru.hip: the sync block rounded up to 256 B (10,056 -> 10,240), then 8 x 2 x 32 x 256 floats
+    CHECK(p.gru.floats * 4 >= 10240 + (size_t)8 * 2 * 32 * 256 * 4, "recurrence scratch");
+  }
+  CHECK(p.LG.floats >= M * nac, "logits");
+  // launch_gru_coop's arguments
+  static const int variant[8] = {2, -1, 0, 1, 3, 3, 4, 5};   // COOP, SIMPLE, TAG16, TAG8, COOP16, AUTO, KSPLIT, PAIR
+  static const bool fast[4] = {true, false, false, true};    // AUTO, GLOBAL, SPREAD, LOCAL
+  const bool spread = t.gru_handoff == SEDX_GRU_HANDOFF_SPREAD || (t.gru_handoff == SEDX_GRU_HANDOFF_AUTO && t.pipelined);
+  CHECK(p.gru_variant == variant[t.gru_kernel] && p.gru_fast == fast[t.gru_handoff] && p.gru_spread == spread,
+        "gru kernel %d handoff %d pipelined %d: variant %d fast %d spread %d", t.gru_kernel, t.gru_handoff, t.pipelined,
+        p.gru_variant, p.gru_fast, p.gru_spread);
+}
+
+// the windowed drivers' device area for tests/test_host_cpu.py's DRIVER_CASES
+// (false: utilities.merge itself raises on the spec's windows, as numpy does)
+bool check_window_plan(const Model& m, const Tuning& t, int driver, bool overlap, int sd, double ov, double secs, int64_t n_clips) {
+  sedx_window_spec spec{};
+  spec.driver = driver;
+  spec.overlap = overlap;
+  spec.sample_duration = sd;
+  spec.overlap_value = ov;
+  WinGeom wg;
+  const char* why = window_geometry(m, (int64_t)std::llround(secs * 16000), &spec, true, &wg);
+  if (why && std::strncmp(why, "merge: operands could not be broadcast", 38) == 0) return false;
+  CHECK(!why, "window spec sd %d ov %g %g s: %s", sd, ov, secs, why);
+  const WinLayout l = win_layout(m, t, n_clips, wg);
+  CHECK(l.fw_off.size() == wg.groups.size() && l.clip_off.size() == wg.groups.size() && !wg.groups.empty(), "groups");
+  const size_t C = m.cfg.classes_num;
+  std::vector<Span> area;
+  int n_win = 0;
+  for (size_t g = 0; g < wg.groups.size(); ++g) {
+    const size_t items = (size_t)n_clips * wg.groups[g].nw;
+    ForwardPlan p;
+    CHECK(!plan_forward(m, t, (int64_t)items, wg.groups[g].g.T, &p) && p.total_bytes <= l.model_bytes, "group %zu's plan", g);
+    area.push_back(Span{"framewise", l.fw_off[g], items * (size_t)wg.groups[g].g.out_frames * C});   // att / fc head
+    area.push_back(Span{"clipwise", l.clip_off[g], items * C});
+    n_win += wg.groups[g].nw;
+  }
+  CHECK(n_win == wg.n_win, "windows in groups");
+  area.push_back(Span{"vote thresholds", l.vthr, 2 * C});                                            // [C] f64
+  area.push_back(Span{"tables", l.tables, l.table_bytes / 4});
+  CHECK(l.total_bytes % 256 == 0 && l.table_bytes % 256 == 0, "window totals");
+  check_spans(area, l.model_bytes / 4, l.total_bytes / 4, "window area");
+  // the tables, in floats of the table block: starts, bases, strides [n_win] i64; off [N + 1] i32; src int2; div [N] i32
+  const size_t N = (size_t)wg.plan.N;
+  check_spans({Span{"start", l.t_start / 4, 2 * (size_t)n_win}, Span{"wb", l.t_wb / 4, 2 * (size_t)n_win},
+               Span{"wcs", l.t_wcs / 4, 2 * (size_t)n_win}, Span{"off", l.t_off / 4, N + 1},
+               Span{"src", l.t_src / 4, 2 * wg.plan.src.size()}, Span{"div", l.t_div / 4, N}},
+              0, l.table_bytes / 4, "window tables");
+  for (size_t b : {l.t_start, l.t_wb, l.t_wcs, l.t_off, l.t_src, l.t_div}) CHECK(b % 256 == 0, "table offset %zu", b);
+  return true;
+}
+
+int check_plans() {
+  int n = 0;
+  for (int model_type = 0; model_type <= 8; ++model_type) {
+    const Model m = model_of(model_type, 25, 512, SEDX_FEATURE_LOGMEL);
+    Tuning t;
+    for (t.precision = 0; t.precision < 3; ++t.precision)
+      for (t.wino_block1 = 0; t.wino_block1 < 3; ++t.wino_block1)
+        for (t.wino_f43 = 0; t.wino_f43 < 3; ++t.wino_f43)
+          for (int pipe = 0; pipe < 2; ++pipe)
+            for (int64_t B : {1, 7, 8, 32, 530})
+              for (int64_t T : {8, 9, 34, 64, 734, 1001, 6131}) {
+                t.pipelined = pipe != 0;
+                check_plan(m, t, B, T), ++n;
+              }
+  }
+  const Model gru = model_of(SEDX_MODEL_GRU_FRAMEATT, 25, 512, SEDX_FEATURE_LOGMEL);
+  for (int kernel = 0; kernel < 8; ++kernel)
+    for (int handoff = 0; handoff < 4; ++handoff)
+      for (int pipe = 0; pipe < 2; ++pipe) {
+        Tuning t;
+        t.gru_kernel = kernel;
+        t.gru_handoff = handoff;
+        t.pipelined = pipe != 0;
+        check_plan(gru, t, 32, 1001), ++n;
+      }
+  // rejections: no frame left after the third pool; a sequence past the
+  // Conformer's positional table; item counts past the launches' 32-bit sizes
+  const Model cf = model_of(SEDX_MODEL_CONFORMER_FRAMEATT, 25, 512, SEDX_FEATURE_LOGMEL);
+  check_plan(gru, Tuning(), 1, 7), ++n;
+  check_plan(cf, Tuning(), 1, 8 * 5001), ++n;
+  check_plan(cf, Tuning(), 1, 8 * 5000), ++n;
+  check_plan(gru, Tuning(), 530, 63310), ++n;      // 530 x 63,310 > INT32_MAX / 64 = 33,554,431
+  check_plan(gru, Tuning(), 530, 63309), ++n;      // the largest that fits
+  struct Case { int driver; bool overlap; int sd; double ov, secs; };
+  const Case cases[15] = {{0, true, 5, 1.0, 10.0}, {0, true, 5, 0.5, 23.0}, {0, false, 5, 1.0, 23.0}, {0, false, 5, 0.7, 17.3},
+                          {0, true, 6, 0.5, 71.3}, {0, true, 5, 1.0, 187.37}, {0, true, 5, 1.0, 3.2}, {1, true, 5, 0.7, 10.0},
+                          {1, true, 6, 0.9, 10.0}, {1, true, 7, 1.3, 10.0}, {1, true, 5, 0.1, 10.0}, {1, true, 5, 0.3, 9.9},
+                          {1, true, 5, 1.0, 12.3}, {1, true, 6, 0.5, 8.7}, {1, true, 7, 0.9, 14.1}};
+  for (const Case& c : cases)
+    for (int64_t n_clips : {1, 3})
+      for (const Model* m : {&gru, &cf}) {
+        const bool planned = check_window_plan(*m, Tuning(), c.driver, c.overlap, c.sd, c.ov, c.secs, n_clips);
+        // 7 s windows every 0.9 s over 14.1 s: the one case whose averaged merge numpy refuses
+        CHECK(planned || (c.sd == 7 && c.secs == 14.1), "window case sd %d ov %g %g s: the merge raises", c.sd, c.ov, c.secs);
+        n += planned;
+      }
+  return n;
+}
 }  // namespace
 
 int main() {
@@ -594,7 +778,8 @@ int main() {
     }
   }
   const int weight_checks = check_weights();
-  std::printf("asan_driver: %d wav_parse cases (%d accepted), %d vad cases, %d weight-pack checks: clean\n", cases,
-              ok, vad_cases, weight_checks);
+  const int plan_checks = check_plans();
+  std::printf("asan_driver: %d wav_parse cases (%d accepted), %d vad cases, %d weight-pack checks, %d plan checks: "
+              "clean\n", cases, ok, vad_cases, weight_checks, plan_checks);
   return 0;
 }

@@ -885,6 +885,114 @@ def test_wino43_item_claims_dirty_workspace_and_regimes():
         assert torch.equal(fw, ref)
 
 
+GUARD = 64 << 10
+
+
+def _guarded(nbytes, device):
+    """nbytes of workspace between two 64 KiB guards, every byte 0xA5."""
+    buf = torch.full((GUARD + nbytes + GUARD,), 0xA5, dtype=torch.uint8, device=device)
+    return buf, buf[GUARD:GUARD + nbytes]
+
+
+def _guards_intact(buf):
+    return bool((buf[:GUARD] == 0xA5).all()) and bool((buf[-GUARD:] == 0xA5).all())
+
+
+def _forward_in(m, wave, ws, ws_bytes):
+    """sedx_forward on ``ws`` (None: the handle's own workspace): (status, framewise, clipwise, embedding)."""
+    import ctypes
+    from sedx import _lib
+    from sedx.models import _ptr
+    nat = m.native(wave.device)
+    L = _lib.lib()
+    B, length = wave.shape
+    fr, sl = ctypes.c_int64(), ctypes.c_int64()
+    _lib.check(L.sedx_output_geometry(nat.h, length, ctypes.byref(fr), ctypes.byref(sl)), nat.h, 'geometry')
+    C = m.classes_num
+    outs = [torch.full(shape, float('nan'), dtype=torch.float32, device=wave.device)
+            for shape in ((B, fr.value, C), (B, C), (B, C if m._embedding_cla else m._embedding_width, sl.value))]
+    stream = ctypes.c_void_p(torch.cuda.current_stream(wave.device).cuda_stream)
+    st = L.sedx_forward(nat.h, _ptr(wave), B, length, _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _ptr(ws),
+                        ws_bytes, stream)
+    torch.cuda.synchronize()
+    return [st] + outs
+
+
+def test_forward_stays_inside_its_workspace():
+    """A forward on a caller's workspace of exactly sedx_workspace_size bytes
+    writes nothing outside it (64 KiB guards of 0xA5 on both sides stay as
+    they are) and gives the outputs of the same forward on the handle's own
+    workspace bit for bit; one byte less is SEDX_EINVAL with nothing
+    launched.  Shapes: 1 x 0.33 s (the sequence scratch decides the larger
+    activation buffer), 3 x 7.33 s (the conv activations do; odd frame
+    count), 9 x 1 s (claim counters in use).  Forms: the GRU model in exact,
+    x3 and Winograd with every (SEDX_TUNE_WINO_BLOCK1, SEDX_TUNE_WINO_F43)
+    pair; the Transformer, Cnn_9layers_FrameMax and
+    Cnn_9layers_Conformer_FrameAtt models in the default form; one windowed
+    forward (2 clips x 10 s, 5 s windows every 1.0 s)."""
+    import ctypes
+    from sedx import _lib, models
+    from sedx.models import _ptr
+    L = _lib.lib()
+    dev = torch.device('cuda', 0)
+
+    def other(mt, seed):
+        m = getattr(models, mt)(*P16, 25)
+        sd = m.state_dict()
+        for k, v in synth.make_state_dict(mt, seed=seed).items():
+            sd[k] = torch.from_numpy(v)
+        m.load_state_dict(sd, strict=True)
+        return m.to('cuda').eval()
+
+    gru = build(GRU)
+    forms = [(gru, 'exact', 2, 2), (gru, 'x3', 2, 2)] + [(gru, 'winograd', b1, f43) for b1 in (0, 1, 2) for f43 in (0, 1, 2)]
+    forms += [(build(TRF), 'winograd', 2, 2),
+              (other('Cnn_9layers_FrameMax', synth.GOLDEN_SEEDS['Cnn_9layers_FrameMax']), 'winograd', 2, 2),
+              (other('Cnn_9layers_Conformer_FrameAtt', synth.CONFORMER_GOLDEN_SEEDS['Cnn_9layers_Conformer_FrameAtt']),
+               'winograd', 2, 2)]
+    waves = [torch.from_numpy(synth.make_waveforms(B, seconds=secs, sample_rate=16000, seed=60 + B)).cuda()
+             for B, secs in ((1, 0.33), (3, 7.33), (9, 1.0))]
+    for m, prec, b1, f43 in forms:
+        m.set_precision(prec).set_tuning(_lib.TUNE_WINO_BLOCK1, b1).set_tuning(_lib.TUNE_WINO_F43, f43)
+        nat = m.native(dev)
+        for wave in waves:
+            what = (type(m).__name__, prec, b1, f43, tuple(wave.shape))
+            ref = _forward_in(m, wave, None, 0)
+            assert ref[0] == 0 and all(torch.isfinite(t).all() for t in ref[1:]), what
+            wsz = ctypes.c_size_t()
+            _lib.check(L.sedx_workspace_size(nat.h, wave.shape[0], wave.shape[1], ctypes.byref(wsz)), nat.h, 'size')
+            buf, ws = _guarded(wsz.value, dev)
+            short = _forward_in(m, wave, ws, wsz.value - 1)
+            assert short[0] == 1 and all(torch.isnan(t).all() for t in short[1:]), what      # SEDX_EINVAL, no launch
+            assert bool((buf == 0xA5).all()), what
+            got = _forward_in(m, wave, ws, wsz.value)
+            assert got[0] == 0, what
+            assert _guards_intact(buf), what
+            for a, b in zip(got[1:], ref[1:]):
+                assert torch.equal(a, b), what
+    gru.set_precision('winograd').set_tuning(_lib.TUNE_WINO_BLOCK1, 2).set_tuning(_lib.TUNE_WINO_F43, 2)
+    # the windowed driver: the model workspace, then the per-window outputs and the tables
+    nat = gru.native(dev)
+    audio = torch.from_numpy(synth.make_waveforms(2, seconds=10.0, sample_rate=16000, seed=71)).cuda()
+    spec = _lib.window_spec(5, 1.0)
+    nf, wsz = ctypes.c_int64(), ctypes.c_size_t()
+    _lib.check(L.sedx_window_geometry(nat.h, audio.shape[1], ctypes.byref(spec), None, None, ctypes.byref(nf)), nat.h,
+               'window_geometry')
+    _lib.check(L.sedx_window_workspace_size(nat.h, 2, audio.shape[1], ctypes.byref(spec), ctypes.byref(wsz)), nat.h,
+               'window_workspace_size')
+    buf, ws = _guarded(wsz.value, dev)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    merged = []
+    for w, nbytes in ((None, 0), (ws, wsz.value)):
+        out = torch.full((2, nf.value, 25), float('nan'), dtype=torch.float32, device=dev)
+        _lib.check(L.sedx_forward_windows(nat.h, _ptr(audio), 2, audio.shape[1], ctypes.byref(spec), _ptr(out), _ptr(w),
+                                          nbytes, stream), nat.h, 'forward_windows')
+        torch.cuda.synchronize()
+        merged.append(out)
+    assert _guards_intact(buf)
+    assert torch.isfinite(merged[0]).all() and torch.equal(merged[0], merged[1])
+
+
 def test_wino_block1_knob_errors():
     """A bad value for the knob is a loud error, not a silent fallback."""
     from sedx import _lib

@@ -193,6 +193,64 @@ def test_native_merge_float_overlap_steps():
         assert got.shape[1] == 500 + 2 * step
 
 
+def _create_handle(L, model_type):
+    import ctypes
+    from sedx import _lib
+    cfg = _lib.SedxConfig(model_type, 0, 16000, 512, 160, 64, 50.0, 7000.0, 25)
+    h = ctypes.c_void_p()
+    assert L.sedx_create(ctypes.byref(cfg), 0, ctypes.byref(h)) == 0
+    return h
+
+
+def test_workspace_sizes_against_the_recorded_grid(golden_dir):
+    """sedx_workspace_size, sedx_output_geometry and sedx_window_workspace_size
+    (no GPU) over the grid tools/make_golden_workspace.py recorded from the
+    library before the forward plan: 9 models x 3 precisions x
+    SEDX_TUNE_WINO_BLOCK1 x SEDX_TUNE_WINO_F43 x 5 (clips, samples), and one
+    window spec per model.  The geometry is equal.  A size may not grow, and
+    may be smaller only by the hand-counted slack the plan's carve removed
+    (at most (4 * 64 + 64) * 4 = 1,280 B of head scratch or 8 * 64 * 4 =
+    2,048 B of Conformer scratch): it lies in [recorded - 4096, recorded]."""
+    import ctypes
+    from sedx import _lib
+    g = json.load(open(os.path.join(golden_dir, 'workspace_sizes.json')))
+    assert len(g['rows']) == 9 * 3 * 3 * 3 * 5 and len(g['window_bytes']) == 9
+    L = _lib.lib()
+    handles = {}
+    for mt, prec, b1, f43, B, n, want, frames, seq in g['rows']:
+        h = handles.get(mt) or handles.setdefault(mt, _create_handle(L, mt))
+        assert L.sedx_set_precision(h, prec) == 0
+        assert L.sedx_set_tuning(h, _lib.TUNE_WINO_BLOCK1, b1) == 0 and L.sedx_set_tuning(h, _lib.TUNE_WINO_F43, f43) == 0
+        wsz, fr, sl = ctypes.c_size_t(), ctypes.c_int64(), ctypes.c_int64()
+        assert L.sedx_workspace_size(h, B, n, ctypes.byref(wsz)) == 0
+        assert L.sedx_output_geometry(h, n, ctypes.byref(fr), ctypes.byref(sl)) == 0
+        assert (fr.value, sl.value) == (frames, seq), (mt, n)
+        assert want - 4096 <= wsz.value <= want, (mt, prec, b1, f43, B, n, wsz.value, want)
+    w = g['window']
+    spec = _lib.window_spec(w['sample_duration'], w['overlap_value'])
+    for mt, want in enumerate(g['window_bytes']):
+        h = _create_handle(L, mt)                     # default tuning, as recorded
+        wsz = ctypes.c_size_t()
+        assert L.sedx_window_workspace_size(h, w['n_clips'], w['samples'], ctypes.byref(spec), ctypes.byref(wsz)) == 0
+        assert want - 4096 <= wsz.value <= want, (mt, wsz.value, want)
+        L.sedx_destroy(h)
+    for h in handles.values():
+        L.sedx_destroy(h)
+
+
+def test_invalid_setter_values_are_einval_before_any_device_call():
+    """sedx_set_pipelined / sedx_set_profiling range-check `on` before they
+    touch HIP: without a GPU an invalid value is SEDX_EINVAL (1), not the
+    SEDX_EHIP (3) of a failed event creation."""
+    from sedx import _lib
+    L = _lib.lib()
+    h = _create_handle(L, 0)
+    assert L.sedx_set_pipelined(h, 3) == 1 and L.sedx_set_pipelined(h, -1) == 1
+    assert L.sedx_set_profiling(h, 3) == 1 and L.sedx_set_profiling(h, -1) == 1
+    assert L.sedx_set_pipelined(h, 0) == 0 and L.sedx_set_profiling(h, 0) == 0
+    L.sedx_destroy(h)
+
+
 def test_no_packed_fp32_in_any_kernel():
     """Every kernel's gfx950 ISA is free of packed FP32 VALU (v_pk_add/mul/
     fma_f32): measured on MI355X, packed FP32 beside MFMA waves on the same
