@@ -131,6 +131,35 @@ sedx_status sedx_output_geometry(const sedx_handle* h, int64_t L_or_T, int64_t* 
 /* Bytes of device workspace sedx_forward* needs for (B, L). */
 sedx_status sedx_workspace_size(const sedx_handle* h, int64_t B, int64_t L_or_T, size_t* bytes);
 
+/* The conv launches of stages 2-8 of a forward of (B, L) at the handle's
+ * current precision and tuning, as the launchers decide them (read-only; no
+ * launch, no output depends on any of it).  One row per launch: a batch whose
+ * input passes the kernels' 32-bit offsets runs a stage as several launches of
+ * whole clips.  Rows of the exact and x3 launchers carry the layer only (the
+ * fields from `clips` on are 0). */
+typedef enum sedx_conv_family {
+  SEDX_CONV_EXACT = 0,
+  SEDX_CONV_X3 = 1,
+  SEDX_CONV_F23 = 2,         /* Winograd F(2x2,3x3) */
+  SEDX_CONV_F23_BLOCK1 = 3,  /* block 1 in one F(2x2,3x3) launch (conv1 inside) */
+  SEDX_CONV_F43 = 4          /* Winograd F(4x4,3x3) */
+} sedx_conv_family;
+typedef struct sedx_conv_launch {
+  int32_t stage, family;              /* 2..8 (sedx_stage_times' numbering), sedx_conv_family */
+  int32_t T, F, cin, cout, epi;       /* the layer: rows, columns, channels; 0 store, 1 2x2 pool, 2 freq mean */
+  int32_t clips;                      /* clips of this launch */
+  int32_t tg, nt, c4;                 /* item: tile groups, channel tiles; chunk-of-4 layout */
+  int32_t tb_per_clip, ngroups;       /* tile blocks per clip, channel groups */
+  int32_t nitems, nwg;                /* items, persistent workgroups */
+  int32_t claim, order2d;             /* items claimed from counters; channel groups per L2 round (0, -1: see DESIGN.md) */
+  int64_t clips_per_launch;           /* most clips one launch takes */
+} sedx_conv_launch;
+/* ncu > 0: the answer for a device of that many CUs, touching no device;
+ * ncu <= 0: the handle's device.  *n_rows = rows of the answer; SEDX_EINVAL
+ * if capacity is smaller or the forward refuses the shape. */
+sedx_status sedx_conv_launch_plan(const sedx_handle* h, int64_t B, int64_t L_or_T, int32_t ncu,
+                                  sedx_conv_launch* rows, int32_t capacity, int32_t* n_rows);
+
 /* Model forward (eval mode): replaces Cnn_9layers_*_FrameAtt.forward(input)
  * (pytorch/models.py:625-688, :1029-1077).
  *   d_wave       [B, L]                         (logmel models)

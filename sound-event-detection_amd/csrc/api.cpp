@@ -303,23 +303,21 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
     // block 1 as one launch: conv1 computed inside conv2's halo staging (the
     // b1c1 stage is just the zero-bordered copy of the bn0 output), or conv2
     // on conv1's activation
-    const Block1Form b1 = p.block1;
-    if (i == 0 && b1 == B1_PAD_X3)
-      launch_block1_fused_x3(nullptr, iB, c.T, in, w.c1_wt, w.c1_b, w.wx3[k], w.cb[k], out, claim, s);
-    else if (i == 0 && b1 == B1_F23_FUSED)
+    WinoFamily wf;
+    const bool wino = conv_launch_family(p, i, &wf);   // sedx_conv_launch_plan answers by the same call
+    if (wino && wf == WINO_F23_BLOCK1)
       launch_block1_wino(in, iB, c.T, w.c1_w, w.c1_b, w.wu[k], w.cb[k], out, w.zero, w.trash, s, p.c4);
-    else if (i == 0 && b1 == B1_CONV1_F23)
-      launch_conv3x3_wino(in, iB, c.T, c.F, c.cin, c.cout, w.wu[k], w.cb[k], out, c.epi, w.zero, w.trash, s);
-    else if (i == 0 && b1 == B1_PAD_EXACT)
+    else if (wino && wf == WINO_F23)
+      launch_conv3x3_wino(in, iB, c.T, c.F, c.cin, c.cout, w.wu[k], w.cb[k], out, c.epi, w.zero, w.trash, s, c.order);
+    else if (wino)   // in block 1 on conv1's activation (B1_CONV1_F43, B1_CONV1C4_F43)
+      launch_conv3x3_wino43(in, iB, c.T, c.F, c.cin, c.cout, w.wu43[k], w.cb[k], out, c.epi, w.trash, s, c.order,
+                            p.c4, 0, claim);
+    else if (i == 0 && p.block1 == B1_PAD_X3)
+      launch_block1_fused_x3(nullptr, iB, c.T, in, w.c1_wt, w.c1_b, w.wx3[k], w.cb[k], out, claim, s);
+    else if (i == 0)   // B1_PAD_EXACT
       launch_block1_exact(in, iB, c.T, w.c1_w, w.c1_b, w.wp[k], w.cb[k], out, w.zero, s);
-    else if (i == 0 || p.family == CONV_WINO43)   // B1_CONV1_F43, B1_CONV1C4_F43: conv2 on conv1's activation
-      launch_conv3x3_wino43(in, iB, c.T, c.F, c.cin, c.cout, w.wu43[k], w.cb[k], out, c.epi, w.trash, s,
-                            t.wino_order, p.c4, 0, claim);
     else if (p.family == CONV_X3)
       launch_conv3x3_x3(in, iB, c.T, c.F, c.cin, c.cout, w.wx3[k], w.cb[k], out, c.epi, claim, s);
-    else if (p.family == CONV_WINO)
-      launch_conv3x3_wino(in, iB, c.T, c.F, c.cin, c.cout, w.wu[k], w.cb[k], out, c.epi, w.zero, w.trash, s,
-                          t.wino_order);
     else
       launch_conv3x3(in, iB, c.T, c.F, c.cin, c.cout, w.wp[k], w.cb[k], out, c.epi, w.zero, s);
     if (p.c4 && c.epi != EPI_FMEAN)
@@ -656,6 +654,51 @@ sedx_status sedx_workspace_size(const sedx_handle* h, int64_t B, int64_t L_or_T,
   ForwardPlan p;
   plan_forward(*h, h->tune, B, g.T, &p);   // the size of a shape no forward runs is still answered
   *bytes = p.total_bytes;
+  return SEDX_OK;
+}
+
+sedx_status sedx_conv_launch_plan(const sedx_handle* h, int64_t B, int64_t L_or_T, int32_t ncu,
+                                  sedx_conv_launch* rows, int32_t capacity, int32_t* n_rows) {
+  if (!h || !n_rows || B <= 0 || capacity < 0 || (capacity && !rows)) return SEDX_EINVAL;
+  *n_rows = 0;
+  Geometry g;
+  if (sedx_status st = query_geometry(h, L_or_T, &g)) return st;
+  ForwardPlan p;
+  if (const char* why = plan_forward(*h, h->tune, B, g.T, &p)) return fail(h, SEDX_EINVAL, "%s", why);
+  if (ncu <= 0) {
+    DeviceGuard dg(h->device);
+    ncu = device_cus();
+  }
+  int n = 0;
+  for (int i = 0; i < 7; ++i) {
+    const ConvLayer& c = p.layers[i];
+    sedx_conv_launch r{};
+    r.stage = 2 + i;
+    r.family = p.family == CONV_X3 ? SEDX_CONV_X3 : SEDX_CONV_EXACT;
+    r.T = c.T, r.F = c.F, r.cin = c.cin, r.cout = c.cout, r.epi = c.epi;
+    WinoFamily wf;
+    const bool wino = conv_launch_family(p, i, &wf);
+    // run_body's arguments: the F(2x2) launchers take no layout flag and no counters
+    const bool c4 = p.c4 && (!wino || wf != WINO_F23);
+    int64_t b0 = 0;
+    do {   // the launchers' loop over whole clips
+      if (wino) {
+        const ConvLaunch l = plan_conv_launch(wf, ncu, B - b0, c.T, c.F, c.cin, c.cout, c.epi, c.order, c4, 0,
+                                              p.claims && wf == WINO_F43);
+        if (l.reject) return fail(h, SEDX_EINVAL, "stage %d: %s", r.stage, l.reject);
+        r.family = wf;
+        r.clips = l.clips, r.tg = l.TG, r.nt = l.NT, r.c4 = c4;
+        r.tb_per_clip = l.tb_per_clip, r.ngroups = l.ngroups, r.nitems = l.nitems, r.nwg = l.nwg;
+        r.claim = l.claim, r.order2d = l.order2d;
+        r.clips_per_launch = l.clips_per_launch;
+      }
+      if (n < capacity) rows[n] = r;
+      ++n;
+      b0 += wino ? r.clips : B;
+    } while (b0 < B);
+  }
+  *n_rows = n;
+  if (n > capacity) return fail(h, SEDX_EINVAL, "%d conv launches: capacity %d", n, capacity);
   return SEDX_OK;
 }
 

@@ -534,12 +534,6 @@ static void launch_f_bn_w(const float* in, int B, int T, int Cin, int Cout, cons
   note_launch_error(hipErrorInvalidValue);
 }
 
-static int device_cus() {
-  int dev = 0, ncu = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  return ncu;
-}
-
 // Shape by grid size: 8-wave 64x64 wave tiles when they make at least two
 // workgroups per CU of the chip; 4-wave ones likewise (one workgroup per CU
 // and a half-empty second round measured slower than the small shapes);

@@ -45,67 +45,12 @@
 #include <type_traits>
 
 #include "sedx_internal.h"
+#include "wino_geom.h"   // WinoGeom: the workgroup's tiles, channels and LDS layout
 
 namespace sedx {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4w __attribute__((ext_vector_type(4)));
-
-// TG tile groups (32 tiles each) x 32 NT channels per workgroup, 4 TG waves.
-// C1 (block 1, F = 64): the input is the bn0 output X0 [B][T][64] and conv1
-// (Cin 1 -> 64, BN folded, ReLU) is computed into each chunk's halo image in
-// LDS (below): conv1's 64-channel activation never exists in HBM.
-template <int F, int TG, int NT = 2, bool C1 = false>
-struct WinoGeom {
-  static constexpr int WAVES = 4 * TG;               // row waves 0..3 of each tile group
-  static constexpr int THREADS = 64 * WAVES;
-  static constexpr int NCH = 32 * NT;                // output channels per workgroup
-  static constexpr int P = 32 * TG;                  // tiles per workgroup
-  static constexpr int FT = F / 2;                   // tiles per tile row
-  static constexpr int TRW = P / FT;                 // tile rows per workgroup
-  static constexpr int RT = 2 * TRW + 2, CS = F + 2, KC = 4;
-  static constexpr int PL = RT * CS;                 // halo pixels
-  static constexpr int PLP = (PL + 63) / 64 * 64;    // whole 64-pixel DMA units
-  // floats: [pixel][4 ch] (C1: a 64-pixel conv1 group for every wave; the
-  // groups past the halo write zeros into the padding)
-  static constexpr int A_SZ = KC * (C1 && PLP < 64 * WAVES ? 64 * WAVES : PLP);
-  static constexpr int W_SZ = 16 * KC * NCH;         // floats: [p][h][n NCH][ks]
-  static constexpr int BUF = A_SZ + W_SZ;
-#ifndef SEDX_WINO_NBUF
-#define SEDX_WINO_NBUF 3
-#endif
-  static constexpr int NBUF = SEDX_WINO_NBUF;        // ring depth
-  static constexpr int UW = W_SZ / 256;              // 1-KiB DMA units per chunk
-  static constexpr int UA = C1 ? 0 : PLP / 64;       // halo units (C1 computes the halo instead)
-  static constexpr int U = UW + UA;
-  static constexpr int UPW = (U + WAVES - 1) / WAVES;
-  static constexpr int VM_MIN = U / WAVES;           // units of the wave with the fewest
-  // epilogue exchange, one channel tile per round: per tile group
-  // [finisher row 4][other row 3][register 4][z 2][lane 64] floats
-  static constexpr int XTG = 4 * 3 * 4 * 2 * 64;
-  static constexpr int XCH = TG * XTG;
-  // C1: an item's X0 rows t0 - 2 .. t0 + RT - 1 ([row][F], zero rows outside
-  // the clip), two buffers by item parity, in 1-KiB DMA units; the conv1
-  // halo pixels in 64-pixel groups, one group per wave
-  static constexpr int XROWS = RT + 2;
-  static constexpr int UX = C1 ? (XROWS * F + 255) / 256 : 0;
-  static constexpr int X0_SZ = 256 * UX;
-  static constexpr int XA_OFF = NBUF * BUF + XCH;
-  // the layer's biases (Cout <= 512), LDS-DMA'd once in the prologue: read
-  // from LDS, the epilogue's bias needs no vmcnt wait (which would also wait
-  // for the next item's DMAs in flight)
-  static constexpr int BIAS_OFF = XA_OFF + 2 * X0_SZ, BIAS_MAX = 512;
-  // C1 with conv1 on the matrix pipe: conv1's weights [64 ch][9] (3 DMA
-  // units, zero-padded) and biases (1 unit), LDS-DMA'd in the prologue
-  static constexpr int W1_OFF = BIAS_OFF + BIAS_MAX, W1_SZ = C1 ? 1024 : 0;
-  static constexpr int LDS_BYTES = 4 * (W1_OFF + W1_SZ);   // ring, epilogue exchange, X0 tiles, biases, conv1 weights
-  static constexpr int WG_PER_CU = WAVES == 8 || LDS_BYTES > 80 * 1024 ? 1 : 2;
-  static_assert(NT == 1 || NT == 2, "channel tiles per wave");
-  static_assert(P % FT == 0, "whole tile rows per workgroup");
-  static_assert(VM_MIN * (NBUF - 1) <= 63, "vmcnt field");
-  static_assert(LDS_BYTES <= 160 * 1024, "LDS per workgroup");
-  static_assert(!C1 || (F == 64 && NT == 2 && PLP <= 64 * WAVES && UX <= WAVES && NBUF >= 3), "C1: block 1 (64 bins), a conv1 group per wave");
-};
 
 // Diagnostic builds only (tools/wino_b1_bench.cpp; never
 // the library): SEDX_WINO_STAMPS accumulates per-wave s_memtime intervals by
@@ -858,70 +803,17 @@ __global__ __launch_bounds__(256 * TG, (WinoGeom<64, TG, 2, true>::WG_PER_CU)) v
 #undef SEDX_WINO_ROWS
 #undef SEDX_WINO_ROWS4
 
-static int wino_device_cus() {
-  int dev = 0, ncu = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  return ncu;
-}
-
-#ifndef SEDX_WINO_ITEMS
-#define SEDX_WINO_ITEMS 4
-#endif
-constexpr int WINO_ITEMS = SEDX_WINO_ITEMS;
-// block 1's one-launch kernel: ~8 items per workgroup (isolated 0.731-0.733
-// ms against 0.735-0.744 at 4 and 0.748-0.752 at 2; the two-stream headline
-// the same within noise over four alternating rounds, tools/gpu_ab_iso.sh)
-#ifndef SEDX_WINO_ITEMS_B1
-#define SEDX_WINO_ITEMS_B1 8
-#endif
-constexpr int WINO_ITEMS_B1 = SEDX_WINO_ITEMS_B1;
-
+// one launch of the plan's (plan.cpp, plan_conv_launch) p.clips clips
 template <int F, int TG, int NT>
-static void launch_wino_w(const float* in, int B, int T, int Cin, int Cout, const float* U, const float* bias,
-                          float* out, int epi, const float* zero16, float* trash, int order, hipStream_t s) {
+static void launch_wino_w(const ConvLaunch& p, const float* in, int T, int Cin, int Cout, const float* U,
+                          const float* bias, float* out, int epi, const float* zero16, float* trash, hipStream_t s) {
   using G = WinoGeom<F, TG, NT>;
-  // tile rows of a clip: POOL2 drops an odd last row (floor), the others keep it
-  const int trows = epi == EPI_POOL2 ? T / 2 : (T + 1) / 2;
-  const int tb_per_clip = (trows + G::TRW - 1) / G::TRW;
-  const int ngroups = Cout / G::NCH;
-  const int64_t tblocks = (int64_t)B * tb_per_clip;
-  const int64_t nitems = (tblocks + 7) / 8 * 8 * ngroups;
-  if (nitems > INT32_MAX || tblocks <= 0 || (int64_t)B * T * F * Cin >= INT32_MAX)   // 32-bit DMA offsets
-    return note_launch_error(hipErrorInvalidValue);
-  // persistent workgroups: as many as are resident, a multiple of 8
-  // (XCD-aware item decode); each walks its items with
-  // the next item's first chunks landing during the current one's last
-  // ~WINO_ITEMS items per workgroup, but at least one resident round: the
-  // hardware dispatcher still balances the workgroups over the CUs (a CU
-  // shared with another stream's kernel finishes its workgroups later)
-  const int64_t resident = (int64_t)wino_device_cus() * G::WG_PER_CU / 8 * 8;
-  const int64_t per = (nitems + WINO_ITEMS - 1) / WINO_ITEMS;
-  const int64_t nwg = std::min<int64_t>(nitems, std::max<int64_t>(std::max<int64_t>(8, resident), (per + 7) / 8 * 8));
-  dim3 grid((unsigned)nwg);
-  // rounds of 32 / G tile blocks x G channel groups: the G (< ngroups,
-  // dividing it) whose round streams the fewest bytes through the XCD's L2 —
-  // G weight slabs (16 Cin NCH floats each) + 32 / G halos (PL Cin floats) —
-  // with whole rounds of tile blocks per XCD, no padding, and a grid of whole
-  // 32-item rounds per XCD (a workgroup keeps its slot in the round from item
-  // to item).  (b4c2: 4 slabs of 2 MB + 8 halos of 0.7 MB instead of 8 + 4.)
-  int order2d = 0;
-  if (order && nwg % 256 == 0 && (nitems / 8) % 32 == 0) {
-    const int64_t slab = (int64_t)16 * Cin * G::NCH * 4, halo = (int64_t)G::PL * Cin * 4;
-    int64_t best = (int64_t)ngroups * slab + (32 / std::min(ngroups, 32)) * halo;   // the default order
-    for (int gr = 1; gr <= 8 && gr < ngroups; gr *= 2) {
-      const int64_t bytes = gr * slab + (32 / gr) * halo;
-      if (ngroups % gr == 0 && tblocks % (8 * (32 / gr)) == 0 && bytes < best) {
-        best = bytes;
-        order2d = gr;
-      }
-    }
-  }
 #define SEDX_WG_LAUNCH(E)                                                                              \
   {                                                                                                    \
     auto* k_ = conv3x3_wino_kernel<F, E, TG, NT>;                                                      \
     if (!launch_info(reinterpret_cast<const void*>(k_), G::THREADS, G::LDS_BYTES).ok) return;          \
-    hipLaunchKernelGGL(k_, grid, dim3(G::THREADS), G::LDS_BYTES, s, in, B, T, Cin, Cout, U, bias, out, zero16, \
-                       trash, tb_per_clip, ngroups, order2d);                                          \
+    hipLaunchKernelGGL(k_, dim3((unsigned)p.nwg), dim3(G::THREADS), G::LDS_BYTES, s, in, p.clips, T, Cin, Cout, U, \
+                       bias, out, zero16, trash, p.tb_per_clip, p.ngroups, p.order2d);                 \
     return;                                                                                            \
   }
   if constexpr (F == 8) {
@@ -935,95 +827,52 @@ static void launch_wino_w(const float* in, int B, int T, int Cin, int Cout, cons
   note_launch_error(hipErrorInvalidValue);
 }
 
-
-// 2 tile groups x 64 channels (8 waves) when that gives every CU a
-// workgroup, else 1 x 64, else 1 x 32: the same per-(tile, channel) work,
-// bit-identical outputs
+// the plan's item shape: TG tile groups x 32 NT channels
 template <int F>
-static void launch_wino_f(const float* in, int B, int T, int Cin, int Cout, const float* U, const float* bias,
-                          float* out, int epi, const float* zero16, float* trash, int order, hipStream_t s) {
-  const int64_t ncu = wino_device_cus();
-  const int trows = epi == EPI_POOL2 ? T / 2 : (T + 1) / 2;
-  auto wgs = [&](int trw, int nch) { return (int64_t)B * ((trows + trw - 1) / trw) * (Cout / nch); };
+static void launch_wino_f(const ConvLaunch& p, const float* in, int T, int Cin, int Cout, const float* U,
+                          const float* bias, float* out, int epi, const float* zero16, float* trash, hipStream_t s) {
 #ifdef SEDX_WINO_TG3
-  if (wgs(WinoGeom<F, 3, 1>::TRW, 32) >= ncu)
-    launch_wino_w<F, 3, 1>(in, B, T, Cin, Cout, U, bias, out, epi, zero16, trash, order, s);
-  else
+  if (p.TG == 3) return launch_wino_w<F, 3, 1>(p, in, T, Cin, Cout, U, bias, out, epi, zero16, trash, s);
 #endif
 #ifdef SEDX_WINO_TG4
-  if (wgs(WinoGeom<F, 4, 1>::TRW, 32) >= ncu)
-    launch_wino_w<F, 4, 1>(in, B, T, Cin, Cout, U, bias, out, epi, zero16, trash, order, s);
-  else
+  if (p.TG == 4) return launch_wino_w<F, 4, 1>(p, in, T, Cin, Cout, U, bias, out, epi, zero16, trash, s);
 #endif
-  if (wgs(WinoGeom<F, 2, 2>::TRW, 64) >= ncu)
-    launch_wino_w<F, 2, 2>(in, B, T, Cin, Cout, U, bias, out, epi, zero16, trash, order, s);
-  else if (wgs(WinoGeom<F, 1, 2>::TRW, 64) >= ncu)
-    launch_wino_w<F, 1, 2>(in, B, T, Cin, Cout, U, bias, out, epi, zero16, trash, order, s);
+  if (p.TG == 2)
+    launch_wino_w<F, 2, 2>(p, in, T, Cin, Cout, U, bias, out, epi, zero16, trash, s);
+  else if (p.NT == 2)
+    launch_wino_w<F, 1, 2>(p, in, T, Cin, Cout, U, bias, out, epi, zero16, trash, s);
   else
-    launch_wino_w<F, 1, 1>(in, B, T, Cin, Cout, U, bias, out, epi, zero16, trash, order, s);
+    launch_wino_w<F, 1, 1>(p, in, T, Cin, Cout, U, bias, out, epi, zero16, trash, s);
 }
 
 void launch_conv3x3_wino(const float* in, int B, int T, int F, int Cin, int Cout, const float* U,
                          const float* bias, float* out, int epi, const float* zero16, float* trash, hipStream_t s,
                          int order) {
-  // halo lanes outside the clip step through the zero block by the chunk's
-  // channel offset: it must hold Cin + 4 floats
-  if (Cin % 8 != 0 || Cin < 32 || Cout % 64 != 0 || Cout > 512 || B <= 0 || T <= 0 || Cin + 4 > ZERO_BLOCK_FLOATS)
-    return note_launch_error(hipErrorInvalidValue);
-  // the kernel's DMA offsets are 32-bit: batches whose input passes 2^31
-  // elements run as several launches over whole clips (same per-clip work,
-  // so the outputs do not depend on the split)
-  const int64_t in_clip = (int64_t)T * F * Cin;
-  const int64_t out_clip = epi == EPI_STORE ? (int64_t)T * F * Cout
-                           : epi == EPI_POOL2 ? (int64_t)(T / 2) * (F / 2) * Cout : (int64_t)T * Cout;
-  const int64_t bmax = (INT32_MAX - 1) / in_clip;
-  if (bmax < 1) return note_launch_error(hipErrorInvalidValue);
-  for (int64_t b0 = 0; b0 < B; b0 += bmax) {
-    const int bs = (int)std::min<int64_t>(bmax, B - b0);
-    const float* in_s = in + b0 * in_clip;
-    float* out_s = out + b0 * out_clip;
+  do {   // the plan's launches over whole clips
+    const ConvLaunch p = plan_conv_launch(WINO_F23, device_cus(), B, T, F, Cin, Cout, epi, order, false, 0, false);
+    if (p.reject) return note_launch_error(hipErrorInvalidValue);
     switch (F) {
-      case 64: launch_wino_f<64>(in_s, bs, T, Cin, Cout, U, bias, out_s, epi, zero16, trash, order, s); break;
-      case 32: launch_wino_f<32>(in_s, bs, T, Cin, Cout, U, bias, out_s, epi, zero16, trash, order, s); break;
-      case 16: launch_wino_f<16>(in_s, bs, T, Cin, Cout, U, bias, out_s, epi, zero16, trash, order, s); break;
-      case 8: launch_wino_f<8>(in_s, bs, T, Cin, Cout, U, bias, out_s, epi, zero16, trash, order, s); break;
-      default: return note_launch_error(hipErrorInvalidValue);
+      case 64: launch_wino_f<64>(p, in, T, Cin, Cout, U, bias, out, epi, zero16, trash, s); break;
+      case 32: launch_wino_f<32>(p, in, T, Cin, Cout, U, bias, out, epi, zero16, trash, s); break;
+      case 16: launch_wino_f<16>(p, in, T, Cin, Cout, U, bias, out, epi, zero16, trash, s); break;
+      default: launch_wino_f<8>(p, in, T, Cin, Cout, U, bias, out, epi, zero16, trash, s); break;
     }
-  }
-}
-
-template <int TG>
-static void launch_block1_w(const float* x0, int B, int T, const float* U, const float* bias, float* out,
-                            const float* w1, const float* b1, const float* zero16, float* trash, bool c4,
-                            hipStream_t s) {
-  using G = WinoGeom<64, TG, 2, true>;
-  const int tb_per_clip = (T / 2 + G::TRW - 1) / G::TRW;   // pooled: an odd last t-row is dropped
-  const int64_t tblocks = (int64_t)B * tb_per_clip;
-  const int64_t nitems = (tblocks + 7) / 8 * 8;           // one channel group (64 channels) per item
-  if (nitems > INT32_MAX || tblocks <= 0 || (int64_t)B * T * 64 >= INT32_MAX) return note_launch_error(hipErrorInvalidValue);
-  const int64_t resident = (int64_t)wino_device_cus() * G::WG_PER_CU / 8 * 8;
-  const int64_t per = (nitems + WINO_ITEMS_B1 - 1) / WINO_ITEMS_B1;
-  const int64_t nwg = std::min<int64_t>(nitems, std::max<int64_t>(std::max<int64_t>(8, resident), (per + 7) / 8 * 8));
-  auto* k_ = c4 ? wino_block1_kernel<TG, true> : wino_block1_kernel<TG, false>;
-  if (!launch_info(reinterpret_cast<const void*>(k_), G::THREADS, G::LDS_BYTES).ok) return;
-  hipLaunchKernelGGL(k_, dim3((unsigned)nwg), dim3(G::THREADS), G::LDS_BYTES, s, x0, B, T, U, bias, out, zero16, trash,
-                     tb_per_clip, w1, b1);
+    in += p.clips * p.in_clip, out += p.clips * p.out_clip, B -= p.clips;
+  } while (B > 0);
 }
 
 void launch_block1_wino(const float* x0, int B, int T, const float* w1, const float* b1, const float* U,
                         const float* bias, float* out, const float* zero16, float* trash, hipStream_t s, bool c4) {
-  if (B <= 0 || T < 2) return note_launch_error(hipErrorInvalidValue);
-  // 32-bit X0 offsets: batches past 2^31 floats run as several launches over
-  // whole clips (same per-clip work)
-  const int64_t in_clip = (int64_t)T * 64, out_clip = (int64_t)(T / 2) * 32 * 64;
-  const int64_t bmax = (INT32_MAX - 1) / in_clip;
-  for (int64_t b0 = 0; b0 < B; b0 += bmax) {
-    const int bs = (int)std::min<int64_t>(bmax, B - b0);
-    // 2 tile groups x 64 channels (64 tiles, 8 waves) at every batch size
-    // (with 1 tile group the 4 waves would not cover the halo's conv1 pixel
-    // groups)
-    launch_block1_w<2>(x0 + b0 * in_clip, bs, T, U, bias, out + b0 * out_clip, w1, b1, zero16, trash, c4, s);
-  }
+  using G = WinoGeom<64, 2, 2, true>;   // the plan's one shape for block 1
+  auto* k_ = c4 ? wino_block1_kernel<2, true> : wino_block1_kernel<2, false>;
+  do {   // the plan's launches over whole clips
+    const ConvLaunch p = plan_conv_launch(WINO_F23_BLOCK1, device_cus(), B, T, 64, 64, 64, EPI_POOL2, 0, c4, 0, false);
+    if (p.reject) return note_launch_error(hipErrorInvalidValue);
+    if (!launch_info(reinterpret_cast<const void*>(k_), G::THREADS, G::LDS_BYTES).ok) return;
+    hipLaunchKernelGGL(k_, dim3((unsigned)p.nwg), dim3(G::THREADS), G::LDS_BYTES, s, x0, p.clips, T, U, bias, out, zero16,
+                       trash, p.tb_per_clip, w1, b1);
+    x0 += p.clips * p.in_clip, out += p.clips * p.out_clip, B -= p.clips;
+  } while (B > 0);
 }
 
 // Block 1's conv1 (Cin = 1, BN folded, ReLU) as its own launch for the

@@ -62,6 +62,7 @@
 #include <type_traits>
 
 #include "sedx_internal.h"
+#include "wino_geom.h"   // W43Geom (the item's tiles and LDS layout), SEDX_W43_EPI2, SEDX_W43_CLAIM
 
 namespace sedx {
 
@@ -79,28 +80,11 @@ typedef float w43_f32x4 __attribute__((ext_vector_type(4)));
 #ifndef SEDX_W43_PRIO
 #define SEDX_W43_PRIO 2   // static s_setprio: waves 4-7 at 1, 8-11 at 2 (the later-dispatched waves of each SIMD)
 #endif
-#ifndef SEDX_W43_EPI2
-#define SEDX_W43_EPI2 0
-#endif
 #ifndef SEDX_W43_USEL
 #define SEDX_W43_USEL 1
 #endif
 #ifndef SEDX_W43_DMA_SPLIT
 #define SEDX_W43_DMA_SPLIT 5
-#endif
-// Item claims (SEDX_W43_CLAIM 1, the default; launches with more items than
-// CUs): a persistent grid, one workgroup per CU, whose workgroups claim their
-// items from the counter of their XCD lane x = blockIdx & 7 (items 8 v + x,
-// the static decode's XCD mapping), so a workgroup that starts late — its CU
-// held by the other batch's GRU — takes fewer items instead of costing a
-// whole extra round.  The first two items come in one claim at the top; the
-// item after next is claimed at an item's epilogue by its last wave (not a
-// finisher) and lands in LDS before the epilogue's last round, read by every
-// wave at the next item's top.  Counters (sched): 8 ints 128 B apart + a
-// done count at [255], zero at launch; the last workgroup to finish zeroes
-// them again.  0: the static grid-stride order of round 5 (A/B builds).
-#ifndef SEDX_W43_CLAIM
-#define SEDX_W43_CLAIM 1
 #endif
 
 // Diagnostic builds only (SEDX_W43_STAMPS, tools/wino43_bench.cpp): per-wave
@@ -117,63 +101,6 @@ __device__ unsigned long long g_w43_stamps[8];
 #else
 #define W43_MARK(i)
 #endif
-
-// TG: tile groups per item — 2 (32 tiles, 12 waves; every full-size launch)
-// or 1 (16 tiles, 6 waves: the one-clip grids of the 16-channel items at
-// F = 16 / 8, twice the items of 2 for the same work)
-template <int F, int TG = 2>
-struct W43Geom {
-  static constexpr int WAVES = 6 * TG, THREADS = 64 * WAVES;
-  static constexpr int NT = 4, NCH = 64;             // channel tiles / output channels per item
-  static constexpr int TILES = 16 * TG;              // TG tile groups of 16
-  static constexpr int FT = F / 4;                   // tiles per tile row
-  static constexpr int TRW = TILES / FT;             // tile rows per item
-  // a tile group is TRG tile rows x TFG tile columns (lane n = tr TFG + tf)
-  static constexpr int TFG = F == 8 ? 2 : F == 64 ? 16 : 4;
-  static constexpr int TRG = 16 / TFG;
-  static constexpr int RT = 4 * TRW + 2, CS = F + 2; // halo rows / columns
-  // halo row stride: (4 tr RS + 4 tf) / 2 over the 16 tiles of a group must
-  // take the 16 even values mod 32 (b64 bank pairs): 2 RS = 8 (mod 32) for
-  // 4 x 4 groups, 2 RS = 20 (mod 32) for 8 x 2
-  // (F = 64, block 1: one tile row of 16 per group, 2 tf = 0, 2, .., 30 for any even RS)
-  static constexpr int RS = F == 64 ? 66 : F == 32 ? 36 : F == 16 ? 20 : 10;
-  // a plane's halo in 64-dword DMA blocks, one per wave 0..HB-1 (RT RS <= 704
-  // for every F); wave 11 issues its four halo DMAs into an LDS trash block,
-  // so every wave has the same DMA count per step (TG 1: RT RS <= 384, a
-  // block per wave, no trash wave)
-  static constexpr int HB = TG == 2 ? 11 : 6;
-  static constexpr int PS = 64 * HB + 2;             // plane stride, = 2 mod 4 (odd bank pairs for odd k)
-  static constexpr int HALO = 4 * PS;                // dwords per halo slot
-  static constexpr int USZ1 = 36 * 4 * 16;           // NT 1: one 16-channel tile's slab ([p][k][m]), 9 KiB
-  static constexpr int NB = 3;                       // ring depth (U and halo)
-  // epilogue exchange per round, per tile group, in the U slot freed by the
-  // item's last step: STORE [row 6][reg 2][kc 4][16 tiles + 4 pad][4 z] (the
-  // pad: a finisher's reads of 4 kc x 16 consecutive (tile, column) words
-  // hit 64 banks), else [row 6][reg 2][z pair 2][lane 64][2] (a finisher's
-  // ds_read_b64 of its own pair: conflict-free)
-  static constexpr int XRS = 4 * 80;
-  static constexpr int XTG = 6 * 2 * XRS;
-  // dwords per U slot: the 64-channel slab ([p][k][m][nt]); TG 1 (NT 1 only):
-  // its 9 KiB slab or one tile group's exchange, the larger
-  static constexpr int USZ = TG == 2 ? 36 * 4 * NCH : (USZ1 > XTG ? USZ1 : XTG);
-  static constexpr int U_OFF = 0, H_OFF = NB * USZ, BIAS_OFF = H_OFF + NB * HALO, BIAS_MAX = 512;
-  static constexpr int HTRASH_OFF = BIAS_OFF + BIAS_MAX;   // 64 dwords: wave 11's halo DMAs
-  // a second exchange area (SEDX_W43_EPI2, pooled / freq-mean epilogues): one
-  // tile group's [row 6][reg 2][z pair 2][lane 64][2] for registers 2, 3
-  static constexpr int X2_OFF = HTRASH_OFF + 64, X2 = SEDX_W43_EPI2 && TG == 2 ? 3072 : 0;
-  static constexpr int CL_OFF = X2_OFF + X2;         // item claims: the landed claim ([0]) and the first item ([1])
-  static constexpr int LDS_BYTES = 4 * (CL_OFF + (SEDX_W43_CLAIM ? 4 : 0));
-  static constexpr int VM = 7;                       // DMAs per wave per step (3 U units + 4 halo planes)
-
-  static_assert(F == 64 || F == 32 || F == 16 || F == 8, "F");
-  static_assert(RT * RS <= 64 * HB, "halo plane fits its DMA blocks");
-  static_assert(TG == 1 || TG == 2, "TG");
-  static_assert(TG == 1 ? HB == WAVES : HB == WAVES - 1, "halo blocks: one per wave (TG 2: wave 11 trash)");
-  static_assert(TG == 1 || 36 % WAVES == 0, "U units per wave");
-  static_assert(TG * XTG <= USZ, "the tile groups' exchange fits one U slot");
-  static_assert(LDS_BYTES <= 160 * 1024, "LDS per workgroup");
-  static_assert(FT * TRW == TILES && TFG * TRG == 16, "tile groups");
-};
 
 // raw workgroup barrier behind "this wave's DMAs and stores older than its N
 // youngest VMEM ops landed, its LDS operations done" (__syncthreads() would
@@ -1002,59 +929,14 @@ __global__ __launch_bounds__(384 * TG, 1) void conv3x3_wino43_kernel(const float
 }
 #undef SEDX_W43_ROWS
 
-// items per workgroup.  Alone on the chip 16 (one persistent workgroup per
-// CU: one exposed prologue per CU) is fastest — blocks 1-4 2.41 -> 2.35 ms
-// (profiles/r05n_w43_items.log; 3 and 6 are slower:
-// their grids break the L2 round order) — but in the two-stream headline
-// long-lived workgroups hold the CUs the other batch's frontend / GRU /
-// head need: 11,362-11,424 clips/s at 16, 11,546-11,585 at 4,
-// 11,708-11,724 at 2 (profiles/r05p_items_ab.log).  2 stays.
-#ifndef SEDX_W43_ITEMS
-#define SEDX_W43_ITEMS 2
-#endif
-
-// one launch of the F(4x4,3x3) kernel with TG tile groups per item and
-// 16- (nt1) or 64-channel items
+// one launch of the plan's (plan.cpp, plan_conv_launch) p.clips clips with TG
+// tile groups per item and 16- (p.NT 1) or 64-channel items
 template <int F, int TG>
-static void launch_w43_g(const float* in, int B, int T, int Cin, int Cout, const float* U, const float* bias,
-                         float* out, int epi, float* trash, int order, bool c4, bool nt1, int ncu, int* sched,
-                         hipStream_t s) {
+static void launch_w43_g(const ConvLaunch& p, const float* in, int T, int Cin, int Cout, const float* U,
+                         const float* bias, float* out, int epi, float* trash, bool c4, int* sched, hipStream_t s) {
   using G = W43Geom<F, TG>;
-  // output rows the epilogue covers: POOL2 drops an odd last row
-  const int rows = epi == EPI_POOL2 ? 2 * (T / 2) : T;
-  const int trows = (rows + 3) / 4;
-  const int tb_per_clip = (trows + G::TRW - 1) / G::TRW;
-  const int64_t tblocks = (int64_t)B * tb_per_clip;
-  const int ngroups = Cout / (nt1 ? 16 : G::NCH);
-  // NT 1: 8 XCD lanes x ceil(groups / 8) channel tiles x every tile block
-  const int64_t nitems = nt1 ? 8 * ((ngroups + 7) / 8) * tblocks : (tblocks + 7) / 8 * 8 * ngroups;
-  const int64_t u_bytes = 2 * (int64_t)Cin * Cout * 36 * 4;   // the NT 4 pack, then the NT 1 pack
-  if (nitems > INT32_MAX || tblocks <= 0 || (int64_t)B * T * F * Cin * 4 >= INT32_MAX || u_bytes >= INT32_MAX)
-    return note_launch_error(hipErrorInvalidValue);
-  const int64_t resident = (int64_t)ncu / 8 * 8;
-  const int64_t per = (nitems + SEDX_W43_ITEMS - 1) / SEDX_W43_ITEMS;
-  int64_t nwg = std::min<int64_t>(nitems, std::max<int64_t>(std::max<int64_t>(8, resident), (per + 7) / 8 * 8));
-  // item claims where there are more than two items per CU: one persistent
-  // workgroup per CU (nwg a multiple of 8: every XCD lane has workgroups).
-  // Below that the first claim's latency is not amortised (B = 4 block 1:
-  // 0.0645 vs 0.0627 ms static, profiles/r06zb_*) and the static order runs.
-  const bool claim = SEDX_W43_CLAIM && sched != nullptr && nitems > 2 * resident && resident >= 8;
-  if (claim) nwg = resident;
-  int* const sched_k = claim ? sched : nullptr;
-  // rounds of 32 / G tile blocks x G channel groups (conv_wino.hip): the G
-  // whose round streams the fewest bytes through an XCD's L2
-  int order2d = F == 64 && order == 2 && !nt1 ? -1 : 0;
-  if (order && !nt1 && F != 64 && nwg % 256 == 0 && (nitems / 8) % 32 == 0) {
-    const int64_t slab = (int64_t)36 * Cin * G::NCH * 4, halo = (int64_t)G::RT * G::CS * Cin * 4;
-    int64_t best = (int64_t)ngroups * slab + (32 / std::min(ngroups, 32)) * halo;
-    for (int gr = 1; gr <= 8 && gr < ngroups; gr *= 2) {
-      const int64_t bytes = gr * slab + (32 / gr) * halo;
-      if (ngroups % gr == 0 && tblocks % (8 * (32 / gr)) == 0 && bytes < best) {
-        best = bytes;
-        order2d = gr;
-      }
-    }
-  }
+  const int u_bytes = 2 * Cin * Cout * 36 * 4;   // the NT 4 pack, then the NT 1 pack (< 2^31: the plan)
+  int* const sched_k = p.claim ? sched : nullptr;
   // Counted vmcnt waits and spills: the chunk-of-4 builds (the product
   // path) are refused if the compiler ever makes them spill (launch_info
   // no_scratch; 0 bytes in this build, -Rpass-analysis / the ISA's
@@ -1063,23 +945,16 @@ static void launch_w43_g(const float* in, int B, int T, int Cin, int Cout, const
   // math: a scratch op the compiler inserts only ever ADDS vector-memory ops
   // to a wave's in-order count, so a counted wait then retires more of the
   // older DMAs than it names, never fewer — stricter, not looser.
-#define SEDX_W43_GO(k_)                                                                                     \
-  {                                                                                                         \
-    if (!launch_info(reinterpret_cast<const void*>(k_), G::THREADS, G::LDS_BYTES, c4).ok) return;           \
-    hipLaunchKernelGGL(k_, dim3((unsigned)nwg), dim3(G::THREADS), G::LDS_BYTES, s, in, B, T, Cin, Cout, U,  \
-                       (int)u_bytes, bias, out, trash, tb_per_clip, ngroups, order2d, sched_k);             \
-    return;                                                                                                 \
-  }
 #define SEDX_W43_LAUNCH(E)                                                                                  \
   {                                                                                                         \
-    if constexpr (TG == 1) {   /* 16-tile items: 16-channel, chunk-of-4 only */                             \
-      if (!nt1 || !c4) return note_launch_error(hipErrorInvalidValue);                                     \
-      SEDX_W43_GO((conv3x3_wino43_kernel<F, E, true, 1, 1>));                                              \
-    } else {                                                                                                \
-      auto* k_ = nt1 ? (c4 ? conv3x3_wino43_kernel<F, E, true, 1> : conv3x3_wino43_kernel<F, E, false, 1>)  \
+    auto* k_ = conv3x3_wino43_kernel<F, E, true, 1, TG>;   /* 16-tile items: 16-channel, chunk-of-4 only (the plan) */ \
+    if constexpr (TG == 2)                                                                                  \
+      k_ = p.NT == 1 ? (c4 ? conv3x3_wino43_kernel<F, E, true, 1> : conv3x3_wino43_kernel<F, E, false, 1>)  \
                      : (c4 ? conv3x3_wino43_kernel<F, E, true, 4> : conv3x3_wino43_kernel<F, E, false, 4>); \
-      SEDX_W43_GO(k_);                                                                                      \
-    }                                                                                                       \
+    if (!launch_info(reinterpret_cast<const void*>(k_), G::THREADS, G::LDS_BYTES, c4).ok) return;           \
+    hipLaunchKernelGGL(k_, dim3((unsigned)p.nwg), dim3(G::THREADS), G::LDS_BYTES, s, in, p.clips, T, Cin,   \
+                       Cout, U, u_bytes, bias, out, trash, p.tb_per_clip, p.ngroups, p.order2d, sched_k);   \
+    return;                                                                                                 \
   }
   if constexpr (F == 64) {   // block 1's conv2 (conv1's output in, 2 x 2 pool)
     if (epi == EPI_POOL2) SEDX_W43_LAUNCH(EPI_POOL2);
@@ -1091,63 +966,33 @@ static void launch_w43_g(const float* in, int B, int T, int Cin, int Cout, const
     if (epi == EPI_POOL2) SEDX_W43_LAUNCH(EPI_POOL2);
   }
 #undef SEDX_W43_LAUNCH
-#undef SEDX_W43_GO
   note_launch_error(hipErrorInvalidValue);
 }
 
-// nt_force: 0 = choose; 4 = 64-channel items; 1 = 16-channel items of 32
-// tiles; 2 = 16-channel items of 16 tiles (F = 16 / 8, chunk-of-4)
 template <int F>
-static void launch_w43_f(const float* in, int B, int T, int Cin, int Cout, const float* U, const float* bias,
-                         float* out, int epi, float* trash, int order, bool c4, int nt_force, int* sched,
-                         hipStream_t s) {
-  using G = W43Geom<F>;
-  const int rows = epi == EPI_POOL2 ? 2 * (T / 2) : T;
-  const int64_t tblocks = (int64_t)B * (((rows + 3) / 4 + G::TRW - 1) / G::TRW);
-  int ncu = 256, dev = 0;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  // 16-channel items (NT 1, bit-identical) when 64-channel ones would give
-  // at most a quarter of the CUs one (measured, profiles/r05q_small_batch.log:
-  // at 128 items — b3c2 at B = 4, b4 at B = 8 — NT 1's four times the items
-  // at a quarter the work each were slower; at <= 64 faster)
-  const bool nt1 = nt_force ? nt_force != 4 : (tblocks + 7) / 8 * 8 * (Cout / G::NCH) <= ncu / 4;
-  // 16-channel items of one tile group (16 tiles, 6 waves) where those of
-  // two would leave CUs idle (one clip: the 256- and 512-channel layers, 128
-  // and 64 items of 32 tiles; bit-identical — the same chains per output)
-  constexpr bool tg1_ok = F == 16 || F == 8;
-  const bool tg1 = tg1_ok && c4 && nt1 &&
-                   (nt_force ? nt_force == 2 : 8 * ((Cout / 16 + 7) / 8) * tblocks < ncu);
-  if (nt_force == 2 && !tg1) return note_launch_error(hipErrorInvalidValue);
-  if constexpr (tg1_ok) {
-    if (tg1) return launch_w43_g<F, 1>(in, B, T, Cin, Cout, U, bias, out, epi, trash, order, c4, true, ncu, sched, s);
+static void launch_w43_f(const ConvLaunch& p, const float* in, int T, int Cin, int Cout, const float* U,
+                         const float* bias, float* out, int epi, float* trash, bool c4, int* sched, hipStream_t s) {
+  if constexpr (F == 16 || F == 8) {
+    if (p.TG == 1) return launch_w43_g<F, 1>(p, in, T, Cin, Cout, U, bias, out, epi, trash, c4, sched, s);
   }
-  launch_w43_g<F, 2>(in, B, T, Cin, Cout, U, bias, out, epi, trash, order, c4, nt1, ncu, sched, s);
+  launch_w43_g<F, 2>(p, in, T, Cin, Cout, U, bias, out, epi, trash, c4, sched, s);
 }
 
 void launch_conv3x3_wino43(const float* in, int B, int T, int F, int Cin, int Cout, const float* U43,
                            const float* bias, float* out, int epi, float* trash, hipStream_t s, int order, bool c4,
                            int nt_force, int* sched) {
-  if (Cin % 8 != 0 || Cin < 16 || Cout % 64 != 0 || Cout > 512 || B <= 0 || T <= 0)
-    return note_launch_error(hipErrorInvalidValue);
-  // byte offsets are 32-bit (buffer DMA): batches whose input passes 2^31
-  // bytes run as several launches over whole clips (same per-clip work)
-  const int64_t in_clip = (int64_t)T * F * Cin;
-  const int64_t out_clip = epi == EPI_STORE ? (int64_t)T * F * Cout
-                           : epi == EPI_POOL2 ? (int64_t)(T / 2) * (F / 2) * Cout : (int64_t)T * Cout;
-  const int64_t bmax = (INT32_MAX / 4 - 1) / in_clip;
-  if (bmax < 1) return note_launch_error(hipErrorInvalidValue);
-  for (int64_t b0 = 0; b0 < B; b0 += bmax) {
-    const int bs = (int)std::min<int64_t>(bmax, B - b0);
-    const float* in_s = in + b0 * in_clip;
-    float* out_s = out + b0 * out_clip;
+  do {   // the plan's launches over whole clips
+    const ConvLaunch p = plan_conv_launch(WINO_F43, device_cus(), B, T, F, Cin, Cout, epi, order, c4, nt_force,
+                                          sched != nullptr);
+    if (p.reject) return note_launch_error(hipErrorInvalidValue);
     switch (F) {
-      case 64: launch_w43_f<64>(in_s, bs, T, Cin, Cout, U43, bias, out_s, epi, trash, order, c4, nt_force, sched, s); break;
-      case 32: launch_w43_f<32>(in_s, bs, T, Cin, Cout, U43, bias, out_s, epi, trash, order, c4, nt_force, sched, s); break;
-      case 16: launch_w43_f<16>(in_s, bs, T, Cin, Cout, U43, bias, out_s, epi, trash, order, c4, nt_force, sched, s); break;
-      case 8: launch_w43_f<8>(in_s, bs, T, Cin, Cout, U43, bias, out_s, epi, trash, order, c4, nt_force, sched, s); break;
-      default: return note_launch_error(hipErrorInvalidValue);
+      case 64: launch_w43_f<64>(p, in, T, Cin, Cout, U43, bias, out, epi, trash, c4, sched, s); break;
+      case 32: launch_w43_f<32>(p, in, T, Cin, Cout, U43, bias, out, epi, trash, c4, sched, s); break;
+      case 16: launch_w43_f<16>(p, in, T, Cin, Cout, U43, bias, out, epi, trash, c4, sched, s); break;
+      default: launch_w43_f<8>(p, in, T, Cin, Cout, U43, bias, out, epi, trash, c4, sched, s); break;
     }
-  }
+    in += p.clips * p.in_clip, out += p.clips * p.out_clip, B -= p.clips;
+  } while (B > 0);
 }
 
 #ifdef SEDX_W43_STAMPS

@@ -764,7 +764,9 @@ static void launch_x3_epi(const float* in, int B, int T, int Cin, int Cout, cons
   if (!li.ok) return;
   const int resident = li.ncu * li.per_cu;
   const size_t pad = li.dyn;
-  const int ntiles = B * ((T + TT - 1) / TT) * (Cout / BN);
+  const int64_t ntiles64 = (int64_t)B * ((T + TT - 1) / TT) * (Cout / BN);
+  if (ntiles64 <= 0 || ntiles64 > INT32_MAX) return note_launch_error(hipErrorInvalidValue);   // the kernel's tile index is an int
+  const int ntiles = (int)ntiles64;
   const int per_xcd = (ntiles + 7) / 8;
   int grid = resident & ~7;
   if (grid < 8) grid = 8;
@@ -778,19 +780,15 @@ static void launch_x3(const float* in, int B, int T, int Cin, int Cout, const ui
                       const float* bias, float* out, int epi, int* sched, hipStream_t s) {
   // only the (F, epilogue) pairs of the model are instantiated
   if constexpr (F == 8) {
-    if (epi == EPI_STORE)
-      launch_x3_epi<8, BN, EPI_STORE>(in, B, T, Cin, Cout, wp, bias, out, sched, s);
-    else if (epi == EPI_FMEAN)
-      launch_x3_epi<8, BN, EPI_FMEAN>(in, B, T, Cin, Cout, wp, bias, out, sched, s);
+    if (epi == EPI_STORE) return launch_x3_epi<8, BN, EPI_STORE>(in, B, T, Cin, Cout, wp, bias, out, sched, s);
+    if (epi == EPI_FMEAN) return launch_x3_epi<8, BN, EPI_FMEAN>(in, B, T, Cin, Cout, wp, bias, out, sched, s);
   } else if constexpr (F == 64) {
-    if (epi == EPI_POOL2)
-      launch_x3_epi<F, BN, EPI_POOL2>(in, B, T, Cin, Cout, wp, bias, out, sched, s);
+    if (epi == EPI_POOL2) return launch_x3_epi<F, BN, EPI_POOL2>(in, B, T, Cin, Cout, wp, bias, out, sched, s);
   } else {
-    if (epi == EPI_STORE)
-      launch_x3_epi<F, BN, EPI_STORE>(in, B, T, Cin, Cout, wp, bias, out, sched, s);
-    else if (epi == EPI_POOL2)
-      launch_x3_epi<F, BN, EPI_POOL2>(in, B, T, Cin, Cout, wp, bias, out, sched, s);
+    if (epi == EPI_STORE) return launch_x3_epi<F, BN, EPI_STORE>(in, B, T, Cin, Cout, wp, bias, out, sched, s);
+    if (epi == EPI_POOL2) return launch_x3_epi<F, BN, EPI_POOL2>(in, B, T, Cin, Cout, wp, bias, out, sched, s);
   }
+  note_launch_error(hipErrorInvalidValue);   // never leave the output unwritten silently
 }
 
 // Shapes: Cin a multiple of 32 (the unit stream pairs chunks), Cout a
@@ -798,21 +796,14 @@ static void launch_x3(const float* in, int B, int T, int Cin, int Cout, const ui
 void launch_conv3x3_x3(const float* in, int B, int T, int F, int Cin, int Cout, const void* wp,
                        const float* bias, float* out, int epi, int* sched, hipStream_t s) {
   const uint4* w = static_cast<const uint4*>(wp);
-  if (Cin % 32 != 0 || Cin < 64) return;   // the claim of tile k+1 lands >= 1 unit before its decode
-  switch (F) {
-    case 64:   // block 1 conv2 (Cout 64)
-      if (Cout % 64 == 0) launch_x3<64, 64>(in, B, T, Cin, Cout, w, bias, out, epi, sched, s);
-      break;
-    case 32:
-      if (Cout % 128 == 0) launch_x3<32, 128>(in, B, T, Cin, Cout, w, bias, out, epi, sched, s);
-      break;
-    case 16:
-      if (Cout % 128 == 0) launch_x3<16, 128>(in, B, T, Cin, Cout, w, bias, out, epi, sched, s);
-      break;
-    case 8:
-      if (Cout % 128 == 0) launch_x3<8, 128>(in, B, T, Cin, Cout, w, bias, out, epi, sched, s);
-      break;
-    default: break;
+  // Cin: the claim of tile k+1 lands >= 1 unit before its decode
+  const bool ok = Cin % 32 == 0 && Cin >= 64 && Cout % (F == 64 ? 64 : 128) == 0;
+  switch (ok ? F : 0) {
+    case 64: return launch_x3<64, 64>(in, B, T, Cin, Cout, w, bias, out, epi, sched, s);   // block 1 conv2 (Cout 64)
+    case 32: return launch_x3<32, 128>(in, B, T, Cin, Cout, w, bias, out, epi, sched, s);
+    case 16: return launch_x3<16, 128>(in, B, T, Cin, Cout, w, bias, out, epi, sched, s);
+    case 8: return launch_x3<8, 128>(in, B, T, Cin, Cout, w, bias, out, epi, sched, s);
+    default: return note_launch_error(hipErrorInvalidValue);   // never leave the output unwritten silently
   }
 }
 

@@ -1,6 +1,8 @@
 // plan.h: the forward plan and the windowed drivers' layout (host only).
 #include "plan.h"
 
+#include "wino_geom.h"
+
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -73,7 +75,8 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
     const int blk = (i + 1) / 2, cout = 64 << blk, Tl = (int)Ts[blk], F = 64 >> blk, pool = i % 2 == 0 && i < 6;
     p->layers[i] = ConvLayer{Tl, F, i == 0 ? 64 : i % 2 ? cout / 2 : cout, cout,
                              i == 6 ? EPI_FMEAN : pool ? EPI_POOL2 : EPI_STORE,
-                             pool ? Tl / 2 : Tl, i == 6 ? 1 : pool ? F / 2 : F, 0, 0};
+                             pool ? Tl / 2 : Tl, i == 6 ? 1 : pool ? F / 2 : F, 0, 0,
+                             i == 0 && p->block1 == B1_CONV1_F23 ? 0 : t.wino_order};
     size_t& ext = i % 2 ? a_conv : p_conv;
     ext = std::max(ext, (size_t)B * p->layers[i].To * p->layers[i].Fo * cout);
   }
@@ -114,6 +117,182 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
              CF_MAX_T);
   else if (B * g.T > INT32_MAX / 64) snprintf(p->reject, sizeof(p->reject), "batch too large");   // 32-bit launch sizes
   return p->reject[0] ? p->reject : nullptr;
+}
+
+// ---- one Winograd conv launch -----------------------------------------------
+// items per persistent workgroup (compile-time inputs of A/B builds)
+#ifndef SEDX_WINO_ITEMS
+#define SEDX_WINO_ITEMS 4
+#endif
+// block 1's one-launch kernel: ~8 items per workgroup (isolated 0.731-0.733
+// ms against 0.735-0.744 at 4 and 0.748-0.752 at 2; the two-stream headline
+// the same within noise over four alternating rounds, tools/gpu_ab_iso.sh)
+#ifndef SEDX_WINO_ITEMS_B1
+#define SEDX_WINO_ITEMS_B1 8
+#endif
+// F(4x4,3x3).  Alone on the chip 16 (one persistent workgroup per
+// CU: one exposed prologue per CU) is fastest — blocks 1-4 2.41 -> 2.35 ms
+// (profiles/r05n_w43_items.log; 3 and 6 are slower:
+// their grids break the L2 round order) — but in the two-stream headline
+// long-lived workgroups hold the CUs the other batch's frontend / GRU /
+// head need: 11,362-11,424 clips/s at 16, 11,546-11,585 at 4,
+// 11,708-11,724 at 2 (profiles/r05p_items_ab.log).  2 stays.
+#ifndef SEDX_W43_ITEMS
+#define SEDX_W43_ITEMS 2
+#endif
+
+namespace {
+constexpr int64_t ceil8(int64_t n) { return (n + 7) / 8 * 8; }
+
+// what the plan reads of an item's geometry (wino_geom.h)
+struct Item {
+  int TG, NT;
+  int trw, nch, wg_per_cu;   // tile rows and output channels of an item, workgroups a CU holds
+  int64_t slab, halo;        // bytes of an item's weight slab and halo per input channel
+};
+template <int F, int TG, int NT, bool C1 = false>
+constexpr Item f23_item() {
+  using G = WinoGeom<F, TG, NT, C1>;
+  return Item{TG, NT, G::TRW, G::NCH, G::WG_PER_CU, 16 * G::NCH * 4, G::PL * 4};
+}
+template <int TG, int NT>
+Item f23_item(int F) {
+  return F == 64 ? f23_item<64, TG, NT>() : F == 32 ? f23_item<32, TG, NT>() : F == 16 ? f23_item<16, TG, NT>()
+                                                                                      : f23_item<8, TG, NT>();
+}
+// nt1: 16-channel items (NT 1) of the same tiles; __launch_bounds__(.., 1): one workgroup per CU
+template <int F, int TG>
+constexpr Item f43_item(bool nt1) {
+  using G = W43Geom<F, TG>;
+  return Item{TG, nt1 ? 1 : G::NT, G::TRW, nt1 ? 16 : G::NCH, 1, 36 * G::NCH * 4, G::RT * G::CS * 4};
+}
+Item f43_item(int F, int TG, bool nt1) {
+  if (TG == 1) return F == 16 ? f43_item<16, 1>(nt1) : f43_item<8, 1>(nt1);   // 16-tile items: F = 16 / 8 only
+  return F == 64 ? f43_item<64, 2>(nt1) : F == 32 ? f43_item<32, 2>(nt1) : F == 16 ? f43_item<16, 2>(nt1)
+                                                                                   : f43_item<8, 2>(nt1);
+}
+
+// Persistent workgroups, a multiple of 8 (XCD-aware item decode), each
+// walking its items with the next item's first chunks landing during the
+// current one's last: ~items_per_wg items per workgroup, but at least one
+// resident round — the hardware dispatcher still balances the workgroups over
+// the CUs (a CU shared with another stream's kernel finishes its workgroups later)
+int64_t persistent_grid(int64_t nitems, int64_t resident, int items_per_wg) {
+  const int64_t per = (nitems + items_per_wg - 1) / items_per_wg;
+  return std::min(nitems, std::max(std::max<int64_t>(8, resident), ceil8(per)));
+}
+
+// Rounds of 32 / G tile blocks x G channel groups: the G (< ngroups, dividing
+// it) whose round streams the fewest bytes through an XCD's L2 — G weight
+// slabs + 32 / G halos — with whole rounds of tile blocks per XCD and no
+// padding; 0: the default order, tile block major.  (F(2x2) b4c2: 4 slabs of
+// 2 MB + 8 halos of 0.7 MB instead of 8 + 4.)
+int l2_round_order(int ngroups, int64_t tblocks, int64_t slab, int64_t halo) {
+  int order2d = 0;
+  int64_t best = (int64_t)ngroups * slab + (32 / std::min(ngroups, 32)) * halo;
+  for (int gr = 1; gr <= 8 && gr < ngroups; gr *= 2) {
+    const int64_t bytes = gr * slab + (32 / gr) * halo;
+    if (ngroups % gr == 0 && tblocks % (8 * (32 / gr)) == 0 && bytes < best) best = bytes, order2d = gr;
+  }
+  return order2d;
+}
+}  // namespace
+
+ConvLaunch plan_conv_launch(WinoFamily family, int ncu, int64_t B, int T, int F, int Cin, int Cout, int epi, int order,
+                            bool c4, int nt_force, bool sched) {
+  ConvLaunch p;
+  auto refuse = [&p](const char* why) { return p.reject = why, p; };
+  const bool b1 = family == WINO_F23_BLOCK1, f43 = family == WINO_F43;
+  if (b1) F = Cin = Cout = 64, epi = EPI_POOL2, order = 0;   // X0 in, conv1's 64 channels, the pooled conv2 out
+  if (B <= 0 || T < (b1 ? 2 : 1)) return refuse("empty batch or clip");
+  if (F != 64 && F != 32 && F != 16 && F != 8) return refuse("F is not 64, 32, 16 or 8");
+  if (Cin % 8 != 0 || Cin < (f43 ? 16 : 32) || Cout % 64 != 0 || Cout > 512) return refuse("channel counts");
+  // F(2x2): halo lanes outside the clip step through the zero block by the
+  // chunk's channel offset, so it must hold Cin + 4 floats
+  if (family == WINO_F23 && Cin + 4 > ZERO_BLOCK_FLOATS) return refuse("Cin past the zero block");
+  // the instantiated epilogues: the freq mean at F = 8 only and no pool
+  // there; F(4x4) at F = 64 is block 1's conv2 (pooled)
+  if (!(epi == EPI_STORE ? !(f43 && F == 64) : epi == EPI_POOL2 ? F != 8 : epi == EPI_FMEAN && F == 8))
+    return refuse("no kernel for this epilogue at this F");
+  // offsets in the kernels are 32-bit — elements, F(4x4)'s buffer DMA bytes:
+  // a batch whose input passes 2^31 runs as launches over whole clips (same
+  // per-clip work, so the outputs do not depend on the split)
+  p.in_clip = b1 ? (int64_t)T * 64 : (int64_t)T * F * Cin;
+  p.out_clip = (int64_t)Cout * (epi == EPI_STORE ? (int64_t)T * F : epi == EPI_POOL2 ? (int64_t)(T / 2) * (F / 2) : T);
+  p.clips_per_launch = (f43 ? INT32_MAX / 4 - 1 : INT32_MAX - 1) / p.in_clip;
+  if (p.clips_per_launch < 1) return refuse("one clip passes the 32-bit offsets");
+  p.clips = (int)std::min(B, p.clips_per_launch);
+  // ---- the item ----
+  // tile rows of a clip: POOL2 drops an odd last row, the others keep it
+  const int rows = epi == EPI_POOL2 ? 2 * (T / 2) : T;
+  const int trows = f43 ? (rows + 3) / 4 : (rows + 1) / 2;
+  auto tblocks_of = [&](const Item& i) { return (int64_t)p.clips * ((trows + i.trw - 1) / i.trw); };
+  Item it;
+  if (f43) {
+    // nt_force: 0 = choose; 4 = 64-channel items; 1 = 16-channel items of 32
+    // tiles; 2 = 16-channel items of 16 tiles (F = 16 / 8, chunk-of-4).
+    // 16-channel items (NT 1, bit-identical) when 64-channel ones would give
+    // at most a quarter of the CUs one (measured, profiles/r05q_small_batch.log:
+    // at 128 items — b3c2 at B = 4, b4 at B = 8 — NT 1's four times the items
+    // at a quarter the work each were slower; at <= 64 faster)
+    const int64_t tb2 = tblocks_of(f43_item(F, 2, false));
+    const bool nt1 = nt_force ? nt_force != 4 : ceil8(tb2) * (Cout / 64) <= ncu / 4;
+    // 16-channel items of one tile group (16 tiles, 6 waves) where those of
+    // two would leave CUs idle (one clip: the 256- and 512-channel layers, 128
+    // and 64 items of 32 tiles; bit-identical — the same chains per output)
+    const bool tg1 = (F == 16 || F == 8) && c4 && nt1 && (nt_force ? nt_force == 2 : ceil8(Cout / 16) * tb2 < ncu);
+    if (nt_force == 2 && !tg1) return refuse("16-tile items: F = 16 / 8 in the chunk-of-4 layout only");
+    it = f43_item(F, tg1 ? 1 : 2, nt1);
+  } else if (b1) {
+    // 2 tile groups x 64 channels (64 tiles, 8 waves) at every batch size (with
+    // 1 tile group the 4 waves would not cover the halo's conv1 pixel groups)
+    it = f23_item<64, 2, 2, true>();
+  } else {
+    // 2 tile groups x 64 channels (8 waves) when that gives every CU a
+    // workgroup, else 1 x 64, else 1 x 32: the same per-(tile, channel) work
+    auto fills = [&](const Item& i) { return tblocks_of(i) * (Cout / i.nch) >= ncu; };
+    it = fills(f23_item<2, 2>(F)) ? f23_item<2, 2>(F) : fills(f23_item<1, 2>(F)) ? f23_item<1, 2>(F) : f23_item<1, 1>(F);
+#ifdef SEDX_WINO_TG4   // A/B builds: 4 (and before it 3) tile groups x 32 channels where they fill the CUs
+    if (fills(f23_item<4, 1>(F))) it = f23_item<4, 1>(F);
+#endif
+#ifdef SEDX_WINO_TG3
+    if (fills(f23_item<3, 1>(F))) it = f23_item<3, 1>(F);
+#endif
+  }
+  p.TG = it.TG, p.NT = it.NT;
+  // ---- items and grid ----
+  p.tb_per_clip = (trows + it.trw - 1) / it.trw;
+  p.ngroups = Cout / it.nch;
+  const int64_t tblocks = tblocks_of(it);
+  // F(4x4) NT 1: 8 XCD lanes x ceil(groups / 8) channel tiles x every tile block
+  const int64_t nitems = f43 && it.NT == 1 ? ceil8(p.ngroups) * tblocks : ceil8(tblocks) * p.ngroups;
+  if (nitems > INT32_MAX || tblocks <= 0) return refuse("no tile row, or items past 2^31");
+  // F(4x4)'s U: the NT 4 pack, then the NT 1 pack, behind one 32-bit buffer range
+  if (f43 && 2 * (int64_t)Cin * Cout * 36 * 4 >= INT32_MAX) return refuse("U passes the 32-bit buffer range");
+  const int64_t resident = (int64_t)ncu * it.wg_per_cu / 8 * 8;
+  const int64_t grid = persistent_grid(nitems, resident, f43 ? SEDX_W43_ITEMS : b1 ? SEDX_WINO_ITEMS_B1 : SEDX_WINO_ITEMS);
+  // F(4x4) item claims where there are more than two items per CU: one
+  // persistent workgroup per CU (nwg a multiple of 8: every XCD lane has
+  // workgroups).  Below that the first claim's latency is not amortised (B = 4
+  // block 1: 0.0645 vs 0.0627 ms static, profiles/r06zb_*) and the static order
+  // runs.  (plan_forward passes no counters below 8 clips: ForwardPlan::claims.)
+  p.claim = f43 && SEDX_W43_CLAIM && sched && nitems > 2 * resident && resident >= 8;
+  const int64_t nwg = p.claim ? resident : grid;
+  p.nitems = (int)nitems, p.nwg = (int)nwg;
+  // ---- the item order: whole 32-item rounds per XCD, a workgroup keeps its
+  // slot in the round from item to item ----
+  const bool rounds = order && nwg % 256 == 0 && (nitems / 8) % 32 == 0;
+  if (f43 && F == 64) p.order2d = order == 2 && it.NT != 1 ? -1 : 0;   // block 1's contiguous per-XCD order
+  else if (rounds && !b1 && !(f43 && it.NT == 1))
+    p.order2d = l2_round_order(p.ngroups, tblocks, it.slab * Cin, it.halo * Cin);
+  return p;
+}
+
+bool conv_launch_family(const ForwardPlan& p, int i, WinoFamily* family) {
+  const bool b1 = i == 0 && p.block1 != B1_PAD_EXACT && p.block1 != B1_PAD_X3;   // a Winograd stage 2
+  if (b1) *family = p.block1 == B1_F23_FUSED ? WINO_F23_BLOCK1 : p.block1 == B1_CONV1_F23 ? WINO_F23 : WINO_F43;
+  else *family = p.family == CONV_WINO ? WINO_F23 : WINO_F43;
+  return b1 || (i > 0 && (p.family == CONV_WINO || p.family == CONV_WINO43));
 }
 
 const char* window_geometry(const Model& m, int64_t L_clip, const sedx_window_spec* spec, bool avg, WinGeom* wg) {

@@ -1,7 +1,8 @@
 // The host's plan of one forward: its geometry, which kernel runs each conv
 // layer and the recurrence, and where everything lives in the workspace.
 // api.cpp launches from it and sizes the workspace by it, so what a forward
-// writes and what sedx_workspace_size asks for cannot drift apart.  Also the
+// writes and what sedx_workspace_size asks for cannot drift apart.  Also what
+// a Winograd conv launch looks like (plan_conv_launch: the launchers ask it), the
 // windowed drivers' loop, merge plan (windows.cpp) and device-area layout.
 // Plain C++: no HIP header, so the plans build and run without a GPU
 // (tests/native/asan_driver.cpp).
@@ -80,6 +81,7 @@ struct ConvLayer {
   int T, F, cin, cout, epi;
   int To, Fo;       // the output's rows and columns ([B][To][Fo][cout]; EPI_FMEAN: Fo = 1)
   size_t in, out;   // float offsets in the workspace
+  int order;        // a Winograd launch's round order: SEDX_TUNE_WINO_ORDER (0 for block 1's F(2x2) conv2)
 };
 struct ForwardPlan {
   Geometry g{};
@@ -111,6 +113,35 @@ struct ForwardPlan {
 // The plan of B items of T frames.  Always filled (the size queries answer for
 // shapes no forward runs); returns why a forward rejects the shape, else nullptr.
 const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, ForwardPlan* p);
+
+// ---- one Winograd conv launch -----------------------------------------------
+// What launch_conv3x3_wino, launch_block1_wino and launch_conv3x3_wino43
+// launch for a layer: the item shape, the persistent grid, the item order and
+// the split of a batch into launches of whole clips.  Every shape performs
+// the same operations in the same order per (tile, channel), so none of this
+// changes an output.  No device: sedx_conv_launch_plan answers for any CU count.
+enum WinoFamily { WINO_F23 = SEDX_CONV_F23, WINO_F23_BLOCK1 = SEDX_CONV_F23_BLOCK1, WINO_F43 = SEDX_CONV_F43 };
+struct ConvLaunch {
+  const char* reject = nullptr;   // why no launch runs this shape (hipErrorInvalidValue), else nullptr
+  // 32-bit offsets in the kernels: a batch runs as launches of at most
+  // clips_per_launch whole clips (same per-clip work); this plan is the
+  // first one's, of `clips` = min(B, clips_per_launch) clips
+  int64_t clips_per_launch = 0, in_clip = 0, out_clip = 0;   // in, out: floats per clip
+  int clips = 0, nitems = 0, nwg = 0;   // items (padded to the XCD decode), persistent workgroups
+  // the item: TG tile groups x NT channel tiles.  F(2x2): groups of 32 tiles,
+  // tiles of 32 channels; F(4x4): groups of 16 tiles, NT 4 (64 channels) or 1 (16)
+  int TG = 0, NT = 0;
+  int tb_per_clip = 0, ngroups = 0;   // tile blocks of a clip, channel groups
+  bool claim = false;                 // F(4x4): workgroups claim items from the counters
+  int order2d = 0;                    // channel groups per L2 round (0: tile block major; -1: block 1's contiguous order)
+};
+// order: SEDX_TUNE_WINO_ORDER; nt_force: launch_conv3x3_wino43's; sched:
+// claim counters were passed.  F(2x2) block 1 takes only B, T and c4.
+ConvLaunch plan_conv_launch(WinoFamily family, int ncu, int64_t B, int T, int F, int Cin, int Cout, int epi, int order,
+                            bool c4, int nt_force, bool sched);
+// the Winograd launcher of stage 2 + i of a forward plan; false: the exact or
+// x3 launchers run it (they keep their own shape choice)
+bool conv_launch_family(const ForwardPlan& p, int i, WinoFamily* family);
 
 // ---- windowed drivers (windows.cpp) ------------------------------------------
 // loop control of predict.py:297-338 / main_strong.py:786-832: the sample

@@ -22,7 +22,8 @@
 // the host side of the contracts, plain C++: weights.h (the constants the
 // packing shares with the kernels, DevWeights, every packed layout) and
 // plan.h (ConvEpi, CONV_SCHED_INTS, block1_pad_floats,
-// gru_coop_workspace_bytes, align256, the forward plan, the window drivers' plans)
+// gru_coop_workspace_bytes, align256, the forward plan, the Winograd launch
+// plan, the window drivers' plans)
 #include "plan.h"
 #include "weights.h"
 
@@ -124,7 +125,7 @@ void launch_conv3x3_wino(const float* in, int B, int T, int F, int Cin, int Cout
 // from pack_conv_wino43 (weights.cpp; 2 Cin Cout 36 floats: the 64- and the
 // 16-channel item packs); nt_force: 0 = the launcher's choice of item shape, 4 =
 // 64-channel items, 1 = 16-channel items of 32 tiles, 2 = 16-channel items of
-// 16 tiles (F = 16 / 8, c4 only) — A/B and tests, all bit-identical; pixels outside the clip are
+// 16 tiles (F = 16 / 8, c4 only) — tools/wino43_bench.cpp's A/B, all bit-identical; pixels outside the clip are
 // zero-filled by the buffer DMA's range check (no zero block); trash >= 64 x
 // 128 floats of device scratch for the out-of-range epilogue stores.
 // c4: input and output in the chunk-of-4 layout [B][C/4][T][F][4] (the
@@ -246,6 +247,21 @@ inline LaunchInfo launch_info(const void* kernel, int block_threads, size_t dyn_
   li.ok = true;
   cache[key] = li;
   return li;
+}
+
+// The current device's CU count, queried once per device (the launchers size
+// their grids by it on every launch).  256 when the query fails: launch_info
+// then refuses the launch.
+inline int device_cus() {
+  static std::mutex mu;
+  static std::map<int, int> cache;
+  int dev = 0, ncu = 256;
+  if (hipGetDevice(&dev) != hipSuccess) return ncu;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = cache.find(dev);
+  if (it != cache.end()) return it->second;
+  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 1) return 256;
+  return cache[dev] = ncu;
 }
 
 // LDS-DMA of 16 B per lane: LDS[m0 + lane * 16] = *src.  Inline asm, so the

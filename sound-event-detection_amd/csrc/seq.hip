@@ -182,8 +182,7 @@ __global__ __launch_bounds__(64 * KS) void linear_small_kernel(const float* __re
 void launch_linear(const float* A, int M, int K, const float* W, int N, const float* bias,
                    float* C, int act, hipStream_t s) {
   dim3 grid((M + 127) / 128, N / 64);
-  int dev = 0, ncu = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+  const int ncu = device_cus();
   const dim3 g2((M + 31) / 32, N / 32);
   if (N <= 64 && act == 0 && K % 256 == 0 && N % 32 == 0)   // the head projection, every M
     return launch_kernel(linear_small_kernel<0, 4>, g2, 256, s, A, M, K, W, N, bias, C);

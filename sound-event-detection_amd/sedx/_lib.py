@@ -25,7 +25,7 @@ EXPORTS = ['sedx_create', 'sedx_destroy', 'sedx_last_error', 'sedx_version', 'se
            'sedx_forward_i16', 'sedx_wav_parse', 'sedx_wav_decode_mono', 'sedx_resample_size',
            'sedx_resample_workspace_size', 'sedx_resample', 'sedx_gamma_workspace_size',
            'sedx_set_tuning', 'sedx_set_capture', 'sedx_window_starts', 'sedx_merge_host', 'sedx_check_error',
-           'sedx_abi_version']
+           'sedx_abi_version', 'sedx_conv_launch_plan']
 TUNE_GRU_KERNEL, TUNE_GRU_HANDOFF, TUNE_WINO_BLOCK1, TUNE_MEL_MFMA, TUNE_GRU_SPIN, TUNE_WINO_ORDER = 0, 1, 2, 3, 4, 5
 TUNE_GAMMA_SPEC = 6
 TUNE_WINO_F43 = 7
@@ -64,6 +64,16 @@ def window_spec(sample_duration, overlap_value, driver='predict', overlap=True, 
     return SedxWindowSpec(DRIVER[driver], int(bool(overlap)), int(sample_duration), int(bool(vote)),
                           float(overlap_value),
                           float(audio_duration) if audio_duration is not None else 0.0)
+
+
+class SedxConvLaunch(ctypes.Structure):
+    """sedx_conv_launch: one conv launch of stages 2-8 (sedx_conv_launch_plan)."""
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        'stage', 'family', 'T', 'F', 'cin', 'cout', 'epi', 'clips', 'tg', 'nt', 'c4', 'tb_per_clip', 'ngroups',
+        'nitems', 'nwg', 'claim', 'order2d')] + [('clips_per_launch', ctypes.c_int64)]
+
+
+CONV_FAMILY = {'exact': 0, 'x3': 1, 'f23': 2, 'f23_block1': 3, 'f43': 4}
 
 
 class SedxConfig(ctypes.Structure):
@@ -106,6 +116,7 @@ def lib():
         'sedx_finalize_weights': ([P], I32),
         'sedx_output_geometry': ([P, I64, PI64, PI64], I32),
         'sedx_workspace_size': ([P, I64, I64, PSZ], I32),
+        'sedx_conv_launch_plan': ([P, I64, I64, I32, ctypes.POINTER(SedxConvLaunch), I32, ctypes.POINTER(I32)], I32),
         'sedx_forward': ([P, P, I64, I64, P, P, P, P, SZ, P], I32),
         'sedx_forward_features': ([P, P, I64, I64, P, P, P, P, SZ, P], I32),
         'sedx_forward_i16': ([P, P, I64, I64, P, P, P, P, SZ, P], I32),

@@ -15,7 +15,11 @@
 //  * the forward and window plans (csrc/plan.cpp): over models, precisions,
 //    knobs, batch sizes and lengths, every workspace region aligned, disjoint
 //    and large enough for what its launch writes by the contracts of
-//    sedx_internal.h, and the kernel choices against literal tables.
+//    sedx_internal.h, and the kernel choices against literal tables;
+//  * the Winograd conv launch plan (plan_conv_launch): over families, layers,
+//    batch sizes, lengths, CU counts and knobs, every launch of a split batch
+//    inside the kernels' 32-bit offsets, the grid and the item order within
+//    what the item decode assumes, and every refusal an expected one.
 // Any memory error, undefined behaviour or failed check aborts the process
 // (non-zero exit).
 #include <cmath>
@@ -711,6 +715,53 @@ int check_plans() {
       }
   return n;
 }
+
+// plan_conv_launch walked the way the launchers walk it (one plan per launch
+// of whole clips), against what the kernels' item decode and 32-bit offsets assume
+int check_launch_plans() {
+  struct Layer { int F, cin, cout, epi; };
+  static const Layer layers[7] = {{64, 64, 64, EPI_POOL2},   {32, 64, 128, EPI_STORE},  {32, 128, 128, EPI_POOL2},
+                                  {16, 128, 256, EPI_STORE}, {16, 256, 256, EPI_POOL2}, {8, 256, 512, EPI_STORE},
+                                  {8, 512, 512, EPI_FMEAN}};
+  int n = 0;
+  for (WinoFamily fam : {WINO_F23, WINO_F23_BLOCK1, WINO_F43})
+    for (int li = 0; li < (fam == WINO_F23_BLOCK1 ? 1 : 7); ++li)
+      for (int64_t B : {1, 2, 3, 7, 8, 9, 31, 32, 130, 131, 523, 524, 600})
+        for (int T : {1, 2, 3, 8, 9, 64, 136, 1001})
+          for (int ncu : {1, 7, 8, 64, 256, 304})
+            for (int order = 0; order < 3; ++order)
+              for (int c4 = 0; c4 < 2; ++c4)
+                for (int ntf : {0, 1, 2, 4}) {
+                  const Layer& l = layers[li];
+                  const bool f43 = fam == WINO_F43, sched = B >= 8;
+                  const char* want = fam == WINO_F23_BLOCK1 && T < 2                              ? "empty batch or clip"
+                                     : f43 && ntf == 2 && !(c4 && (l.F == 16 || l.F == 8))       ? "16-tile items"
+                                     : l.epi == EPI_POOL2 && T < 2                                ? "no tile row"
+                                                                                                  : nullptr;
+                  int64_t b0 = 0;
+                  do {
+                    const ConvLaunch p = plan_conv_launch(fam, ncu, B - b0, T, l.F, l.cin, l.cout, l.epi, order, c4 != 0, ntf, sched);
+                    CHECK((p.reject == nullptr) == (want == nullptr), "family %d layer %d B %lld T %d ncu %d: %s", fam, li,
+                          (long long)B, T, ncu, p.reject ? p.reject : "accepted");
+                    if (p.reject) {
+                      CHECK(std::strstr(p.reject, want) != nullptr && b0 == 0, "reason '%s' at clip %lld", p.reject, (long long)b0);
+                      break;
+                    }
+                    CHECK(p.clips_per_launch >= 1 && p.clips >= 1 && p.clips == std::min(B - b0, p.clips_per_launch), "clips %d", p.clips);
+                    const int64_t in = (int64_t)p.clips * T * (fam == WINO_F23_BLOCK1 ? 64 : l.F * l.cin);
+                    CHECK(p.in_clip * p.clips == in && (f43 ? 4 * in : in) < INT32_MAX, "family %d: %lld input floats in one launch", fam, (long long)in);
+                    CHECK(p.nwg >= 1 && p.nwg <= p.nitems && p.nwg % 8 == 0, "nwg %d of %d items", p.nwg, p.nitems);
+                    CHECK(p.order2d == 0 || p.order2d == -1 || (p.order2d > 0 && p.ngroups % p.order2d == 0), "order2d %d of %d groups", p.order2d, p.ngroups);
+                    CHECK(!p.claim || (f43 && sched && p.nwg == ncu / 8 * 8), "claim with %d workgroups on %d CUs", p.nwg, ncu);
+                    CHECK(f43 ? (p.NT == 4 && p.TG == 2) || (p.NT == 1 && (p.TG == 2 || (p.TG == 1 && c4 && l.F <= 16)))
+                              : p.TG >= 1 && p.TG <= 4 && (p.NT == 1 || p.NT == 2), "item %d x %d", p.TG, p.NT);
+                    CHECK(p.tb_per_clip >= 1 && p.ngroups >= 1 && (int64_t)p.nitems >= (int64_t)p.clips * p.tb_per_clip * p.ngroups, "items");
+                    b0 += p.clips;
+                    ++n;
+                  } while (b0 < B);
+                }
+  return n;
+}
 }  // namespace
 
 int main() {
@@ -779,7 +830,8 @@ int main() {
   }
   const int weight_checks = check_weights();
   const int plan_checks = check_plans();
-  std::printf("asan_driver: %d wav_parse cases (%d accepted), %d vad cases, %d weight-pack checks, %d plan checks: "
-              "clean\n", cases, ok, vad_cases, weight_checks, plan_checks);
+  const int launch_checks = check_launch_plans();
+  std::printf("asan_driver: %d wav_parse cases (%d accepted), %d vad cases, %d weight-pack checks, %d plan checks, "
+              "%d conv launch plans: clean\n", cases, ok, vad_cases, weight_checks, plan_checks, launch_checks);
   return 0;
 }

@@ -40,6 +40,7 @@ import numpy as np
 import pytest
 import torch
 
+import launch_plan as LP
 from oracle import layer_refs as R
 
 pytestmark = pytest.mark.gpu
@@ -312,7 +313,7 @@ def test_stage_chain(B, T, form):
     the GRU model; the sequence and head steps on both.  (72, 136) runs every
     F(4x4,3x3) launch with item claims."""
     if form == ('winograd', 2) and (B, T) == (72, 136):
-        assert [R.w43_regime(l, B, T, ncu()) for l in range(7)] == ['nt4_claim'] * 7
+        assert [LP.w43_regime(l, B, T, ncu()) for l in range(7)] == ['nt4_claim'] * 7
     ck = Checks('chain', form)
     f = feats(B, T)
     x = torch.from_numpy(f).cuda()
@@ -366,7 +367,21 @@ SWEEP_IDS = ['B%d-T%d..B%d-T%d' % (g[0] + g[-1]) for g in SWEEP_GROUPS]
 def test_sweep_covers_every_w43_regime():
     """Over the sweep's shapes each of the seven F(4x4,3x3) launches runs in
     every regime it can reach on this device."""
-    assert R.w43_missing(R.SWEEP_SHAPES, ncu()) == []
+    assert LP.w43_missing(R.SWEEP_SHAPES, ncu()) == []
+
+
+def test_launch_plan_of_the_device_is_the_plan_of_its_cu_count():
+    """sedx_conv_launch_plan asked for the handle's device (ncu 0: the CU
+    count the launchers themselves read) answers what it answers for that CU
+    count given as a number, the form the CPU tests use; on a 256-CU device
+    the three shapes run the regimes tests/test_layer_refs_cpu.py lists."""
+    for B, T in ((1, 64), (8, 136), (16, 37)):
+        st, rows = LP.conv_launches(B, T, 0)
+        assert st == 0 and len(rows) == 7 and all(r['nwg'] > 0 for r in rows)
+        assert (st, rows) == LP.conv_launches(B, T, ncu()), (B, T)
+    if ncu() == 256:
+        assert [LP.w43_regime(l, 1, 64, 0) for l in range(7)] == ['nt1_tg2'] * 3 + ['nt1_tg1'] * 4
+        assert LP.w43_regime(3, 8, 136, 0) == 'nt1_tg2' and LP.w43_regime(3, 16, 37, 0) == 'nt1_tg2'
 
 
 @pytest.mark.parametrize('group', SWEEP_GROUPS, ids=SWEEP_IDS)
@@ -449,8 +464,8 @@ def test_features_b32_t994_claims():
     their items.  Clips 0, 13, 31 against the float64 chain, and bit for bit
     against the same three clips as a B = 3 batch (static item order)."""
     B, T, form, pick = 32, 994, ('winograd', 2), [0, 13, 31]
-    assert [R.w43_regime(l, B, T, ncu()) for l in range(5)] == ['nt4_claim'] * 5
-    assert all(R.w43_regime(l, 3, T, ncu()) != 'nt4_claim' for l in range(7))
+    assert [LP.w43_regime(l, B, T, ncu()) for l in range(5)] == ['nt4_claim'] * 5
+    assert all(LP.w43_regime(l, 3, T, ncu()) != 'nt4_claim' for l in range(7))
     f = R.features(B, T, seed=994)
     m = model(GRU, form)
     big = run(m, GRU, torch.from_numpy(f).cuda())

@@ -238,6 +238,47 @@ def test_workspace_sizes_against_the_recorded_grid(golden_dir):
         L.sedx_destroy(h)
 
 
+def test_conv_launch_plan_against_the_recorded_launches(golden_dir):
+    """sedx_conv_launch_plan (no GPU) equals, field by field, what the conv
+    launchers decided before the decisions moved into the plan
+    (tools/make_golden_conv_launches.py, recorded from an instrumented build
+    of that commit): default tuning at 256 CUs over the GPU sweep's shapes, the
+    bench shapes and two batches that split stage 2; SEDX_TUNE_WINO_F43 x
+    _BLOCK1 x _ORDER at 256 CUs and the default at 64 and 304 CUs over 16
+    shapes.  Launches of the exact launcher (block 1 with
+    SEDX_TUNE_WINO_BLOCK1 0) were not recorded: their rows carry the layer only."""
+    import launch_plan as LP
+    from sedx import _lib
+    g = json.load(open(os.path.join(golden_dir, 'conv_launches.json')))
+    assert len(g['cases']) == 143 + 27 * 16 + 2 * 16
+    for b1, f43, order, ncu, B, T, ids in g['cases']:
+        st, rows = LP.conv_launches(B, T, ncu, [(_lib.TUNE_WINO_BLOCK1, b1), (_lib.TUNE_WINO_F43, f43),
+                                                (_lib.TUNE_WINO_ORDER, order)])
+        assert st == 0
+        exact = [r for r in rows if r['family'] == _lib.CONV_FAMILY['exact']]
+        assert [r['stage'] for r in exact] == ([2] if b1 == 0 else []) and all(r['nwg'] == 0 for r in exact)
+        got = [[r[c] for c in g['columns']] for r in rows if r not in exact]
+        assert got == [g['rows'][i] for i in ids], (b1, f43, order, ncu, B, T)
+
+
+def test_conv_launch_plan_refusals():
+    """A shape the forward refuses (no frame left after the third pool) and a
+    row buffer that is too small are SEDX_EINVAL; the latter still reports the
+    row count."""
+    import ctypes
+    import launch_plan as LP
+    from sedx import _lib
+    assert LP.conv_launches(2, 7, 256)[0] == 1                       # T3 = 0
+    st, rows = LP.conv_launches(2, 8, 256)
+    assert st == 0 and len(rows) == 7
+    st, rows = LP.conv_launches(2, 8, 256, capacity=6)
+    assert st == 1 and len(rows) == 6
+    n = ctypes.c_int32()
+    assert _lib.lib().sedx_conv_launch_plan(LP._h(), 200, 1000 * 160, 256, None, 0, ctypes.byref(n)) == 1
+    assert n.value == 8                                              # stage 2 splits under F(4x4)'s byte limit
+    assert b'capacity' in _lib.lib().sedx_last_error(LP._h())
+
+
 def test_invalid_setter_values_are_einval_before_any_device_call():
     """sedx_set_pipelined / sedx_set_profiling range-check `on` before they
     touch HIP: without a GPU an invalid value is SEDX_EINVAL (1), not the

@@ -1,11 +1,13 @@
 """oracle/layer_refs.py against the oracle it is built from (CPU only): the
 float64 step chain agrees with the fp32 ``O.forward``, composes to the
-oracle's own straight call bit for bit, its layout helpers round-trip, and
-``w43_regime`` gives the regimes the launcher is known to take."""
+oracle's own straight call bit for bit and its layout helpers round-trip; and
+the library's launch plan (tests/launch_plan.py) gives the F(4x4,3x3) regimes
+the sweep's shapes are chosen for."""
 import numpy as np
 import pytest
 import torch
 
+import launch_plan as LP
 from oracle import layer_refs as R
 from oracle import sed_oracle as O
 
@@ -118,29 +120,29 @@ def test_chain_conv1_fp32():
 
 def test_w43_regimes():
     ncu = 256
-    head = [R.w43_regime(l, 32, 1001, ncu) for l in range(7)]
+    head = [LP.w43_regime(l, 32, 1001, ncu) for l in range(7)]
     assert head == ['nt4_claim'] * 5 + ['nt4_static'] * 2, head      # blocks 1-3 claim, block 4: 512 items
-    assert R.w43_launch(6, 32, 1001, ncu)['nitems'] == 512
-    assert all(not R.w43_launch(l, 4, 1001, ncu)['claim'] for l in range(7))
-    assert [R.w43_regime(l, 32, 994, ncu) for l in range(5)] == ['nt4_claim'] * 5
+    assert LP.w43_launch(6, 32, 1001, ncu)['nitems'] == 512
+    assert all(not LP.w43_launch(l, 4, 1001, ncu)['claim'] for l in range(7))
+    assert [LP.w43_regime(l, 32, 994, ncu) for l in range(5)] == ['nt4_claim'] * 5
     # B = 72, T = 136: every launch claims (1224 / 720 / 576 / 576 items against 512)
-    assert [R.w43_launch(l, 72, 136, ncu)['nitems'] for l in range(7)] == [1224, 720, 720, 576, 576, 576, 576]
-    assert all(R.w43_regime(l, 72, 136, ncu) == 'nt4_claim' for l in range(7))
-    assert all(R.w43_launch(l, 72, 136, ncu)['nwg'] == 256 for l in range(7))
+    assert [LP.w43_launch(l, 72, 136, ncu)['nitems'] for l in range(7)] == [1224, 720, 720, 576, 576, 576, 576]
+    assert all(LP.w43_regime(l, 72, 136, ncu) == 'nt4_claim' for l in range(7))
+    assert all(LP.w43_launch(l, 72, 136, ncu)['nwg'] == 256 for l in range(7))
     # one clip: 16-channel items, of 16 tiles in the F = 16 / 8 layers
-    assert [R.w43_regime(l, 1, 64, ncu) for l in range(7)] == ['nt1_tg2'] * 3 + ['nt1_tg1'] * 4
+    assert [LP.w43_regime(l, 1, 64, ncu) for l in range(7)] == ['nt1_tg2'] * 3 + ['nt1_tg1'] * 4
     # the 32-tile 16-channel regime of blocks 3-4 needs exactly 16 and 8 tile blocks
-    assert R.w43_regime(3, 16, 37, ncu) == 'nt1_tg2' and R.w43_regime(3, 8, 136, ncu) == 'nt1_tg2'
-    assert R.w43_regime(5, 8, 64, ncu) == 'nt1_tg2' and R.w43_regime(5, 16, 64, ncu) == 'nt4_static'
+    assert LP.w43_regime(3, 16, 37, ncu) == 'nt1_tg2' and LP.w43_regime(3, 8, 136, ncu) == 'nt1_tg2'
+    assert LP.w43_regime(5, 8, 64, ncu) == 'nt1_tg2' and LP.w43_regime(5, 16, 64, ncu) == 'nt4_static'
     # below 8 clips the launches get no claim counters, whatever the item count
-    assert R.w43_launch(0, 7, 1001, ncu)['nitems'] > 512 and R.w43_regime(0, 7, 1001, ncu) == 'nt4_static'
+    assert LP.w43_launch(0, 7, 1001, ncu)['nitems'] > 512 and LP.w43_regime(0, 7, 1001, ncu) == 'nt4_static'
 
 
 def test_sweep_covers_every_regime():
     """The shape list of the GPU sweep runs each of the seven F(4x4,3x3)
     launches in every regime it can reach (256 CUs)."""
-    assert R.w43_missing(R.SWEEP_SHAPES, 256) == []
+    assert LP.w43_missing(R.SWEEP_SHAPES, 256) == []
     assert len(set(R.SWEEP_SHAPES)) == len(R.SWEEP_SHAPES)
     # and the check can fail: without the B >= 8 shapes nothing claims
     small = [s for s in R.SWEEP_SHAPES if s[0] < 8]
-    assert (0, 'nt4_claim') in R.w43_missing(small, 256)
+    assert (0, 'nt4_claim') in LP.w43_missing(small, 256)

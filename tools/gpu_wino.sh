@@ -1,6 +1,6 @@
 #!/bin/bash
 # Winograd conv check + timing (tools/wino_bench.cpp).  BUILD=1 (here, CPU):
-# tools/prev/wb_full from the tree's conv.hip + conv_wino.hip + the host packers (weights.cpp); RUN=1 (GPU
+# tools/prev/wb_full from the tree's conv.hip + conv_wino.hip + the launch plan (plan.cpp, with windows.cpp) + the host packers (weights.cpp); RUN=1 (GPU
 # box): run it at each of BATCHES (default 32 4 1), optional PMC pass.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out tools/prev
@@ -8,10 +8,10 @@ HIPCC="/opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -Wno-unused-resu
 C=sound-event-detection_amd/csrc
 O=tools/prev
 if [ -n "$BUILD" ]; then
-  $HIPCC -o $O/wb_full tools/wino_bench.cpp $C/conv.hip $C/conv_wino.hip $C/weights.cpp $C/gamma_weights.cpp || exit 1
+  $HIPCC -o $O/wb_full tools/wino_bench.cpp $C/conv.hip $C/conv_wino.hip $C/plan.cpp $C/windows.cpp $C/weights.cpp $C/gamma_weights.cpp || exit 1
   # VARIANT_FLAGS: "name:-DFLAG=1,-DOTHER name2:..." extra builds
-  for vf in $VARIANT_FLAGS; do n=${vf%%:*}; f=${vf#*:}; $HIPCC ${f//,/ } -o $O/wb_$n tools/wino_bench.cpp $C/conv.hip $C/conv_wino.hip $C/weights.cpp $C/gamma_weights.cpp || exit 1; done
-  for nb in $NBUFS; do $HIPCC -DSEDX_WINO_NBUF=$nb -o $O/wb_nb$nb tools/wino_bench.cpp $C/conv.hip $C/conv_wino.hip $C/weights.cpp $C/gamma_weights.cpp || exit 1; done
+  for vf in $VARIANT_FLAGS; do n=${vf%%:*}; f=${vf#*:}; $HIPCC ${f//,/ } -o $O/wb_$n tools/wino_bench.cpp $C/conv.hip $C/conv_wino.hip $C/plan.cpp $C/windows.cpp $C/weights.cpp $C/gamma_weights.cpp || exit 1; done
+  for nb in $NBUFS; do $HIPCC -DSEDX_WINO_NBUF=$nb -o $O/wb_nb$nb tools/wino_bench.cpp $C/conv.hip $C/conv_wino.hip $C/plan.cpp $C/windows.cpp $C/weights.cpp $C/gamma_weights.cpp || exit 1; done
 fi
 [ -n "$RUN" ] || exit 0
 export TMPDIR=/tmp

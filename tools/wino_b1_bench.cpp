@@ -4,8 +4,8 @@
 // time per launch, an output checksum (a stamped build must match the plain
 // one), and — in a SEDX_WINO_STAMPS build — the per-phase s_memtime split of
 // the waves' cycles.  Ablation builds (SEDX_WINO_ABL) give wrong outputs and
-// are timed only.  Links conv_wino.hip and the host packers (csrc/weights.cpp,
-// csrc/gamma_weights.cpp).
+// are timed only.  Links conv_wino.hip, the launch plan (csrc/plan.cpp, csrc/windows.cpp) and the host
+// packers (csrc/weights.cpp, csrc/gamma_weights.cpp).
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
