@@ -62,8 +62,20 @@ typedef enum {
    * and a 144-wide head; framewise padded to a multiple of 100 with its last
    * frame (:1359-1360, :1571-1572).  fp32 in every precision mode. */
   SEDX_MODEL_CONFORMER_FRAMEATT = 7,    /* Cnn_9layers_Conformer_FrameAtt  :1189-1410: AttBlock(144, 25) */
-  SEDX_MODEL_CONFORMER_FRAMEAVG = 8     /* Cnn_9layers_Conformer_FrameAvg  :1412-1625: fc(144), mean over
+  SEDX_MODEL_CONFORMER_FRAMEAVG = 8,    /* Cnn_9layers_Conformer_FrameAvg  :1412-1625: fc(144), mean over
                                            the padded frames (:1575)                                   */
+  /* the 14-layer trunk: blocks 1-3 as above, block 4 pooled 2x2, block 5
+   * (512 -> 1024, pooled) and block 6 (1024 -> 2048, frequency mean of its 2
+   * bins): T/32 sequence frames of 2048 channels, x32 frame repeat, framewise
+   * padded to a multiple of 100 with its last frame unless it has 1000 frames.
+   * AttBlock(2048, 25).  feature_type must be LOGMEL.  Blocks 5-6, block 4's
+   * conv2, the sequence layer and the head are fp32 in every precision mode
+   * (sedx_set_precision and the Winograd knobs select the arithmetic of
+   * blocks 1-3 and block 4's conv1 only). */
+  /* 9 is not assigned: callers written against the nine 9-layer models probe it
+   * as the first unknown model_type, and sedx_create keeps answering SEDX_EINVAL */
+  SEDX_MODEL_GRU14_FRAMEATT = 10,         /* Cnn_14layers_Gru_FrameAtt  :691-791: nn.GRU(2048, 1024, bidirectional) */
+  SEDX_MODEL_TRANSFORMER14_FRAMEATT = 11  /* Cnn_14layers_Transformer_FrameAtt  :1080-1184: MultiHead(8, 2048, 64, 64) */
 } sedx_model;
 
 typedef enum { SEDX_FEATURE_LOGMEL = 0, SEDX_FEATURE_GAMMA = 1 } sedx_feature;
@@ -88,7 +100,8 @@ typedef struct sedx_handle sedx_handle;
 /* Model construction: replaces Model(...) (pytorch/models.py:565-623 / :982-1024
  * and the constructors of the other sedx_model values).  feature_type GAMMA is
  * Cnn_9layers_Gru_FrameAtt's alone (Cnn_9layers_Gru_FrameAvg takes the argument
- * and ignores it, :512-518); any other model_type with it is SEDX_EINVAL. */
+ * and ignores it, :512-518); any other model_type with it is SEDX_EINVAL
+ * (the two 14-layer models included). */
 sedx_status sedx_create(const sedx_config* cfg, int device, sedx_handle** out);
 void sedx_destroy(sedx_handle* h);
 const char* sedx_last_error(const sedx_handle* h);
@@ -387,8 +400,13 @@ sedx_status sedx_set_precision(sedx_handle* h, int32_t mode);
  *                         forward's outputs into NaN and is reported by
  *                         sedx_check_error (tests force it with 0: every
  *                         step that would wait fails, whether or not its data
- *                         has arrived).
- *  SEDX_TUNE_GAMMA_SPEC   (gammatone, nfft 2048) 0 (default): the spectrum
+ *                         has arrived).  The 14-layer GRU model's recurrence
+ *                         (hidden size 1024) is one launch per time step
+ *                         with no spins: SEDX_TUNE_GRU_SPIN,
+ *                         SEDX_TUNE_GRU_KERNEL and SEDX_TUNE_GRU_HANDOFF are
+ *                         accepted and ignored on its handles, and
+ *                         sedx_check_error has nothing to report for them.
+ *  SEDX_TUNE_GAMMA_SPEC  (gammatone, nfft 2048) 0 (default): the spectrum
  *                         as a 256-thread Stockham FFT per frame; 1: one
  *                         wave per frame (16 x 16 x 4 four-step in registers,
  *                         wave-local transposes).  Same int16 codes in every
@@ -493,6 +511,14 @@ sedx_status sedx_set_pipelined(sedx_handle* h, int32_t on);
  *   21 + 4b + j block b = 0..2: j = 0 after ffn1, 1 after mhsa, 2 after the
  *               conv module, 3 the block's output (after ffn2 and its norm);
  *               32 is the same tensor as 9
+ * 14-layer models: 0 and 2..7 as above; 8 is block 4's pooled output
+ * [items][T/16][4][512], 9 the GRU / MHA output [items][T/32][2048], and
+ *   40  conv1 of block 5              [items][T/16][4][1024]
+ *   41  block 5 output (pooled)       [items][T/32][2][1024]
+ *   42  conv1 of block 6              [items][T/32][2][2048]
+ *   43  block 6 + freq mean           [items][T/32][2048] (the sequence input)
+ * Their timed stage 8 spans block 4's conv2 and the four launches of blocks
+ * 5-6; stage 9 is the sequence layer alone.
  * stage < 0 or d_buf == NULL switches capture off. */
 sedx_status sedx_set_capture(sedx_handle* h, int32_t stage, float* d_buf, size_t bytes);
 sedx_status sedx_set_profiling(sedx_handle* h, int32_t on);

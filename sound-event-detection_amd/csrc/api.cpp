@@ -184,6 +184,9 @@ sedx_status query_geometry(const sedx_handle* h, int64_t L_or_T, Geometry* g) {
   *g = geometry_from_T(*h, h->cfg.feature_type == SEDX_FEATURE_GAMMA ? L_or_T : conv_T(*h, L_or_T));
   if (seq_too_long(*h, g->T3))
     return fail(h, SEDX_EINVAL, "%lld sequence frames: the Conformer encoder holds %d", (long long)g->T3, CF_MAX_T);
+  // the 14-layer models have no output below 32 frames (the reference's fifth
+  // avg_pool2d raises): the queries reject what the forward rejects
+  if (h->depth == 14 && g->Ts < 1) return fail(h, SEDX_EINVAL, "input too short for the 5 pooling stages");
   return SEDX_OK;
 }
 
@@ -263,7 +266,7 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
   const Tuning& t = h->tune;
   const Geometry& g = p.g;
   const int64_t B = p.B;
-  const int iB = (int)B, M = p.M, T3 = (int)g.T3;
+  const int iB = (int)B, M = p.M, T3 = (int)g.Ts;   // the sequence's frames (T5 on the 14-layer trunk)
   float* X0 = ws + p.x0.off;
   float* A = ws + p.A.off;
   int* sched = reinterpret_cast<int*>(ws + p.sched.off);
@@ -293,11 +296,21 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
   mark(h, 1, s);
   capture(h, 0, X0, (size_t)B * g.T * 64, s);
   if (!first_early) block1_first();
-  for (int i = 0; i < 7; ++i) {
+  for (int i = 0; i < p.nlayers; ++i) {
     const ConvLayer& c = p.layers[i];
     const int k = i + 1;   // the layer's weights
     float* in = ws + c.in;
     float* out = ws + c.out;
+    if (i >= p.first_deep) {
+      // 14-layer trunk: block 4's pooled conv2 (stage 8, reading block 4 conv1's
+      // layout) and blocks 5-6 (timed inside stage 8; captures 40..43), fp32 in every mode
+      if (i < 7) mark(h, 2 + i, s);
+      const int l = i - p.first_deep;   // the layer's slice of the deep pack (weights.h)
+      launch_conv3x3_deep(in, iB, c.T, c.F, c.cin, c.cout, w.wp[7] + deep_w_off(l), w.cb[7] + deep_b_off(l), out,
+                          c.epi, p.c4 && l == 0, s);
+      capture(h, i < 7 ? 2 + i : 40 + (i - 7), out, (size_t)B * c.To * c.Fo * c.cout, s);
+      continue;
+    }
     int* claim = p.claims ? sched + i * CONV_SCHED_INTS : nullptr;
     mark(h, 2 + i, s);
     // block 1 as one launch: conv1 computed inside conv2's halo staging (the
@@ -331,7 +344,7 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
     h->conv_done_recorded = true;
   }
   const bool x3 = t.precision == SEDX_PRECISION_X3;
-  float* S = ws + p.P.off;                        // [B][T3][512]
+  float* S = ws + p.P.off;                        // [B][T3][512] (14-layer: [B][T5][2048])
   float* G = ws + p.G.off;
   float* Hs = ws + p.Hs.off;
   float* O = ws + p.O.off;
@@ -347,7 +360,17 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
   // the head's input [M][512]: the sequence layer's output, or (no sequence
   // layer: no projection, no recurrence / MHA launch) the stage-8 buffer itself
   const float* HI = h->seq == SEQ_NONE ? S : Hs;
-  if (h->seq == SEQ_CONFORMER) {
+  if (h->depth == 14) {
+    // fp32 in every precision mode: the generic fp32 GEMM at the new widths
+    if (h->seq == SEQ_GRU) {
+      launch_linear(S, M, 2048, w.w_ih, 6144, w.b_ih, G, 0, s);
+      launch_gru1024(G, iB, T3, w.whh, w.bhh, Hs, s);
+    } else {
+      launch_linear(S, M, 2048, w.wqkv, 1536, w.bqkv, G, 0, s);
+      launch_mha(G, iB, T3, O, s);
+      launch_linear(O, M, 512, w.wfc, 2048, w.bfc, Hs, 1, s);
+    }
+  } else if (h->seq == SEQ_CONFORMER) {
     // fp32 in every precision mode; x is updated in place by the residual epilogues
     float* X = ws + p.X.off;
     float* Xn = ws + p.Xn.off;
@@ -408,11 +431,13 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
   // head projection (att|cla rows or fc rows, zero-padded to nac), then its finish
   if (h->seq == SEQ_CONFORMER)
     launch_cf_gemm(HI, M, CF_D, w.wac, h->nac, w.bac, nullptr, LG, CF_EPI_NONE, s);
+  else if (h->depth == 14)
+    launch_linear(HI, M, 2048, w.wac, h->nac, w.bac, LG, 0, s);
   else
     linear(HI, w.wac, w.wac_x3, h->nac, 64, w.bac, LG, 0);
   if (h->head == HEAD_ATT)
     launch_att_head(LG, iB, T3, h->cfg.classes_num, h->nac, (int)g.out_frames, d_fw, d_clip,
-                    h->emb_cla ? d_emb : nullptr, s);
+                    h->emb_cla ? d_emb : nullptr, s, g.rep);
   else
     launch_fc_head(LG, iB, T3, h->cfg.classes_num, h->nac, h->head == HEAD_FC_MAX, d_fw, d_clip, s,
                    (int)g.out_frames);
@@ -458,7 +483,8 @@ sedx_status sedx_set_capture(sedx_handle* h, int32_t stage, float* d_buf, size_t
     return SEDX_OK;
   }
   const bool cf_stage = h->seq == SEQ_CONFORMER && stage >= 20 && stage <= 20 + 4 * CF_BLOCKS;
-  if (stage == 1 || (stage > 9 && !cf_stage)) return fail(h, SEDX_EINVAL, "stage %d cannot be captured", (int)stage);
+  const bool deep_stage = h->depth == 14 && stage >= 40 && stage <= 43;   // blocks 5-6 of the 14-layer trunk
+  if (stage == 1 || (stage > 9 && !cf_stage && !deep_stage)) return fail(h, SEDX_EINVAL, "stage %d cannot be captured", (int)stage);
   h->cap_stage = stage;
   h->cap_buf = d_buf;
   h->cap_bytes = bytes;
@@ -643,7 +669,7 @@ sedx_status sedx_output_geometry(const sedx_handle* h, int64_t L_or_T, int64_t* 
   Geometry g;
   if (sedx_status st = query_geometry(h, L_or_T, &g)) return st;
   *out_frames = g.out_frames;
-  *seq_len = g.T3;
+  *seq_len = g.Ts;
   return SEDX_OK;
 }
 
@@ -670,7 +696,7 @@ sedx_status sedx_conv_launch_plan(const sedx_handle* h, int64_t B, int64_t L_or_
     ncu = device_cus();
   }
   int n = 0;
-  for (int i = 0; i < 7; ++i) {
+  for (int i = 0; i < std::min(7, p.first_deep); ++i) {   // the launches of the 9-layer families (not conv_deep.hip's)
     const ConvLayer& c = p.layers[i];
     sedx_conv_launch r{};
     r.stage = 2 + i;

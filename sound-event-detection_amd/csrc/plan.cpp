@@ -15,12 +15,18 @@ Geometry geometry_from_T(const Model& m, int64_t T) {
   g.T1 = T / 2;
   g.T2 = g.T1 / 2;
   g.T3 = g.T2 / 2;
-  g.fw_len = 8 * g.T3;
+  g.T4 = g.T3 / 2;
+  g.T5 = g.T4 / 2;
+  const bool deep = m.depth == 14;
+  g.Ts = deep ? g.T5 : g.T3;
+  g.rep = deep ? 32 : 8;   // interpolate_ratio (models.py:741, :1133)
+  g.fw_len = g.rep * g.Ts;
   g.out_frames = g.fw_len;
   // pad_framewise_output(roundup) models.py:678-681: Cnn_9layers_Gru_FrameAtt
   // (Cnn_9layers_Gru_FrameAvg returns the 8 T3 frames, :551) and the two
   // Conformer models (:1359-1360, :1571-1572)
-  const bool pad100 = m.cfg.model_type == SEDX_MODEL_GRU_FRAMEATT || m.seq == SEQ_CONFORMER;
+  // and both 14-layer models (:783-784, :1176-1177)
+  const bool pad100 = m.cfg.model_type == SEDX_MODEL_GRU_FRAMEATT || m.seq == SEQ_CONFORMER || deep;
   if (pad100 && g.fw_len != 1000)
     g.out_frames = (g.fw_len % 100 == 0) ? g.fw_len : g.fw_len + 100 - g.fw_len % 100;
   return g;
@@ -35,7 +41,10 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
   const Geometry g = geometry_from_T(m, T);
   p->g = g;
   p->B = B;
-  p->M = (int)(B * g.T3);
+  p->M = (int)(B * g.Ts);
+  const bool deep = m.depth == 14;
+  p->nlayers = deep ? 11 : 7;
+  p->first_deep = deep ? 6 : 7;
   // ---- which kernels ----
   const bool wino = t.precision == SEDX_PRECISION_WINOGRAD, x3 = t.precision == SEDX_PRECISION_X3;
   // Winograd block 1 (SEDX_TUNE_WINO_BLOCK1): 1 = conv1's activation
@@ -71,7 +80,16 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
                                                                          : (size_t)B * T * 64 * 64;
   size_t p_conv = 0;
   const int64_t Ts[4] = {g.T, g.T1, g.T2, g.T3};
-  for (int i = 0; i < 7; ++i) {
+  // 14-layer trunk: block 4's conv2 pools 2x2; block 5 at F = 4, block 6 at F = 2 (its conv2: the mean of 2 bins)
+  for (int i = 6; i < p->nlayers; ++i) {
+    const int blk = (i + 1) / 2, cout = 64 << blk, F = 64 >> blk, last = i == 10, pool = i % 2 == 0 && !last;
+    const int Tl = (int)(blk == 3 ? g.T3 : blk == 4 ? g.T4 : g.T5);
+    p->layers[i] = ConvLayer{Tl, F, i % 2 ? cout / 2 : cout, cout, last ? EPI_FMEAN : pool ? EPI_POOL2 : EPI_STORE,
+                             pool ? Tl / 2 : Tl, last ? 1 : pool ? F / 2 : F, 0, 0, 0};
+    size_t& ext = i % 2 ? a_conv : p_conv;
+    ext = std::max(ext, (size_t)B * p->layers[i].To * p->layers[i].Fo * cout);
+  }
+  for (int i = 0; i < (deep ? 6 : 7); ++i) {
     const int blk = (i + 1) / 2, cout = 64 << blk, Tl = (int)Ts[blk], F = 64 >> blk, pool = i % 2 == 0 && i < 6;
     p->layers[i] = ConvLayer{Tl, F, i == 0 ? 64 : i % 2 ? cout / 2 : cout, cout,
                              i == 6 ? EPI_FMEAN : pool ? EPI_POOL2 : EPI_STORE,
@@ -82,11 +100,11 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
   }
   const size_t M = (size_t)p->M;
   size_t e_head = a0;
-  p->G = take(e_head, M * 1536);
-  p->Hs = take(e_head, M * 512);
+  p->G = take(e_head, M * (deep && m.seq == SEQ_GRU ? 6144 : 1536));
+  p->Hs = take(e_head, M * (deep ? 2048 : 512));
   p->O = take(e_head, M * 512);
   p->LG = take(e_head, M * m.nac);
-  p->gru = take(e_head, gru_coop_workspace_bytes((int)B) / 4);
+  p->gru = take(e_head, deep ? 0 : gru_coop_workspace_bytes((int)B) / 4);   // gru1024.hip: no scratch
   size_t e_a = std::max(a0 + align256(a_conv * 4), e_head);
   if (m.seq == SEQ_CONFORMER) {
     size_t e_cf = a0;
@@ -104,7 +122,7 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
   p->P = take(end, p_conv);
   p->sched = take(end, 7 * CONV_SCHED_INTS);
   p->total_bytes = end;
-  for (int i = 0; i < 7; ++i) {
+  for (int i = 0; i < p->nlayers; ++i) {
     p->layers[i].in = i % 2 ? p->P.off : p->A.off;
     p->layers[i].out = i % 2 ? p->A.off : p->P.off;
   }
@@ -112,6 +130,7 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
   // ---- shapes no forward runs ----
   p->reject[0] = 0;
   if (g.T3 < 1) snprintf(p->reject, sizeof(p->reject), "input too short for the 3 pooling stages");
+  else if (g.Ts < 1) snprintf(p->reject, sizeof(p->reject), "input too short for the 5 pooling stages");
   else if (seq_too_long(m, g.T3))
     snprintf(p->reject, sizeof(p->reject), "%lld sequence frames: the Conformer encoder holds %d", (long long)g.T3,
              CF_MAX_T);
@@ -325,7 +344,7 @@ const char* window_geometry(const Model& m, int64_t L_clip, const sedx_window_sp
       g.w0 = w;
       g.len = len;
       g.g = geometry_from_T(m, conv_T(m, len));
-      if (g.g.T3 < 1) return refuse("window %d too short for the CNN", w, 0, 0);
+      if (g.g.Ts < 1) return refuse("window %d too short for the CNN", w, 0, 0);
       if (seq_too_long(m, g.g.T3))
         return refuse("window %d gives %lld sequence frames: the Conformer encoder holds %d", w, (long long)g.g.T3,
                       CF_MAX_T);

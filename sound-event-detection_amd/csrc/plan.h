@@ -35,8 +35,11 @@ constexpr size_t block1_pad_floats(int B, int T) { return (size_t)B * (T + 2) * 
 constexpr size_t gru_coop_workspace_bytes(int /*B*/) { return 10240 + (size_t)8 * 2 * 32 * 256 * 4; }
 
 // ---- geometry ---------------------------------------------------------------
+// Ts: the sequence's frames (T3 on the 9-layer trunk, T5 on the 14-layer one); rep: frames per sequence frame
 struct Geometry {
   int64_t T, T1, T2, T3, fw_len, out_frames;
+  int64_t T4 = 0, T5 = 0, Ts = 0;
+  int rep = 8;
 };
 inline int64_t conv_T(const Model& m, int64_t L) { return L / m.cfg.hop_size + 1; }
 // the Conformer encoder's positional table has CF_MAX_T rows; the reference
@@ -77,6 +80,7 @@ enum Block1Form {
   B1_CONV1C4_F43,   // launch_conv1_c4 + launch_conv3x3_wino43 in the chunk-of-4 layout
 };
 enum ConvFamily { CONV_EXACT, CONV_X3, CONV_WINO, CONV_WINO43 };   // layers 2-7
+constexpr int MAX_CONV_LAYERS = 11;   // conv launches after block 1's first: 7, or 11 on the 14-layer trunk
 struct ConvLayer {
   int T, F, cin, cout, epi;
   int To, Fo;       // the output's rows and columns ([B][To][Fo][cout]; EPI_FMEAN: Fo = 1)
@@ -86,7 +90,11 @@ struct ConvLayer {
 struct ForwardPlan {
   Geometry g{};
   int64_t B = 0;
-  int M = 0;                       // B * T3: rows of the sequence / head GEMMs
+  int M = 0;                       // B * Ts: rows of the sequence / head GEMMs
+  // conv launches after block 1's first: 7; the 14-layer trunk's 11, of which
+  // layers[first_deep ..] run launch_conv3x3_deep (fp32 in every mode; block
+  // 4's conv2 reads block 4 conv1's layout, then NHWC)
+  int nlayers = 7, first_deep = 7;
   Block1Form block1 = B1_PAD_EXACT;
   ConvFamily family = CONV_EXACT;
   // winograd with F(4x4,3x3): block 1 and blocks 2-4 keep their activations
@@ -96,13 +104,14 @@ struct ForwardPlan {
   // always in x3; F(4x4,3x3) from 8 clips (below: the static item order, same
   // outputs, and no memset: one fill launch less on the one-clip latency path)
   bool claims = false;
-  ConvLayer layers[7] = {};        // stages 2-8
+  ConvLayer layers[MAX_CONV_LAYERS] = {};   // stages 2-8 (and the 14-layer trunk's blocks 5-6)
   // launch_gru_coop's variant (-1: launch_gru, SEDX_GRU_KERNEL_SIMPLE), allow_fast, spread
   int gru_variant = 2;
   bool gru_fast = false, gru_spread = false;
   Region x0, A, P, sched;          // bn0 output, the two activation buffers, 7 x CONV_SCHED_INTS counters
   // inside A once the conv stack is done: G/QKV [M][1536], H [M][512], O
-  // [M][512], the logits [M][nac] and the cooperative recurrence's scratch ...
+  // [M][512], the logits [M][nac] and the cooperative recurrence's scratch
+  // (14-layer: G [M][6144] or QKV [M][1536], H [M][2048], O [M][512], no scratch) ...
   Region G, Hs, O, LG, gru;
   // ... or the Conformer encoder's x [M][144], LayerNorm(x), the hidden [M][576],
   // the attention / depthwise output, r and r_k [3][T3][144] (and LG)

@@ -136,6 +136,14 @@ void launch_conv3x3_wino(const float* in, int B, int T, int F, int Cin, int Cout
 void launch_conv3x3_wino43(const float* in, int B, int T, int F, int Cin, int Cout, const float* U43,
                            const float* bias, float* out, int epi, float* trash, hipStream_t s, int order = 0,
                            bool c4 = false, int nt_force = 0, int* sched = nullptr);
+// The 14-layer trunk's deep layers (conv_deep.hip): the same contract as fp32
+// direct conv, one in-order fma chain per output (order: the file's header),
+// fp32 in every precision mode.  (F, epi) in {(8, POOL2), (4, STORE), (4, POOL2),
+// (2, STORE), (2, FMEAN)}, Cin % 16 == 0, Cout % 128 == 0; wd from
+// pack_conv_deep (weights.cpp).  in_c4: the input in the chunk-of-4 layout
+// [B][Cin/4][T][F][4] (block 4's conv1 under F(4x4,3x3)), else NHWC; the output is NHWC.
+void launch_conv3x3_deep(const float* in, int B, int T, int F, int Cin, int Cout, const float* wd,
+                         const float* bias, float* out, int epi, bool in_c4, hipStream_t s);
 // [B][C/4][T][F][4] -> [B][T][F][C] (stage captures of the C4 layers)
 void launch_c4_to_nhwc(const float* src, int B, int T, int F, int C, float* dst, hipStream_t s);
 // block 1 as one Winograd launch: conv1 (w1 [64][9] folded, b1 [64], ReLU)
@@ -326,12 +334,18 @@ void launch_gru_coop(const float* G, int B, int T, const float* whh, const float
                      void* ws, bool exact, bool allow_fast, int variant, unsigned* host_err, unsigned spin,
                      hipStream_t s, bool spread = false);
 
+// bi-GRU recurrence of the 14-layer model, hidden size 1024 (gru1024.hip): one
+// launch per time step, no spins.  G [B][T][6144] = x W_ih^T + b_ih (both
+// directions, r | z | n each); whh [2][3072][1024]; bhh [2][3072]; H [B][T][2048]
+void launch_gru1024(const float* G, int B, int T, const float* whh, const float* bhh, float* H, hipStream_t s);
+
 // MHA core: QKV [B][T][1536] (q|k|v, head h = cols 64h..64h+63) -> O [B][T][512]
 void launch_mha(const float* QKV, int B, int T, float* O, hipStream_t s);
 
 // AttBlock finish + framewise expansion.  logits [B][T][ldl] (0..C-1 att, C..2C-1 cla)
+// ratio: frames per sequence frame, 8 or 32 (the 14-layer trunk's interpolate_ratio)
 void launch_att_head(const float* logits, int B, int T, int C, int ldl, int out_frames,
-                     float* framewise, float* clipwise, float* emb_cla, hipStream_t s);
+                     float* framewise, float* clipwise, float* emb_cla, hipStream_t s, int ratio = 8);
 // fc head finish (models.py:284-288, :369-373): sigmoid of logits [B][T][ldl]
 // (columns 0..C-1), x8 frame repeat -> framewise [B][8T][C], clipwise [B][C] =
 // the max (max_pool) or the mean over the frames

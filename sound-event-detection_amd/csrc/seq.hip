@@ -7,7 +7,7 @@
 //   mha_kernel      per (clip, head) softmax(q k^T / 8) v, exact two-pass softmax
 //                   (ScaledDotProductAttention, pytorch/models.py:805-820)
 //   att_head_kernel AttBlock finish (clamp, exp, normalise over T, sigmoid,
-//                   weighted sum) + x8 frame repeat + GRU last-frame padding
+//                   weighted sum) + x8 (14-layer trunk: x32) frame repeat + last-frame padding
 //                   (pytorch/models.py:161-175, :84-95, :65-81)
 //   fc_head_kernel  fc head finish of the FrameMax / FrameAvg models (sigmoid,
 //                   x8 frame repeat, max / mean over the frames)
@@ -353,8 +353,9 @@ __device__ __forceinline__ float sum8_(float v) {      // over the 8 lanes of a 
 // One workgroup per clip; the clip's att / cla logits are staged into LDS
 // 128 frames at a time by independent coalesced loads (a 10 s clip's 125
 // frames once, for both passes) instead of per-lane dependent global loads.
+// rsh: log2 of the frame repeat ratio (interpolate_ratio 8, or 32 on the 14-layer trunk).
 __global__ __launch_bounds__(256) void att_head_kernel(const float* __restrict__ logits, int T,
-                                                       int C, int ldl, int out_frames,
+                                                       int C, int ldl, int out_frames, int rsh,
                                                        float* __restrict__ fw,
                                                        float* __restrict__ clip,
                                                        float* __restrict__ emb) {
@@ -406,8 +407,8 @@ __global__ __launch_bounds__(256) void att_head_kernel(const float* __restrict__
         }
       __syncthreads();
       if ((tid & 31) < nc)
-        for (int fr = tid >> 5; fr < nt * 8; fr += 8)
-          fw[((int64_t)b * out_frames + 8 * t0 + fr) * C + c0 + (tid & 31)] = s_cla[fr >> 3][tid & 31];
+        for (int fr = tid >> 5; fr < (nt << rsh); fr += 8)
+          fw[((int64_t)b * out_frames + ((int64_t)t0 << rsh) + fr) * C + c0 + (tid & 31)] = s_cla[fr >> rsh][tid & 31];
       if (emb)
         for (int cc = tid >> 7; cc < nc; cc += 2)
           if ((tid & 127) < nt) emb[((int64_t)b * C + c0 + cc) * T + t0 + (tid & 127)] = s_cla[tid & 127][cc];
@@ -416,17 +417,18 @@ __global__ __launch_bounds__(256) void att_head_kernel(const float* __restrict__
     acc = sum8_(acc);
     if (act && l == 0) clip[(int64_t)b * C + c] = acc;
     __syncthreads();
-    const int npad = out_frames - 8 * T;          // GRU: last frame repeated
+    const int nfr = T << rsh;                     // GRU / 14-layer: last frame repeated past it
     if ((tid & 31) < nc)
-      for (int f = 8 * T + (tid >> 5); f < 8 * T + npad; f += 8)
+      for (int f = nfr + (tid >> 5); f < out_frames; f += 8)
         fw[((int64_t)b * out_frames + f) * C + c0 + (tid & 31)] = s_last[tid & 31];
   }
 }
 
 void launch_att_head(const float* logits, int B, int T, int C, int ldl, int out_frames,
-                     float* framewise, float* clipwise, float* emb_cla, hipStream_t s) {
+                     float* framewise, float* clipwise, float* emb_cla, hipStream_t s, int ratio) {
+  if (ratio != 8 && ratio != 32) return note_launch_error(hipErrorInvalidValue);
   hipLaunchKernelGGL(att_head_kernel, dim3(B), dim3(256), 0, s, logits, T, C, ldl, out_frames,
-                     framewise, clipwise, emb_cla);
+                     ratio == 8 ? 3 : 5, framewise, clipwise, emb_cla);
 }
 
 // ---------------------------------------------------------------------------

@@ -25,6 +25,8 @@ static bool model_parts(int32_t model_type, int* seq, int* head) {
     case SEDX_MODEL_TRANSFORMER_FRAMEAVG: *seq = SEQ_MHA, *head = HEAD_FC_AVG; return true;
     case SEDX_MODEL_CONFORMER_FRAMEATT: *seq = SEQ_CONFORMER, *head = HEAD_ATT; return true;
     case SEDX_MODEL_CONFORMER_FRAMEAVG: *seq = SEQ_CONFORMER, *head = HEAD_FC_AVG; return true;
+    case SEDX_MODEL_GRU14_FRAMEATT: *seq = SEQ_GRU, *head = HEAD_ATT; return true;
+    case SEDX_MODEL_TRANSFORMER14_FRAMEATT: *seq = SEQ_MHA, *head = HEAD_ATT; return true;
     default: return false;
   }
 }
@@ -32,7 +34,8 @@ static bool model_parts(int32_t model_type, int* seq, int* head) {
 bool make_model(const sedx_config& cfg, Model* m) {
   if (!model_parts(cfg.model_type, &m->seq, &m->head)) return false;
   m->cfg = cfg;
-  m->hw = m->seq == SEQ_CONFORMER ? CF_D : 512;
+  m->depth = cfg.model_type == SEDX_MODEL_GRU14_FRAMEATT || cfg.model_type == SEDX_MODEL_TRANSFORMER14_FRAMEATT ? 14 : 9;
+  m->hw = m->depth == 14 ? 2048 : m->seq == SEQ_CONFORMER ? CF_D : 512;
   m->nac = (((m->head == HEAD_ATT ? 2 : 1) * cfg.classes_num + 63) / 64) * 64;
   return true;
 }
@@ -101,7 +104,7 @@ void add_bn(std::map<std::string, std::vector<int64_t>>& e, const std::string& p
   for (const char* s : {".weight", ".bias", ".running_mean", ".running_var"}) e[p + s] = {n};
 }
 
-const int CONV_CH[5] = {1, 64, 128, 256, 512};
+const int CONV_CH[7] = {1, 64, 128, 256, 512, 1024, 2048};   // blocks 5-6: the 14-layer trunk
 
 }  // namespace
 
@@ -112,7 +115,8 @@ std::map<std::string, std::vector<int64_t>> expected_params(const Model& m) {
   e["spectrogram_extractor.stft.conv_imag.weight"] = {K, 1, m.cfg.window_size};
   e["logmel_extractor.melW"] = {K, m.cfg.mel_bins};
   add_bn(e, "bn0", 64);
-  for (int k = 1; k <= 4; ++k) {
+  const bool deep = m.depth == 14;
+  for (int k = 1; k <= (deep ? 6 : 4); ++k) {
     const std::string p = "conv_block" + std::to_string(k);
     e[p + ".conv1.weight"] = {CONV_CH[k], CONV_CH[k - 1], 3, 3};
     e[p + ".conv2.weight"] = {CONV_CH[k], CONV_CH[k], 3, 3};
@@ -131,19 +135,24 @@ std::map<std::string, std::vector<int64_t>> expected_params(const Model& m) {
     e["fc.bias"] = {C};
   }
   if (m.seq == SEQ_GRU) {
+    // nn.GRU(512, 256), or nn.GRU(2048, 1024) on the 14-layer trunk (models.py:727)
+    const int64_t hid = deep ? 1024 : 256;
     for (const char* s : {"", "_reverse"}) {
-      e[std::string("gru.weight_ih_l0") + s] = {768, 512};
-      e[std::string("gru.weight_hh_l0") + s] = {768, 256};
-      e[std::string("gru.bias_ih_l0") + s] = {768};
-      e[std::string("gru.bias_hh_l0") + s] = {768};
+      e[std::string("gru.weight_ih_l0") + s] = {3 * hid, m.hw};
+      e[std::string("gru.weight_hh_l0") + s] = {3 * hid, hid};
+      e[std::string("gru.bias_ih_l0") + s] = {3 * hid};
+      e[std::string("gru.bias_hh_l0") + s] = {3 * hid};
     }
   } else if (m.seq == SEQ_MHA) {
-    for (const char* n : {"w_qs", "w_ks", "w_vs", "fc"}) {
-      e[std::string("multihead.") + n + ".weight"] = {512, 512};
+    // MultiHead(8, 512, 64, 64), or MultiHead(8, 2048, 64, 64) (models.py:1116-1121)
+    for (const char* n : {"w_qs", "w_ks", "w_vs"}) {
+      e[std::string("multihead.") + n + ".weight"] = {512, m.hw};
       e[std::string("multihead.") + n + ".bias"] = {512};
     }
-    e["multihead.layer_norm.weight"] = {512};   // unused in forward (models.py:853-877)
-    e["multihead.layer_norm.bias"] = {512};
+    e["multihead.fc.weight"] = {m.hw, 512};
+    e["multihead.fc.bias"] = {m.hw};
+    e["multihead.layer_norm.weight"] = {m.hw};   // unused in forward (models.py:853-877)
+    e["multihead.layer_norm.bias"] = {m.hw};
   } else if (m.seq == SEQ_CONFORMER) {
     for (const auto& t : CF_TOP) e[t.key] = t.shape;
     for (int b = 0; b < CF_BLOCKS; ++b) {
@@ -365,6 +374,16 @@ void pack_conv_wino43(const double* wf, int Cin, int Cout, float* Up) {
     }
 }
 
+// 14-layer trunk's direct conv (conv_deep.hip): [Cout/32][Cin/16][9][4 q][32 n][4 c]
+// with output channel 32 g + n and input channel 16 chunk + 4 q + c: a wave's
+// 32 output channels read one (chunk, tap, q) as 512 contiguous bytes, lane n
+// its four channels as one 16-byte word (deep_pack_index, weights.h)
+void pack_conv_deep(const double* wf, int Cin, int Cout, float* out) {
+  for (int o = 0; o < Cout; ++o)
+    for (int i = 0; i < Cin; ++i)
+      for (int t = 0; t < 9; ++t) out[deep_pack_index(Cin, o, i, t)] = (float)wf[((size_t)o * Cin + i) * 9 + t];
+}
+
 // head projection [nac][hw] and its bias [nac], rows zero-padded to nac:
 // att | cla (row c, row C + c), or fc
 void pack_head(const Model& m, const Params& P, std::vector<float>* wac, std::vector<float>* bac) {
@@ -457,7 +476,9 @@ sedx_status prepare_weights(const Model& m, const Params& P, DevWeights* Wp, Wei
   }
 
   // ---- conv stack: BN folded into the weights in float64, then each layout ----
-  for (int k = 1; k <= 4; ++k)
+  const bool deep = m.depth == 14;
+  std::vector<float> deep_w, deep_b;
+  for (int k = 1; k <= (deep ? 6 : 4); ++k)
     for (int j = 1; j <= 2; ++j) {
       const std::string p = "conv_block" + std::to_string(k);
       const int cin = (j == 1) ? CONV_CH[k - 1] : CONV_CH[k], cout = CONV_CH[k];
@@ -485,6 +506,21 @@ sedx_status prepare_weights(const Model& m, const Params& P, DevWeights* Wp, Wei
         continue;
       }
       const int idx = 2 * (k - 1) + (j - 1);
+      if (deep && idx >= 7) {
+        // block 4's conv2 (pooled here) and blocks 5-6: the deep pack only, fp32 in
+        // every mode; the five layers back to back behind wp[7] / cb[7] (weights.h)
+        const int l = idx - 7;
+        if (l == 0) deep_w.assign(deep_w_off(DEEP_LAYERS), 0.f), deep_b.assign(deep_b_off(DEEP_LAYERS), 0.f);
+        if (cin != DEEP_CIN[l] || cout != DEEP_COUT[l]) return fail(err, SEDX_EINVAL, "deep layer %d shape", l);
+        pack_conv_deep(wf.data(), cin, cout, deep_w.data() + deep_w_off(l));
+        std::copy(bias.begin(), bias.end(), deep_b.begin() + deep_b_off(l));
+        if (l == DEEP_LAYERS - 1) {
+          blob->add(&W.wp[7], deep_w.data(), deep_w.size());
+          blob->add(&W.cb[7], deep_b.data(), deep_b.size());
+          std::vector<float>().swap(deep_w);
+        }
+        continue;
+      }
       std::vector<float> pk((size_t)cin * 9 * cout);
       pack_conv_exact(wf.data(), cin, cout, pk.data());
       blob->add(&W.wp[idx], pk.data(), pk.size());
@@ -502,7 +538,25 @@ sedx_status prepare_weights(const Model& m, const Params& P, DevWeights* Wp, Wei
 
   // ---- sequence layer ----
   std::vector<float> w_ih, wqkv;   // kept for their x3 packs, which follow the head in the image
-  if (m.seq == SEQ_GRU) {
+  if (m.seq == SEQ_GRU && deep) {
+    // nn.GRU(2048, 1024): both directions' W_ih stacked [6144][2048], W_hh as it stands [2][3072][1024]
+    std::vector<float> b_ih, whh_nat, bhh;
+    const char* sfx[2] = {"", "_reverse"};
+    for (int d = 0; d < 2; ++d) {
+      const auto& wih = get(std::string("gru.weight_ih_l0") + sfx[d]);
+      const auto& whh = get(std::string("gru.weight_hh_l0") + sfx[d]);
+      const auto& bi = get(std::string("gru.bias_ih_l0") + sfx[d]);
+      const auto& bh = get(std::string("gru.bias_hh_l0") + sfx[d]);
+      w_ih.insert(w_ih.end(), wih.begin(), wih.end());
+      whh_nat.insert(whh_nat.end(), whh.begin(), whh.end());
+      b_ih.insert(b_ih.end(), bi.begin(), bi.end());
+      bhh.insert(bhh.end(), bh.begin(), bh.end());
+    }
+    blob->add(&W.w_ih, w_ih.data(), w_ih.size());
+    blob->add(&W.b_ih, b_ih.data(), b_ih.size());
+    blob->add(&W.whh, whh_nat.data(), whh_nat.size());
+    blob->add(&W.bhh, bhh.data(), bhh.size());
+  } else if (m.seq == SEQ_GRU) {
     std::vector<float> b_ih(1536), whhT(2 * 256 * 768), whh_nat, bhh(2 * 768);
     w_ih.resize(1536 * 512);
     const char* sfx[2] = {"", "_reverse"};
@@ -525,18 +579,18 @@ sedx_status prepare_weights(const Model& m, const Params& P, DevWeights* Wp, Wei
     blob->add(&W.bhh, bhh.data(), bhh.size());
   } else if (m.seq == SEQ_MHA) {
     std::vector<float> bqkv(1536);
-    wqkv.resize(1536 * 512);
+    wqkv.resize((size_t)1536 * hw);   // q | k | v rows, [1536][hw]
     const char* nm[3] = {"w_qs", "w_ks", "w_vs"};
     for (int i = 0; i < 3; ++i) {
       const auto& ww = get(std::string("multihead.") + nm[i] + ".weight");
       const auto& bb = get(std::string("multihead.") + nm[i] + ".bias");
-      std::copy(ww.begin(), ww.end(), wqkv.begin() + (size_t)i * 512 * 512);
+      std::copy(ww.begin(), ww.end(), wqkv.begin() + (size_t)i * 512 * hw);
       std::copy(bb.begin(), bb.end(), bqkv.begin() + i * 512);
     }
     blob->add(&W.wqkv, wqkv.data(), wqkv.size());
     blob->add(&W.bqkv, bqkv.data(), bqkv.size());
-    blob->add(&W.wfc, get("multihead.fc.weight").data(), (size_t)512 * 512);
-    blob->add(&W.bfc, get("multihead.fc.bias").data(), (size_t)512);
+    blob->add(&W.wfc, get("multihead.fc.weight").data(), (size_t)hw * 512);
+    blob->add(&W.bfc, get("multihead.fc.bias").data(), (size_t)hw);
   }
 
   std::vector<float> wac, bac;
@@ -549,7 +603,9 @@ sedx_status prepare_weights(const Model& m, const Params& P, DevWeights* Wp, Wei
     const std::vector<uint16_t> px = pack_x3(w, N, 512, 1, BN);
     blob->add(dst, px.data(), px.size());
   };
-  if (m.seq == SEQ_GRU) {
+  if (deep) {
+    // the 14-layer models' linear layers run fp32 in every mode: no x3 packs
+  } else if (m.seq == SEQ_GRU) {
     add_x3(&W.w_ih_x3, w_ih.data(), 1536, 128);
   } else if (m.seq == SEQ_MHA) {
     add_x3(&W.wqkv_x3, wqkv.data(), 1536, 128);

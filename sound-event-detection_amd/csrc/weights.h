@@ -27,6 +27,15 @@ constexpr int CF_D = 144;        // adim
 constexpr int CF_FF = 576;       // eunits
 constexpr int CF_BLOCKS = 3;     // elayers
 constexpr int CF_MAX_T = 5000;   // rows of the positional table pe (PositionalEncoding max_len)
+// 14-layer trunk: the launches of conv_deep.hip (block 4's conv2, blocks 5-6)
+constexpr int DEEP_LAYERS = 5;
+constexpr int DEEP_CK = 16;      // input channels per K chunk
+constexpr int DEEP_BN = 128;     // output channels per workgroup (4 waves x 32)
+constexpr int DEEP_CIN[DEEP_LAYERS] = {512, 512, 1024, 1024, 2048};    // b4c2, b5c1, b5c2, b6c1, b6c2
+constexpr int DEEP_COUT[DEEP_LAYERS] = {512, 1024, 1024, 2048, 2048};
+// float offsets of deep layer l in the handle's deep weight pack / bias block (DevWeights::wp[7], cb[7])
+constexpr size_t deep_w_off(int l) { return l == 0 ? 0 : deep_w_off(l - 1) + (size_t)9 * DEEP_CIN[l - 1] * DEEP_COUT[l - 1]; }
+constexpr size_t deep_b_off(int l) { return l == 0 ? 0 : deep_b_off(l - 1) + DEEP_COUT[l - 1]; }
 
 // ---- the model ------------------------------------------------------------
 // a model = the CNN trunk, then a sequence layer, then a head
@@ -44,7 +53,8 @@ struct Model {
   sedx_config cfg{};
   int seq = SEQ_GRU;   // what follows the CNN trunk
   int head = HEAD_ATT; // the head that reads its output
-  int hw = 512;        // width of the head's input: 512, or 144 after the Conformer encoder
+  int depth = 9;       // conv layers of the trunk: 9, or 14 (blocks 5-6 and five pools: T/32 sequence frames)
+  int hw = 512;        // width of the head's input: 512, 144 after the Conformer encoder, 2048 on the 14-layer trunk
   int nac = 64;        // rows of the head projection: att|cla (2C) or fc (C), rounded up to 64
 };
 // cfg -> Model (seq, head, hw, nac); false for an unknown model_type
@@ -107,14 +117,17 @@ struct DevWeights {
   void* wx3[8] = {};    // split bf16 hi/lo packs for conv3x3_x3 (same indices)
   float* wu[8] = {};    // Winograd U = G g G^T packs for conv3x3_wino (same indices)
   float* wu43[8] = {};  // F(4x4,3x3) U packs for conv3x3_wino43 (block 1's conv2: 1, blocks 2-4: 2..7)
-  float* w_ih = nullptr;   // [1536][512]
-  float* b_ih = nullptr;   // [1536]
-  float* whhT = nullptr;   // [2][256][768]
-  float* whh = nullptr;    // [2][768][256] (cooperative recurrence)
-  float* bhh = nullptr;    // [2][768]
-  float* wqkv = nullptr;   // [1536][512]
+  // 14-layer trunk (conv_deep.hip): wp[7] holds pack_conv_deep of b4c2, b5c1, b5c2, b6c1, b6c2 back to
+  // back (layer l at deep_w_off(l)) and cb[7] their folded biases (at deep_b_off(l)); block 4's conv2
+  // has no other pack on such a handle and blocks 5-6 no other slot
+  float* w_ih = nullptr;   // [1536][512]; 14-layer: [6144][2048]
+  float* b_ih = nullptr;   // [1536]; [6144]
+  float* whhT = nullptr;   // [2][256][768] (9-layer only)
+  float* whh = nullptr;    // [2][768][256] (cooperative recurrence); 14-layer: [2][3072][1024] (gru1024.hip)
+  float* bhh = nullptr;    // [2][768]; [2][3072]
+  float* wqkv = nullptr;   // [1536][512]; 14-layer: [1536][2048]
   float* bqkv = nullptr;
-  float* wfc = nullptr;    // [512][512]
+  float* wfc = nullptr;    // [512][512]; 14-layer: [2048][512]
   float* bfc = nullptr;
   float* wac = nullptr;    // [nac][hw]
   float* bac = nullptr;
@@ -161,6 +174,11 @@ struct WeightBlob {
 void pack_conv_exact(const double* wf, int Cin, int Cout, float* out);    // out: Cin * 9 * Cout floats
 void pack_conv_wino(const double* wf, int Cin, int Cout, float* U);       // U: Cin * Cout * 16 floats
 void pack_conv_wino43(const double* wf, int Cin, int Cout, float* U);     // U: 2 * Cin * Cout * 36 floats
+void pack_conv_deep(const double* wf, int Cin, int Cout, float* out);     // out: Cin * 9 * Cout floats
+// where pack_conv_deep puts weight (o, i, tap): [Cout/32][Cin/16][9][4 q][32 n][4 c], o = 32 g + n, i = 16 chunk + 4 q + c
+inline size_t deep_pack_index(int Cin, int o, int i, int tap) {
+  return ((((((size_t)(o / 32) * (Cin / DEEP_CK) + i / DEEP_CK) * 9 + tap) * 4 + (i % DEEP_CK) / 4) * 32 + o % 32) * 4) + i % 4;
+}
 // w [N][K][taps] fp32 -> split-bf16 pack for conv_x3.hip (taps 9) and linear_x3.hip (taps 1):
 // x = hi + lo + (dropped), hi = bf16(x), lo = bf16(x - hi), both round-to-nearest-even
 std::vector<uint16_t> pack_x3(const float* w, int N, int K, int taps, int BN);

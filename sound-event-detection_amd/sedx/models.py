@@ -14,7 +14,9 @@ same rule, and so do the two Conformer models on that trunk
 ``(..., classes_num, cnn_kwargs=None, encoder_kwargs=None,
 encoder_type="Conformer", pooling="token", layer_init="pytorch")`` and
 ``forward(x, mixup_lambda=None, timeshift=False, spec_augment=True,
-mask=None)``).  The submodules are parameter containers; the whole eval-mode forward runs in
+mask=None)``), and the two models on the 14-layer trunk
+(``Cnn_14layers_Gru_FrameAtt``, ``Cnn_14layers_Transformer_FrameAtt``: eight
+constructor arguments, 25 classes).  The submodules are parameter containers; the whole eval-mode forward runs in
 libsedx (HIP kernels for gfx950) through the C ABI in include/sedx.h.  There
 is no CPU or eager-PyTorch fallback: a non-HIP input raises.
 
@@ -40,6 +42,7 @@ from . import _lib
 from .stft import Spectrogram, LogmelFilterBank
 
 __all__ = ['Cnn_9layers_Gru_FrameAtt', 'Cnn_9layers_Transformer_FrameAtt',
+           'Cnn_14layers_Gru_FrameAtt', 'Cnn_14layers_Transformer_FrameAtt',
            'Cnn_9layers_FrameMax', 'Cnn_9layers_FrameAvg', 'Cnn_9layers_FrameAtt',
            'Cnn_9layers_Gru_FrameAvg', 'Cnn_9layers_Transformer_FrameAvg',
            'Cnn_9layers_Conformer_FrameAtt', 'Cnn_9layers_Conformer_FrameAvg', 'ConformerEncoder', 'ConvBlock',
@@ -50,7 +53,8 @@ __all__ = ['Cnn_9layers_Gru_FrameAtt', 'Cnn_9layers_Transformer_FrameAtt',
 MODEL_IDS = {'Cnn_9layers_Gru_FrameAtt': 0, 'Cnn_9layers_Transformer_FrameAtt': 1,
              'Cnn_9layers_FrameMax': 2, 'Cnn_9layers_FrameAvg': 3, 'Cnn_9layers_FrameAtt': 4,
              'Cnn_9layers_Gru_FrameAvg': 5, 'Cnn_9layers_Transformer_FrameAvg': 6,
-             'Cnn_9layers_Conformer_FrameAtt': 7, 'Cnn_9layers_Conformer_FrameAvg': 8}
+             'Cnn_9layers_Conformer_FrameAtt': 7, 'Cnn_9layers_Conformer_FrameAvg': 8,
+             'Cnn_14layers_Gru_FrameAtt': 10, 'Cnn_14layers_Transformer_FrameAtt': 11}   # 9 is not assigned
 FEATURE_IDS = {'logmel': 0, 'gamma': 1}
 
 
@@ -154,8 +158,8 @@ class MultiHead(nn.Module):
 
     def __init__(self, n_head, d_model, d_k, d_v, dropout=0.1):
         super().__init__()
-        if (n_head, d_model, d_k, d_v) != (8, 512, 64, 64):
-            raise ValueError('the native MHA implements the reference shape (8 heads, 512, 64, 64)')
+        if (n_head, d_k, d_v) != (8, 64, 64) or d_model not in (512, 2048):
+            raise ValueError('the native MHA implements the reference shapes (8 heads, 512 or 2048, 64, 64)')
         self.n_head, self.d_k, self.d_v = n_head, d_k, d_v
         self.w_qs = nn.Linear(d_model, n_head * d_k)
         self.w_ks = nn.Linear(d_model, n_head * d_k)
@@ -765,3 +769,53 @@ class Cnn_9layers_Conformer_FrameAvg(_ConformerModel):
 
     def _build_head(self, classes_num):
         self.fc = nn.Linear(144, classes_num, bias=True)
+
+
+class _Deep14Model(_SedModel):
+    """The 14-layer trunk (pytorch/models.py:720-725, :1109-1114): blocks 1-4,
+    then ``conv_block5`` (512 -> 1024) and ``conv_block6`` (1024 -> 2048), five
+    2x2 pools: ``data_length // hop // 32`` sequence frames of 2048 channels,
+    x32 frame repeat, framewise padded to a multiple of 100 with its last frame
+    unless it has 1000 frames.  ``AttBlock(2048, 25)``: 25 classes whatever
+    ``classes_num`` is (:730, :1123).  ``feature_type`` is accepted and ignored,
+    as the reference's forward ignores it (always logmel).  Block 4's conv2,
+    blocks 5-6, the sequence layer and the head run fp32 in every precision
+    mode; ``set_precision`` selects blocks 1-3 and block 4's conv1."""
+    _embedding_width = 2048
+
+    def __init__(self, sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num,
+                 feature_type):
+        super().__init__(sample_rate, window_size, hop_size, mel_bins, fmin, fmax, 25, 'logmel')
+        self.conv_block5 = ConvBlock(512, 1024)
+        self.conv_block6 = ConvBlock(1024, 2048)
+
+
+class Cnn_14layers_Gru_FrameAtt(_Deep14Model):
+    """pytorch/models.py:691-791: ``nn.GRU(2048, 1024, bidirectional)``;
+    embedding = cla (batch, 25, seq)."""
+    _model_name = 'Cnn_14layers_Gru_FrameAtt'
+    _embedding_cla = True
+
+    def __init__(self, sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num,
+                 feature_type):
+        super().__init__(sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num,
+                         feature_type)
+        self.gru = nn.GRU(input_size=2048, hidden_size=1024, num_layers=1, bias=True,
+                          batch_first=True, bidirectional=True)
+        self.att_block = AttBlock(n_in=2048, n_out=25, activation='sigmoid')
+        init_bn(self.bn0)
+        init_gru(self.gru)
+
+
+class Cnn_14layers_Transformer_FrameAtt(_Deep14Model):
+    """pytorch/models.py:1080-1184: ``MultiHead(8, 2048, 64, 64)``; embedding =
+    its output (batch, 2048, seq)."""
+    _model_name = 'Cnn_14layers_Transformer_FrameAtt'
+
+    def __init__(self, sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num,
+                 feature_type):
+        super().__init__(sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num,
+                         feature_type)
+        self.multihead = MultiHead(8, 2048, 64, 64, 0.2)
+        self.att_block = AttBlock(n_in=2048, n_out=25, activation='sigmoid')
+        init_bn(self.bn0)

@@ -18,6 +18,8 @@ buffers (``spectrogram_extractor.stft.conv_{real,imag}.weight``,
 import numpy as np
 
 CONV_CHANNELS = [(1, 64), (64, 128), (128, 256), (256, 512)]
+# blocks 5-6 of the 14-layer trunk (models.py:724-725)
+DEEP_CONV_CHANNELS = [(512, 1024), (1024, 2048)]
 
 
 def _xavier_uniform(rng, shape, fan_in, fan_out, gain=1.0):
@@ -46,6 +48,8 @@ MODEL_PARTS = {
     'Cnn_9layers_Transformer_FrameAvg': ('mha', 'fc'),
     'Cnn_9layers_Conformer_FrameAtt': ('conformer', 'att'),
     'Cnn_9layers_Conformer_FrameAvg': ('conformer', 'fc'),
+    'Cnn_14layers_Gru_FrameAtt': ('gru', 'att'),
+    'Cnn_14layers_Transformer_FrameAtt': ('mha', 'att'),
 }
 # the weight seed of every model's golden fixtures (tests/golden/)
 GOLDEN_SEEDS = {
@@ -64,6 +68,16 @@ GOLDEN_SEEDS = {
 CONFORMER_GOLDEN_SEEDS = {
     'Cnn_9layers_Conformer_FrameAtt': 7,
     'Cnn_9layers_Conformer_FrameAvg': 8,
+}
+# the two 14-layer models' (tests/golden/deep14_*): ``pytorch/models.py:691-791``, ``:1080-1184``.
+# The GRU model's seed is one at which the reference's windowed output keeps
+# every value that decides an event at least 1e-4 away from its threshold
+# (tools/make_golden_deep14.py asserts it and records the margin in
+# deep14_meta.json; with seed 9 one class sat 8e-5 from its threshold on every
+# waveform tried)
+DEEP14_GOLDEN_SEEDS = {
+    'Cnn_14layers_Gru_FrameAtt': 19,
+    'Cnn_14layers_Transformer_FrameAtt': 10,
 }
 CONFORMER_DIM, CONFORMER_FF, CONFORMER_BLOCKS, CONFORMER_HEADS, CONFORMER_KERNEL = 144, 576, 3, 4, 7
 
@@ -120,7 +134,7 @@ def _conformer_encoder(rng):
 
 def make_state_dict(model_type, classes_num=25, seed=0):
     """Return {key: np.ndarray} for the non-frontend parameters of one of the
-    nine 9-layer models (``MODEL_PARTS``).  Draw order: the trunk, the
+    nine 9-layer models or the two 14-layer ones (``MODEL_PARTS``).  Draw order: the trunk, the
     sequence layer's tensors, the head's (so two models with one seed share
     every tensor up to the first that differs).  ``Cnn_9layers_FrameAtt``'s
     AttBlock has 25 classes whatever ``classes_num`` is (models.py:416), and so
@@ -132,14 +146,16 @@ def make_state_dict(model_type, classes_num=25, seed=0):
         raise ValueError('unknown model_type %r' % model_type)
     seq, head = MODEL_PARTS[model_type]
     ctor_classes = classes_num
-    if model_type in ('Cnn_9layers_FrameAtt', 'Cnn_9layers_Conformer_FrameAtt'):
+    deep = model_type in DEEP14_GOLDEN_SEEDS      # AttBlock(2048, 25) too (models.py:730, :1123)
+    if model_type in ('Cnn_9layers_FrameAtt', 'Cnn_9layers_Conformer_FrameAtt') or deep:
         classes_num = 25
-    width = CONFORMER_DIM if seq == 'conformer' else 512
+    width = CONFORMER_DIM if seq == 'conformer' else 2048 if deep else 512
+    hid = width // 2                              # nn.GRU(512, 256) / nn.GRU(2048, 1024)
     rng = np.random.default_rng(seed)
     sd = {}
     # bn0 normalises log-mel dB values (models.py:607,642-644); realistic stats
     sd.update(_bn(rng, 'bn0', 64, mean_range=(-45.0, -35.0), var_range=(300.0, 500.0)))
-    for k, (cin, cout) in enumerate(CONV_CHANNELS, start=1):
+    for k, (cin, cout) in enumerate(CONV_CHANNELS + (DEEP_CONV_CHANNELS if deep else []), start=1):
         p = 'conv_block%d' % k
         sd[p + '.conv1.weight'] = _xavier_uniform(rng, (cout, cin, 3, 3), cin * 9, cout * 9)
         sd[p + '.conv2.weight'] = _xavier_uniform(rng, (cout, cout, 3, 3), cout * 9, cout * 9)
@@ -149,23 +165,23 @@ def make_state_dict(model_type, classes_num=25, seed=0):
         # init_gru (models.py:35-60): U(+-sqrt(3/fan_in)) per gate block; small
         # random biases so the bias paths are exercised.
         for sfx in ('', '_reverse'):
-            b_ih = np.sqrt(3.0 / 512)
-            b_hh = np.sqrt(3.0 / 256)
-            sd['gru.weight_ih_l0' + sfx] = rng.uniform(-b_ih, b_ih, (768, 512)).astype(np.float32)
-            sd['gru.weight_hh_l0' + sfx] = rng.uniform(-b_hh, b_hh, (768, 256)).astype(np.float32)
-            sd['gru.bias_ih_l0' + sfx] = rng.uniform(-0.1, 0.1, 768).astype(np.float32)
-            sd['gru.bias_hh_l0' + sfx] = rng.uniform(-0.1, 0.1, 768).astype(np.float32)
+            b_ih = np.sqrt(3.0 / width)
+            b_hh = np.sqrt(3.0 / hid)
+            sd['gru.weight_ih_l0' + sfx] = rng.uniform(-b_ih, b_ih, (3 * hid, width)).astype(np.float32)
+            sd['gru.weight_hh_l0' + sfx] = rng.uniform(-b_hh, b_hh, (3 * hid, hid)).astype(np.float32)
+            sd['gru.bias_ih_l0' + sfx] = rng.uniform(-0.1, 0.1, 3 * hid).astype(np.float32)
+            sd['gru.bias_hh_l0' + sfx] = rng.uniform(-0.1, 0.1, 3 * hid).astype(np.float32)
     elif seq == 'mha':
         # MultiHead init (models.py:835-852): normal(0, sqrt(2/(d_model+d_k)))
-        std_qkv = np.sqrt(2.0 / (512 + 64))
+        std_qkv = np.sqrt(2.0 / (width + 64))
         for nm in ('w_qs', 'w_ks', 'w_vs'):
-            sd['multihead.%s.weight' % nm] = rng.normal(0, std_qkv, (512, 512)).astype(np.float32)
+            sd['multihead.%s.weight' % nm] = rng.normal(0, std_qkv, (512, width)).astype(np.float32)
             sd['multihead.%s.bias' % nm] = rng.uniform(-0.05, 0.05, 512).astype(np.float32)
-        sd['multihead.layer_norm.weight'] = np.ones(512, np.float32)
-        sd['multihead.layer_norm.bias'] = np.zeros(512, np.float32)
-        std_fc = np.sqrt(2.0 / (512 + 512))
-        sd['multihead.fc.weight'] = rng.normal(0, std_fc, (512, 512)).astype(np.float32)
-        sd['multihead.fc.bias'] = rng.uniform(-0.05, 0.05, 512).astype(np.float32)
+        sd['multihead.layer_norm.weight'] = np.ones(width, np.float32)
+        sd['multihead.layer_norm.bias'] = np.zeros(width, np.float32)
+        std_fc = np.sqrt(2.0 / (512 + width))
+        sd['multihead.fc.weight'] = rng.normal(0, std_fc, (width, 512)).astype(np.float32)
+        sd['multihead.fc.bias'] = rng.uniform(-0.05, 0.05, width).astype(np.float32)
     elif seq == 'conformer':
         sd.update(_conformer_encoder(rng))
     if head == 'fc':
