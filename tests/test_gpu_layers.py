@@ -2,7 +2,8 @@
 and sequence-chunk edges.
 
 Every model here takes a [B, 64, T] feature matrix (``sedx_forward_features``),
-so T and B are free and no audio frontend is involved; ``sedx_set_capture``
+so T and B are free and no audio frontend is involved (the log-mel front end
+alone, waveform -> stage 0: tests/test_gpu_frontend.py); ``sedx_set_capture``
 exposes stages 0 and 2-9.  The reference of a step is the oracle's own layer
 function in float64 (oracle/layer_refs.py) applied to the GPU's own previous
 stage, so one layer's rounding is all that a layer-isolated check measures.

@@ -571,6 +571,26 @@ def test_gamma_codes_vs_oracle(seconds, seed, spec):
         assert np.array_equal(q[b], ref), (b, int((q[b] != ref).sum()))
 
 
+@pytest.mark.parametrize('fit', [False, True], ids=['1s', 'fit'])
+@pytest.mark.parametrize('preset', ['16k', '8k'])
+def test_gamma_codes_vs_oracle_low_rates(preset, fit):
+    """The 16 kHz (nfft 1024) and 8 kHz (nfft 512) gammatone spectra: bit-exact
+    int16 codes against the oracle on 3 clips of about 1 s, one case with
+    (L - nfft) % hop == 0.  The clips keep every float64 pre-truncation value
+    1e-6 or more from an integer (tests/test_frontend_refs_cpu.py), so a
+    differing code is not a tie."""
+    import frontend_refs as FR
+    from sedx import inference
+    m = build(GRU, PRESET_ARGS[preset], 'gamma')
+    audio, ref, _ = FR.gamma_case(preset, fit)
+    q = _codes(inference.gamma_features(m, torch.from_numpy(audio).cuda()))
+    assert q.shape == ref.shape
+    d = q != ref
+    print('gamma', preset, 'fit' if fit else '1s', ref.shape, 'cells differing =', int(d.sum()),
+          'first', np.argwhere(d)[:4].tolist())
+    assert not d.any()
+
+
 @pytest.mark.parametrize('mt', [GRU, TRF])
 @pytest.mark.parametrize('preset', ['8k', '32k'])
 def test_logmel_presets_vs_oracle(mt, preset):
