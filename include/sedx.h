@@ -75,7 +75,29 @@ typedef enum {
   /* 9 is not assigned: callers written against the nine 9-layer models probe it
    * as the first unknown model_type, and sedx_create keeps answering SEDX_EINVAL */
   SEDX_MODEL_GRU14_FRAMEATT = 10,         /* Cnn_14layers_Gru_FrameAtt  :691-791: nn.GRU(2048, 1024, bidirectional) */
-  SEDX_MODEL_TRANSFORMER14_FRAMEATT = 11  /* Cnn_14layers_Transformer_FrameAtt  :1080-1184: MultiHead(8, 2048, 64, 64) */
+  SEDX_MODEL_TRANSFORMER14_FRAMEATT = 11, /* Cnn_14layers_Transformer_FrameAtt  :1080-1184: MultiHead(8, 2048, 64, 64) */
+  /* 12 is not assigned either (probed as the first unknown id after the two models above) */
+  /* Cnn14_DecisionLevelAtt  :2685-2783, the PANNs architecture: the 14-layer
+   * trunk, then over the T/32 sequence frames max_pool1d(3, 1, 1) +
+   * avg_pool1d(3, 1, 1) (zero padding, always / 3), fc1 = Linear(2048, 2048) +
+   * ReLU, AttBlock(2048, classes_num) with classes_num up to 527 (every other
+   * model: 256).  feature_type must be LOGMEL.
+   *   geometry   T = L / hop + 1 frames; seq_len = T / 32; out_frames = T - 1:
+   *              every sequence frame x32, then the last frame repeated
+   *              (T % 32) - 1 times (10 s at hop 320 / 32 kHz: 992 + 8 = 1000)
+   *   refusals   T < 32 (the fifth pool has no output) and every T % 32 == 0
+   *              (the reference's padding count is -1 and it raises):
+   *              SEDX_EINVAL from the forwards, sedx_output_geometry,
+   *              sedx_workspace_size and the windowed drivers alike
+   *   keys       the 14-layer trunk's (frontend buffers, bn0, conv_block1-6),
+   *              fc1.{weight [2048][2048], bias}, att_block.{att,cla}.{weight
+   *              [C][2048][1], bias} and att_block.bn_att.* (accepted, unused)
+   *   outputs    framewise and clipwise only: the reference returns no
+   *              'embedding', d_embedding is ignored and may be NULL
+   * The pooling, fc1 and the head are fp32 in every precision mode; captures:
+   * 43 is the pooling's input, 9 is fc1's output [items][T/32][2048], and the
+   * timed stage 9 is the one pooling + fc1 launch. */
+  SEDX_MODEL_CNN14_DECISIONLEVELATT = 13
 } sedx_model;
 
 typedef enum { SEDX_FEATURE_LOGMEL = 0, SEDX_FEATURE_GAMMA = 1 } sedx_feature;
@@ -101,7 +123,8 @@ typedef struct sedx_handle sedx_handle;
  * and the constructors of the other sedx_model values).  feature_type GAMMA is
  * Cnn_9layers_Gru_FrameAtt's alone (Cnn_9layers_Gru_FrameAvg takes the argument
  * and ignores it, :512-518); any other model_type with it is SEDX_EINVAL
- * (the two 14-layer models included). */
+ * (the 14-layer models included).  classes_num: 1..256, and up to 527 for
+ * SEDX_MODEL_CNN14_DECISIONLEVELATT. */
 sedx_status sedx_create(const sedx_config* cfg, int device, sedx_handle** out);
 void sedx_destroy(sedx_handle* h);
 const char* sedx_last_error(const sedx_handle* h);
@@ -183,7 +206,8 @@ sedx_status sedx_conv_launch_plan(const sedx_handle* h, int64_t B, int64_t L_or_
  *                transposed (the GRU / MHA output; CNN_FRAMEMAX / CNN_FRAMEAVG:
  *                block 4's frequency mean); the Conformer models:
  *                [B, 144, seq_len], the encoder output transposed
- *                (may be NULL)
+ *                (may be NULL); CNN14_DECISIONLEVELATT: ignored, nothing is
+ *                written (the reference returns no embedding)
  * The Conformer models hold at most 5000 sequence frames (the positional
  * table): beyond, the forward, geometry and workspace queries are SEDX_EINVAL.
  *   d_workspace  NULL = handle-owned cache, else >= sedx_workspace_size bytes. */
@@ -518,7 +542,9 @@ sedx_status sedx_set_pipelined(sedx_handle* h, int32_t on);
  *   42  conv1 of block 6              [items][T/32][2][2048]
  *   43  block 6 + freq mean           [items][T/32][2048] (the sequence input)
  * Their timed stage 8 spans block 4's conv2 and the four launches of blocks
- * 5-6; stage 9 is the sequence layer alone.
+ * 5-6; stage 9 is the sequence layer alone.  SEDX_MODEL_CNN14_DECISIONLEVELATT
+ * has no sequence layer: its 9 is relu(fc1) [items][T/32][2048], computed from
+ * 43 by the one pooling + fc1 launch that stage 9 times.
  * stage < 0 or d_buf == NULL switches capture off. */
 sedx_status sedx_set_capture(sedx_handle* h, int32_t stage, float* d_buf, size_t bytes);
 sedx_status sedx_set_profiling(sedx_handle* h, int32_t on);

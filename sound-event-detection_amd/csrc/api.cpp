@@ -187,6 +187,7 @@ sedx_status query_geometry(const sedx_handle* h, int64_t L_or_T, Geometry* g) {
   // the 14-layer models have no output below 32 frames (the reference's fifth
   // avg_pool2d raises): the queries reject what the forward rejects
   if (h->depth == 14 && g->Ts < 1) return fail(h, SEDX_EINVAL, "input too short for the 5 pooling stages");
+  if (decision_pad_negative(*h, g->T)) return fail(h, SEDX_EINVAL, DECISION_PAD_REFUSAL, (long long)g->T);
   return SEDX_OK;
 }
 
@@ -359,8 +360,11 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
   };
   // the head's input [M][512]: the sequence layer's output, or (no sequence
   // layer: no projection, no recurrence / MHA launch) the stage-8 buffer itself
-  const float* HI = h->seq == SEQ_NONE ? S : Hs;
-  if (h->depth == 14) {
+  const float* HI = h->seq == SEQ_NONE && !h->decision ? S : Hs;
+  if (h->decision) {
+    // Cnn14_DecisionLevelAtt: max + avg pooling over 3 sequence frames inside fc1's A staging, + ReLU: one launch
+    launch_decision(S, iB, T3, w.wfc, w.bfc, Hs, s);   // fc1 in the MultiHead fc's slots (weights.h)
+  } else if (h->depth == 14) {
     // fp32 in every precision mode: the generic fp32 GEMM at the new widths
     if (h->seq == SEQ_GRU) {
       launch_linear(S, M, 2048, w.w_ih, 6144, w.b_ih, G, 0, s);
@@ -437,11 +441,11 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
     linear(HI, w.wac, w.wac_x3, h->nac, 64, w.bac, LG, 0);
   if (h->head == HEAD_ATT)
     launch_att_head(LG, iB, T3, h->cfg.classes_num, h->nac, (int)g.out_frames, d_fw, d_clip,
-                    h->emb_cla ? d_emb : nullptr, s, g.rep);
+                    h->emb_cla && !h->decision ? d_emb : nullptr, s, g.rep);
   else
     launch_fc_head(LG, iB, T3, h->cfg.classes_num, h->nac, h->head == HEAD_FC_MAX, d_fw, d_clip, s,
                    (int)g.out_frames);
-  if (!h->emb_cla && d_emb) launch_transpose_btd(HI, iB, T3, h->hw, d_emb, s);
+  if (!h->emb_cla && !h->decision && d_emb) launch_transpose_btd(HI, iB, T3, h->hw, d_emb, s);
   mark(h, 11, s);
   return launch_status(h);
 }
@@ -523,7 +527,9 @@ sedx_status sedx_create(const sedx_config* cfg, int device, sedx_handle** out) {
   *out = nullptr;
   if (cfg->mel_bins != 64) return SEDX_EINVAL;
   if (cfg->window_size != 256 && cfg->window_size != 512 && cfg->window_size != 1024) return SEDX_EINVAL;
-  if (cfg->hop_size <= 0 || cfg->sample_rate <= 0 || cfg->classes_num <= 0 || cfg->classes_num > 256)
+  // 256 classes; AudioSet's 527 for Cnn14_DecisionLevelAtt alone (weights.h)
+  const int max_classes = cfg->model_type == SEDX_MODEL_CNN14_DECISIONLEVELATT ? DECISION_MAX_CLASSES : MAX_CLASSES;
+  if (cfg->hop_size <= 0 || cfg->sample_rate <= 0 || cfg->classes_num <= 0 || cfg->classes_num > max_classes)
     return SEDX_EINVAL;
   if (cfg->feature_type == SEDX_FEATURE_GAMMA && cfg->model_type != SEDX_MODEL_GRU_FRAMEATT)
     return SEDX_EINVAL;

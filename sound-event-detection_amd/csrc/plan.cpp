@@ -27,7 +27,11 @@ Geometry geometry_from_T(const Model& m, int64_t T) {
   // Conformer models (:1359-1360, :1571-1572)
   // and both 14-layer models (:783-784, :1176-1177)
   const bool pad100 = m.cfg.model_type == SEDX_MODEL_GRU_FRAMEATT || m.seq == SEQ_CONFORMER || deep;
-  if (pad100 && g.fw_len != 1000)
+  if (m.decision) {
+    // Cnn14_DecisionLevelAtt: frames_num = T - 1 (models.py:2738, :2778), not a multiple of 100; where the
+    // model has no output (T < 32, T % 32 == 0: refused by every caller) the repeated frames stand
+    if (g.Ts >= 1 && T % 32 != 0) g.out_frames = T - 1;
+  } else if (pad100 && g.fw_len != 1000)
     g.out_frames = (g.fw_len % 100 == 0) ? g.fw_len : g.fw_len + 100 - g.fw_len % 100;
   return g;
 }
@@ -100,9 +104,10 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
   }
   const size_t M = (size_t)p->M;
   size_t e_head = a0;
-  p->G = take(e_head, M * (deep && m.seq == SEQ_GRU ? 6144 : 1536));
+  // (Cnn14_DecisionLevelAtt: H [M][2048] and the logits only)
+  p->G = take(e_head, m.decision ? 0 : M * (deep && m.seq == SEQ_GRU ? 6144 : 1536));
   p->Hs = take(e_head, M * (deep ? 2048 : 512));
-  p->O = take(e_head, M * 512);
+  p->O = take(e_head, m.decision ? 0 : M * 512);
   p->LG = take(e_head, M * m.nac);
   p->gru = take(e_head, deep ? 0 : gru_coop_workspace_bytes((int)B) / 4);   // gru1024.hip: no scratch
   size_t e_a = std::max(a0 + align256(a_conv * 4), e_head);
@@ -131,6 +136,7 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
   p->reject[0] = 0;
   if (g.T3 < 1) snprintf(p->reject, sizeof(p->reject), "input too short for the 3 pooling stages");
   else if (g.Ts < 1) snprintf(p->reject, sizeof(p->reject), "input too short for the 5 pooling stages");
+  else if (decision_pad_negative(m, T)) snprintf(p->reject, sizeof(p->reject), DECISION_PAD_REFUSAL, (long long)T);
   else if (seq_too_long(m, g.T3))
     snprintf(p->reject, sizeof(p->reject), "%lld sequence frames: the Conformer encoder holds %d", (long long)g.T3,
              CF_MAX_T);
@@ -345,6 +351,9 @@ const char* window_geometry(const Model& m, int64_t L_clip, const sedx_window_sp
       g.len = len;
       g.g = geometry_from_T(m, conv_T(m, len));
       if (g.g.Ts < 1) return refuse("window %d too short for the CNN", w, 0, 0);
+      if (decision_pad_negative(m, g.g.T))
+        return refuse("window %d has %lld frames, a multiple of 32: Cnn14_DecisionLevelAtt has no output for it", w,
+                      (long long)g.g.T, 0);
       if (seq_too_long(m, g.g.T3))
         return refuse("window %d gives %lld sequence frames: the Conformer encoder holds %d", w, (long long)g.g.T3,
                       CF_MAX_T);

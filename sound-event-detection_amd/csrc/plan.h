@@ -46,6 +46,12 @@ inline int64_t conv_T(const Model& m, int64_t L) { return L / m.cfg.hop_size + 1
 // fails on a longer sequence too (embedding.py:30: the add does not broadcast)
 inline bool seq_too_long(const Model& m, int64_t T3) { return m.seq == SEQ_CONFORMER && T3 > CF_MAX_T; }
 Geometry geometry_from_T(const Model& m, int64_t T);
+// Cnn14_DecisionLevelAtt pads 32 (T / 32) frames to T - 1 with (T % 32) - 1 copies of
+// the last one (models.py:2738, :2778): at T % 32 == 0 that count is -1 and
+// the reference raises, so the forwards and the size queries refuse it alike
+inline bool decision_pad_negative(const Model& m, int64_t T) { return m.decision && T >= 32 && T % 32 == 0; }
+constexpr const char* DECISION_PAD_REFUSAL =   // fits ForwardPlan::reject
+    "%lld frames: a multiple of 32 has no output (the reference pads by -1 frames)";
 
 // ---- what the handle's setters store ----------------------------------------
 struct Tuning {

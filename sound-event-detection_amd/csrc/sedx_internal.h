@@ -339,6 +339,12 @@ void launch_gru_coop(const float* G, int B, int T, const float* whh, const float
 // directions, r | z | n each); whh [2][3072][1024]; bhh [2][3072]; H [B][T][2048]
 void launch_gru1024(const float* G, int B, int T, const float* whh, const float* bhh, float* H, hipStream_t s);
 
+// Cnn14_DecisionLevelAtt's decision-level stage (decision.hip), one launch, fp32 in every precision mode:
+// H[b][t] = relu(b1 + W1 P[b][t]), P[b][t] = max_pool1d(3, 1, 1)(S)[b][t] + avg_pool1d(3, 1, 1)(S)[b][t]
+// over the clip's own T frames (the file's header states P's arithmetic and every output's summation
+// order).  S [B][T][2048] (block 6's frequency mean, >= 0); W1 [2048][2048] = fc1.weight; H [B][T][2048]
+void launch_decision(const float* S, int B, int T, const float* W1, const float* b1, float* H, hipStream_t s);
+
 // MHA core: QKV [B][T][1536] (q|k|v, head h = cols 64h..64h+63) -> O [B][T][512]
 void launch_mha(const float* QKV, int B, int T, float* O, hipStream_t s);
 

@@ -27,6 +27,7 @@ static bool model_parts(int32_t model_type, int* seq, int* head) {
     case SEDX_MODEL_CONFORMER_FRAMEAVG: *seq = SEQ_CONFORMER, *head = HEAD_FC_AVG; return true;
     case SEDX_MODEL_GRU14_FRAMEATT: *seq = SEQ_GRU, *head = HEAD_ATT; return true;
     case SEDX_MODEL_TRANSFORMER14_FRAMEATT: *seq = SEQ_MHA, *head = HEAD_ATT; return true;
+    case SEDX_MODEL_CNN14_DECISIONLEVELATT: *seq = SEQ_NONE, *head = HEAD_ATT; return true;
     default: return false;
   }
 }
@@ -34,7 +35,11 @@ static bool model_parts(int32_t model_type, int* seq, int* head) {
 bool make_model(const sedx_config& cfg, Model* m) {
   if (!model_parts(cfg.model_type, &m->seq, &m->head)) return false;
   m->cfg = cfg;
-  m->depth = cfg.model_type == SEDX_MODEL_GRU14_FRAMEATT || cfg.model_type == SEDX_MODEL_TRANSFORMER14_FRAMEATT ? 14 : 9;
+  m->decision = cfg.model_type == SEDX_MODEL_CNN14_DECISIONLEVELATT;
+  m->depth = cfg.model_type == SEDX_MODEL_GRU14_FRAMEATT || cfg.model_type == SEDX_MODEL_TRANSFORMER14_FRAMEATT ||
+                     m->decision
+                 ? 14
+                 : 9;
   m->hw = m->depth == 14 ? 2048 : m->seq == SEQ_CONFORMER ? CF_D : 512;
   m->nac = (((m->head == HEAD_ATT ? 2 : 1) * cfg.classes_num + 63) / 64) * 64;
   return true;
@@ -133,6 +138,10 @@ std::map<std::string, std::vector<int64_t>> expected_params(const Model& m) {
   } else {
     e["fc.weight"] = {C, m.hw};         // nn.Linear(512, classes_num) (models.py:247, :332, :503, :921; 144: :1500)
     e["fc.bias"] = {C};
+  }
+  if (m.decision) {
+    e["fc1.weight"] = {m.hw, m.hw};   // nn.Linear(2048, 2048) (models.py:2722)
+    e["fc1.bias"] = {m.hw};
   }
   if (m.seq == SEQ_GRU) {
     // nn.GRU(512, 256), or nn.GRU(2048, 1024) on the 14-layer trunk (models.py:727)
@@ -591,6 +600,12 @@ sedx_status prepare_weights(const Model& m, const Params& P, DevWeights* Wp, Wei
     blob->add(&W.bqkv, bqkv.data(), bqkv.size());
     blob->add(&W.wfc, get("multihead.fc.weight").data(), (size_t)hw * 512);
     blob->add(&W.bfc, get("multihead.fc.bias").data(), (size_t)hw);
+  }
+  if (m.decision) {
+    // fc1 as it stands (decision.hip reads row n of [2048][2048] along k), in the slots of the
+    // MultiHead fc this model does not have
+    blob->add(&W.wfc, get("fc1.weight").data(), (size_t)hw * hw);
+    blob->add(&W.bfc, get("fc1.bias").data(), (size_t)hw);
   }
 
   std::vector<float> wac, bac;

@@ -27,6 +27,8 @@ constexpr int CF_D = 144;        // adim
 constexpr int CF_FF = 576;       // eunits
 constexpr int CF_BLOCKS = 3;     // elayers
 constexpr int CF_MAX_T = 5000;   // rows of the positional table pe (PositionalEncoding max_len)
+constexpr int MAX_CLASSES = 256;            // sedx_create's limit ...
+constexpr int DECISION_MAX_CLASSES = 527;   // ... and Cnn14_DecisionLevelAtt's (AudioSet)
 // 14-layer trunk: the launches of conv_deep.hip (block 4's conv2, blocks 5-6)
 constexpr int DEEP_LAYERS = 5;
 constexpr int DEEP_CK = 16;      // input channels per K chunk
@@ -56,6 +58,9 @@ struct Model {
   int depth = 9;       // conv layers of the trunk: 9, or 14 (blocks 5-6 and five pools: T/32 sequence frames)
   int hw = 512;        // width of the head's input: 512, 144 after the Conformer encoder, 2048 on the 14-layer trunk
   int nac = 64;        // rows of the head projection: att|cla (2C) or fc (C), rounded up to 64
+  // Cnn14_DecisionLevelAtt: between the trunk and the head, max + avg pooling over 3 sequence frames and
+  // fc1 = Linear(2048, 2048) + ReLU (decision.hip); T - 1 framewise frames, no embedding output
+  bool decision = false;
 };
 // cfg -> Model (seq, head, hw, nac); false for an unknown model_type
 bool make_model(const sedx_config& cfg, Model* m);
@@ -127,8 +132,8 @@ struct DevWeights {
   float* bhh = nullptr;    // [2][768]; [2][3072]
   float* wqkv = nullptr;   // [1536][512]; 14-layer: [1536][2048]
   float* bqkv = nullptr;
-  float* wfc = nullptr;    // [512][512]; 14-layer: [2048][512]
-  float* bfc = nullptr;
+  float* wfc = nullptr;    // [512][512]; 14-layer: [2048][512]; Cnn14_DecisionLevelAtt (no MultiHead): fc1.weight
+  float* bfc = nullptr;    //   as it stands [2048][2048] and fc1.bias [2048]
   float* wac = nullptr;    // [nac][hw]
   float* bac = nullptr;
   // Conformer encoder (fp32 in every mode)

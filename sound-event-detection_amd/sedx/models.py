@@ -16,7 +16,10 @@ encoder_type="Conformer", pooling="token", layer_init="pytorch")`` and
 ``forward(x, mixup_lambda=None, timeshift=False, spec_augment=True,
 mask=None)``), and the two models on the 14-layer trunk
 (``Cnn_14layers_Gru_FrameAtt``, ``Cnn_14layers_Transformer_FrameAtt``: eight
-constructor arguments, 25 classes).  The submodules are parameter containers; the whole eval-mode forward runs in
+constructor arguments, 25 classes), and ``Cnn14_DecisionLevelAtt`` (the PANNs
+architecture: seven constructor arguments, up to 527 classes,
+``forward(input, mixup_lambda=None)`` returning the reference's two keys, no
+``'embedding'``).  The submodules are parameter containers; the whole eval-mode forward runs in
 libsedx (HIP kernels for gfx950) through the C ABI in include/sedx.h.  There
 is no CPU or eager-PyTorch fallback: a non-HIP input raises.
 
@@ -42,7 +45,7 @@ from . import _lib
 from .stft import Spectrogram, LogmelFilterBank
 
 __all__ = ['Cnn_9layers_Gru_FrameAtt', 'Cnn_9layers_Transformer_FrameAtt',
-           'Cnn_14layers_Gru_FrameAtt', 'Cnn_14layers_Transformer_FrameAtt',
+           'Cnn_14layers_Gru_FrameAtt', 'Cnn_14layers_Transformer_FrameAtt', 'Cnn14_DecisionLevelAtt',
            'Cnn_9layers_FrameMax', 'Cnn_9layers_FrameAvg', 'Cnn_9layers_FrameAtt',
            'Cnn_9layers_Gru_FrameAvg', 'Cnn_9layers_Transformer_FrameAvg',
            'Cnn_9layers_Conformer_FrameAtt', 'Cnn_9layers_Conformer_FrameAvg', 'ConformerEncoder', 'ConvBlock',
@@ -54,7 +57,8 @@ MODEL_IDS = {'Cnn_9layers_Gru_FrameAtt': 0, 'Cnn_9layers_Transformer_FrameAtt': 
              'Cnn_9layers_FrameMax': 2, 'Cnn_9layers_FrameAvg': 3, 'Cnn_9layers_FrameAtt': 4,
              'Cnn_9layers_Gru_FrameAvg': 5, 'Cnn_9layers_Transformer_FrameAvg': 6,
              'Cnn_9layers_Conformer_FrameAtt': 7, 'Cnn_9layers_Conformer_FrameAvg': 8,
-             'Cnn_14layers_Gru_FrameAtt': 10, 'Cnn_14layers_Transformer_FrameAtt': 11}   # 9 is not assigned
+             'Cnn_14layers_Gru_FrameAtt': 10, 'Cnn_14layers_Transformer_FrameAtt': 11,   # 9 is not assigned
+             'Cnn14_DecisionLevelAtt': 13}                                              # nor is 12
 FEATURE_IDS = {'logmel': 0, 'gamma': 1}
 
 
@@ -396,6 +400,7 @@ class _SedModel(nn.Module):
     # 512-channel input (batch, 512, seq)
     _embedding_cla = False
     _embedding_width = 512     # 144 after the Conformer encoder
+    _has_embedding = True      # False: the reference's forward returns no 'embedding' (Cnn14_DecisionLevelAtt)
 
     def __init__(self, sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num,
                  feature_type='logmel'):
@@ -586,7 +591,7 @@ class _SedModel(nn.Module):
         fw = torch.empty((B, fr.value, C), dtype=torch.float32, device=dev)
         clip = torch.empty((B, C), dtype=torch.float32, device=dev)
         emb_shape = (B, C, sl.value) if self._embedding_cla else (B, self._embedding_width, sl.value)
-        emb = torch.empty(emb_shape, dtype=torch.float32, device=dev)
+        emb = torch.empty(emb_shape, dtype=torch.float32, device=dev) if self._has_embedding else None
         wsz = ctypes.c_size_t()
         _lib.check(L.sedx_workspace_size(nat.h, B, length, ctypes.byref(wsz)), nat.h, 'workspace_size')
         ws = torch.empty(wsz.value, dtype=torch.uint8, device=dev)
@@ -595,6 +600,8 @@ class _SedModel(nn.Module):
             L.sedx_forward_i16 if i16 else L.sedx_forward)
         _lib.check(fn(nat.h, _ptr(x), B, length, _ptr(fw), _ptr(clip), _ptr(emb), _ptr(ws),
                       wsz.value, stream), nat.h, 'forward')
+        if emb is None:
+            return {'framewise_output': fw, 'clipwise_output': clip}
         return {'framewise_output': fw, 'clipwise_output': clip, 'embedding': emb}
 
 
@@ -819,3 +826,33 @@ class Cnn_14layers_Transformer_FrameAtt(_Deep14Model):
         self.multihead = MultiHead(8, 2048, 64, 64, 0.2)
         self.att_block = AttBlock(n_in=2048, n_out=25, activation='sigmoid')
         init_bn(self.bn0)
+
+
+class Cnn14_DecisionLevelAtt(_SedModel):
+    """pytorch/models.py:2685-2783, the PANNs architecture: the 14-layer trunk,
+    ``max_pool1d(3, 1, 1) + avg_pool1d(3, 1, 1)`` over the
+    ``data_length // hop // 32`` sequence frames, ``fc1 = Linear(2048, 2048)`` +
+    ReLU and ``AttBlock(2048, classes_num)`` at the constructor's class count
+    (up to 527: AudioSet at 32 kHz is ``(32000, 1024, 320, 64, 50, 14000,
+    527)``).  Seven constructor arguments (always logmel) and
+    ``forward(input, mixup_lambda=None)`` returning ``framewise_output``
+    (batch, T - 1, classes: every sequence frame x32, then the last frame
+    repeated) and ``clipwise_output`` only.  An input of fewer than 32 frames, or
+    of a multiple of 32 frames (``T = data_length // hop + 1``), raises as the
+    reference does.  Block 4's conv2, blocks 5-6, the pooling, ``fc1`` and the
+    head run fp32 in every precision mode."""
+    _model_name = 'Cnn14_DecisionLevelAtt'
+    _has_embedding = False
+
+    def __init__(self, sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num):
+        super().__init__(sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num,
+                         'logmel')
+        self.conv_block5 = ConvBlock(512, 1024)
+        self.conv_block6 = ConvBlock(1024, 2048)
+        self.fc1 = nn.Linear(2048, 2048, bias=True)
+        self.att_block = AttBlock(n_in=2048, n_out=classes_num, activation='sigmoid')
+        init_bn(self.bn0)
+        init_layer(self.fc1)
+
+    def forward(self, input, mixup_lambda=None):
+        return super().forward(input, mixup_lambda=mixup_lambda)

@@ -50,6 +50,7 @@ MODEL_PARTS = {
     'Cnn_9layers_Conformer_FrameAvg': ('conformer', 'fc'),
     'Cnn_14layers_Gru_FrameAtt': ('gru', 'att'),
     'Cnn_14layers_Transformer_FrameAtt': ('mha', 'att'),
+    'Cnn14_DecisionLevelAtt': ('fc1', 'att'),
 }
 # the weight seed of every model's golden fixtures (tests/golden/)
 GOLDEN_SEEDS = {
@@ -78,6 +79,13 @@ CONFORMER_GOLDEN_SEEDS = {
 DEEP14_GOLDEN_SEEDS = {
     'Cnn_14layers_Gru_FrameAtt': 19,
     'Cnn_14layers_Transformer_FrameAtt': 10,
+}
+# Cnn14_DecisionLevelAtt's (tests/golden/cnn14_*): ``pytorch/models.py:2685-2783``.  A seed at which the
+# reference's windowed output keeps every event-deciding value at least 1e-4 from its threshold
+# (tools/make_golden_cnn14.py asserts it and records the margin in cnn14_meta.json; with seed 12 some value
+# sat within 3e-5 of a threshold on each of 450 waveforms tried, with seed 0 the first waveform clears 5e-4)
+CNN14_GOLDEN_SEEDS = {
+    'Cnn14_DecisionLevelAtt': 0,
 }
 CONFORMER_DIM, CONFORMER_FF, CONFORMER_BLOCKS, CONFORMER_HEADS, CONFORMER_KERNEL = 144, 576, 3, 4, 7
 
@@ -134,7 +142,7 @@ def _conformer_encoder(rng):
 
 def make_state_dict(model_type, classes_num=25, seed=0):
     """Return {key: np.ndarray} for the non-frontend parameters of one of the
-    nine 9-layer models or the two 14-layer ones (``MODEL_PARTS``).  Draw order: the trunk, the
+    nine 9-layer models, the two 14-layer ones or ``Cnn14_DecisionLevelAtt`` (``MODEL_PARTS``).  Draw order: the trunk, the
     sequence layer's tensors, the head's (so two models with one seed share
     every tensor up to the first that differs).  ``Cnn_9layers_FrameAtt``'s
     AttBlock has 25 classes whatever ``classes_num`` is (models.py:416), and so
@@ -146,8 +154,10 @@ def make_state_dict(model_type, classes_num=25, seed=0):
         raise ValueError('unknown model_type %r' % model_type)
     seq, head = MODEL_PARTS[model_type]
     ctor_classes = classes_num
-    deep = model_type in DEEP14_GOLDEN_SEEDS      # AttBlock(2048, 25) too (models.py:730, :1123)
-    if model_type in ('Cnn_9layers_FrameAtt', 'Cnn_9layers_Conformer_FrameAtt') or deep:
+    fixed25 = model_type in DEEP14_GOLDEN_SEEDS   # AttBlock(2048, 25) too (models.py:730, :1123)
+    # the 14-layer trunk; Cnn14_DecisionLevelAtt's AttBlock has the caller's class count (:2723)
+    deep = fixed25 or model_type in CNN14_GOLDEN_SEEDS
+    if model_type in ('Cnn_9layers_FrameAtt', 'Cnn_9layers_Conformer_FrameAtt') or fixed25:
         classes_num = 25
     width = CONFORMER_DIM if seq == 'conformer' else 2048 if deep else 512
     hid = width // 2                              # nn.GRU(512, 256) / nn.GRU(2048, 1024)
@@ -184,6 +194,11 @@ def make_state_dict(model_type, classes_num=25, seed=0):
         sd['multihead.fc.bias'] = rng.uniform(-0.05, 0.05, width).astype(np.float32)
     elif seq == 'conformer':
         sd.update(_conformer_encoder(rng))
+    elif seq == 'fc1':
+        # nn.Linear(2048, 2048) with init_layer's xavier weight (models.py:2722, :2729); a small drawn bias
+        # (init_layer's is zero) so that the bias path is exercised
+        sd['fc1.weight'] = _xavier_uniform(rng, (width, width), width, width)
+        sd['fc1.bias'] = rng.uniform(-0.1, 0.1, width).astype(np.float32)
     if head == 'fc':
         # nn.Linear(512, classes_num) with init_layer's xavier weight
         # (models.py:247, :253); a negative bias like cla's below
