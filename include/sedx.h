@@ -619,6 +619,63 @@ sedx_status sedx_segment_counts_device(const float* d_x, int64_t n_clips, int64_
                                        const int64_t* n_smooth, const int64_t* n_salt,
                                        int64_t* d_counts, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* Average precision (pytorch/evaluate.py:24, :76 call
+ * sklearn.metrics.average_precision_score: the non-interpolated AP), per class,
+ * as a ranking: a segmented radix sort on the device (csrc/rank.hip), a stable
+ * sort on the host (csrc/rank_host.cpp).  For one class with M samples, float32
+ * scores s_i and labels y_i (target != 0):
+ *   ordering    by float32 VALUE, descending, compared as numbers: -0.0 and
+ *               +0.0 are one threshold; distinct denormals are distinct
+ *               thresholds (nothing is flushed)
+ *   thresholds  t_1 > ... > t_K the distinct values; n_k = #{i : s_i >= t_k},
+ *               tp_k = #{i : s_i >= t_k, y_i = 1}, tp_0 = 0, P = tp_K
+ *   AP          sum over k = 1..K of
+ *                 ((double)(tp_k - tp_{k-1}) / (double)P) * ((double)tp_k / (double)n_k)
+ *               in float64, in ONE order, the same on the host and the device
+ *               and independent of C, of the class's column and of any launch
+ *               geometry: 64 consecutive terms (k = 64 q + 1 .. 64 q + 64,
+ *               missing ones +0.0) are added by the tree a[j] += a[j + off],
+ *               off = 32, 16, 8, 4, 2, 1; 64 consecutive such sums by the same
+ *               tree; the resulting sums (one per 4096 terms) in ascending
+ *               order, starting from +0.0.  The order of equal scores among
+ *               themselves never matters: the curve is read only at the end
+ *               of each run of equal scores.
+ *   P = 0       AP = NaN: the reference's environment (Python 3.7) has an
+ *               sklearn that divides 0 / 0 there, which is why it takes
+ *               np.nanmean (main_strong.py:313-323); recent sklearn returns
+ *               0.0 with a warning instead.  info still holds (0, K, 0).
+ *   non-finite  sklearn raises ValueError for NaN / +-inf scores.  Here a class
+ *               with any has AP = NaN, K = 0, no curve written, and its count
+ *               in info; the other classes are unaffected.  The host entry
+ *               then returns SEDX_EINVAL (all outputs are filled) and the
+ *               message counts them; the device entry is asynchronous and
+ *               returns SEDX_OK: its caller reads info.
+ *   scores  float32 [M][C], target uint8 [M][C], as they lie, class fastest
+ *           (a framewise [N][T][C] tensor is [N T][C])
+ *   ap      float64 [C]
+ *   info    int64 [C][3] = (P, K, number of non-finite scores)
+ *   thr / tp / n   optional curve, all three or none (NULL): float32 / int32 /
+ *           int32 [C][M], the first K of each row valid: t_k descending (a
+ *           zero threshold as +0.0), tp_k, n_k
+ * 1 <= M < 2^31 and 1 <= C <= 65535; anything else, a null pointer or a
+ * workspace smaller than the size query's answer returns SEDX_EINVAL with a
+ * per-thread message (the handle-free message of sedx_last_error).  The device
+ * entry is asynchronous on `stream` (the device that owns the pointers must be
+ * current), never synchronises and zeroes what it accumulates.  Classes are
+ * ranked in groups of max(1, min(C, 2^22 / M)) so the workspace stays bounded:
+ * about 14 bytes per (sample, class of a group) plus 1 KiB per (tile, class of
+ * a group).  The tile is the number of keys one workgroup takes per radix pass
+ * (tests aim at its boundaries). */
+sedx_status sedx_average_precision(const float* h_scores, const uint8_t* h_target, int64_t M, int64_t C,
+                                   double* h_ap, int64_t* h_info,
+                                   float* h_thr, int32_t* h_tp, int32_t* h_n);
+sedx_status sedx_average_precision_workspace_size(int64_t M, int64_t C, size_t* bytes);
+sedx_status sedx_average_precision_device(const float* d_scores, const uint8_t* d_target, int64_t M, int64_t C,
+                                          double* d_ap, int64_t* d_info,
+                                          float* d_thr, int32_t* d_tp, int32_t* d_n,
+                                          void* d_workspace, size_t workspace_bytes, void* stream);
+int64_t sedx_rank_tile(void);
+
 /* ------------------------------------------------------------------------
  * Input side: librosa.core.load(path, sr, mono=True) as
  * pytorch/predict.py:295 and pytorch/main_strong.py:787 call it

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/sedx.h"
+#include "rank.h"
 #include "sedx_internal.h"
 
 using namespace sedx;
@@ -474,7 +475,10 @@ sedx_status sedx_set_precision(sedx_handle* h, int32_t mode) {
 
 const char* sedx_last_error(const sedx_handle* h) {
   if (h) return h->err.c_str();
-  const char* seg = segment_error();                // handle-free segment-count entry points
+  // handle-free entry points: average precision (cleared by a later
+  // segment-count failure, so the latest of the two is reported), segment counts
+  if (const char* rank = rank_error()) return rank;
+  const char* seg = segment_error();
   return seg ? seg : "null handle";
 }
 

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/sedx.h"
+#include "rank.h"
 
 namespace sedx {
 
@@ -26,6 +27,7 @@ sedx_status segment_fail(const char* fmt, ...) {
   vsnprintf(buf, sizeof(buf), fmt, ap);
   va_end(ap);
   g_segment_error = buf;
+  rank_error_clear();   // sedx_last_error(NULL) reports the latest failure of either family
   return SEDX_EINVAL;
 }
 

@@ -25,7 +25,9 @@ EXPORTS = ['sedx_create', 'sedx_destroy', 'sedx_last_error', 'sedx_version', 'se
            'sedx_forward_i16', 'sedx_wav_parse', 'sedx_wav_decode_mono', 'sedx_resample_size',
            'sedx_resample_workspace_size', 'sedx_resample', 'sedx_gamma_workspace_size',
            'sedx_set_tuning', 'sedx_set_capture', 'sedx_window_starts', 'sedx_merge_host', 'sedx_check_error',
-           'sedx_abi_version', 'sedx_conv_launch_plan']
+           'sedx_abi_version', 'sedx_conv_launch_plan',
+           'sedx_average_precision', 'sedx_average_precision_workspace_size', 'sedx_average_precision_device',
+           'sedx_rank_tile']
 TUNE_GRU_KERNEL, TUNE_GRU_HANDOFF, TUNE_WINO_BLOCK1, TUNE_MEL_MFMA, TUNE_GRU_SPIN, TUNE_WINO_ORDER = 0, 1, 2, 3, 4, 5
 TUNE_GAMMA_SPEC = 6
 TUNE_WINO_F43 = 7
@@ -138,6 +140,10 @@ def lib():
         'sedx_segment_counts': ([P, I64, I64, I64, P, I64, I64, P, P, P, P, P], I32),
         'sedx_segment_counts_workspace_size': ([I64, I64, I64, I64, PSZ], I32),
         'sedx_segment_counts_device': ([P, I64, I64, I64, P, I64, I64, P, P, P, P, P, P, SZ, P], I32),
+        'sedx_average_precision': ([P, P, I64, I64, P, P, P, P, P], I32),
+        'sedx_average_precision_workspace_size': ([I64, I64, PSZ], I32),
+        'sedx_average_precision_device': ([P, P, I64, I64, P, P, P, P, P, P, SZ, P], I32),
+        'sedx_rank_tile': ([], I64),
         'sedx_set_profiling': ([P, I32], I32),
         'sedx_set_precision': ([P, I32], I32),
         'sedx_set_pipelined': ([P, I32], I32),
