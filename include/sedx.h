@@ -196,6 +196,30 @@ typedef struct sedx_conv_launch {
 sedx_status sedx_conv_launch_plan(const sedx_handle* h, int64_t B, int64_t L_or_T, int32_t ncu,
                                   sedx_conv_launch* rows, int32_t capacity, int32_t* n_rows);
 
+/* The GEMM launches of the sequence layer (stage 9) and the head (stage 10) of
+ * a forward of (B, L) at the handle's current precision, in launch order
+ * (read-only; no launch, no output depends on any of it).  Rows of the fp32
+ * GEMM launcher carry the kernel it picks for M = B * seq_len rows on `ncu`
+ * CUs and its grid; rows of the split-bf16 and Conformer GEMM launchers carry
+ * the GEMM only (grid 0).  Cnn14_DecisionLevelAtt's fused pooling + fc1 launch
+ * is not a GEMM launcher's: its one row is the head projection.  ncu, capacity
+ * and *n_rows as for the conv query above, and the same refusals. */
+typedef enum sedx_gemm_kernel {
+  SEDX_GEMM_TILED = 0,     /* 128 x 64 tiles through LDS, 256 threads */
+  SEDX_GEMM_ONE_WAVE = 1,  /* 32 x 32 tiles, one wave each, operands from L2 */
+  SEDX_GEMM_KSPLIT = 2,    /* 32 x 32 tiles, four waves on K quarters (N <= 64: the AttBlock / fc projection) */
+  SEDX_GEMM_X3 = 3,        /* the split-bf16 launcher (9-layer models, SEDX_PRECISION_X3) */
+  SEDX_GEMM_CONFORMER = 4  /* the Conformer encoder's launcher */
+} sedx_gemm_kernel;
+typedef struct sedx_gemm_launch {
+  int32_t stage;             /* 9 sequence layer, 10 head */
+  int32_t M, K, N, act;      /* C [M][N] = act(A [M][K] W^T + b); act 1 = ReLU (Conformer rows: 0, its own epilogues) */
+  int32_t kernel;            /* sedx_gemm_kernel */
+  int32_t grid_x, grid_y;    /* workgroups over rows and columns */
+} sedx_gemm_launch;
+sedx_status sedx_gemm_launch_plan(const sedx_handle* h, int64_t B, int64_t L_or_T, int32_t ncu,
+                                  sedx_gemm_launch* rows, int32_t capacity, int32_t* n_rows);
+
 /* Model forward (eval mode): replaces Cnn_9layers_*_FrameAtt.forward(input)
  * (pytorch/models.py:625-688, :1029-1077).
  *   d_wave       [B, L]                         (logmel models)

@@ -351,7 +351,9 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
   float* Hs = ws + p.Hs.off;
   float* O = ws + p.O.off;
   float* LG = ws + p.LG.off;
-  // GEMMs: x3 split-bf16 MFMA in x3 mode, fp32 MFMA in exact mode
+  // GEMMs: x3 split-bf16 MFMA in x3 mode, fp32 MFMA in exact mode.  (Their
+  // order from here to the head finish is what plan_gemm_launches lists,
+  // plan.cpp: sedx_gemm_launch_plan's rows.)
   auto linear = [&](const float* a, const float* wf, void* wx, int n, int bn, const float* bias, float* c,
                     int act) {
     if (x3)
@@ -735,6 +737,28 @@ sedx_status sedx_conv_launch_plan(const sedx_handle* h, int64_t B, int64_t L_or_
   }
   *n_rows = n;
   if (n > capacity) return fail(h, SEDX_EINVAL, "%d conv launches: capacity %d", n, capacity);
+  return SEDX_OK;
+}
+
+sedx_status sedx_gemm_launch_plan(const sedx_handle* h, int64_t B, int64_t L_or_T, int32_t ncu,
+                                  sedx_gemm_launch* rows, int32_t capacity, int32_t* n_rows) {
+  if (!h || !n_rows || B <= 0 || capacity < 0 || (capacity && !rows)) return SEDX_EINVAL;
+  *n_rows = 0;
+  Geometry g;
+  if (sedx_status st = query_geometry(h, L_or_T, &g)) return st;
+  ForwardPlan p;
+  if (const char* why = plan_forward(*h, h->tune, B, g.T, &p)) return fail(h, SEDX_EINVAL, "%s", why);
+  if (ncu <= 0) {
+    DeviceGuard dg(h->device);
+    ncu = device_cus();
+  }
+  int n = 0;
+  for (const GemmRow& r : plan_gemm_launches(*h, h->tune, p, ncu)) {   // run_body's launch order
+    if (n < capacity) rows[n] = sedx_gemm_launch{r.stage, r.M, r.K, r.N, r.act, r.l.kernel, r.l.grid_x, r.l.grid_y};
+    ++n;
+  }
+  *n_rows = n;
+  if (n > capacity) return fail(h, SEDX_EINVAL, "%d GEMM launches: capacity %d", n, capacity);
   return SEDX_OK;
 }
 

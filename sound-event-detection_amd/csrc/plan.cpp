@@ -320,6 +320,58 @@ bool conv_launch_family(const ForwardPlan& p, int i, WinoFamily* family) {
   return b1 || (i > 0 && (p.family == CONV_WINO || p.family == CONV_WINO43));
 }
 
+// ---- one fp32 GEMM launch -----------------------------------------------------
+GemmLaunch plan_linear_launch(int M, int K, int N, int act, int ncu) {
+  const int tx = (M + 127) / 128, ty = N / 64;   // the tiled kernel's grid
+  const int sx = (M + 31) / 32, sy = N / 32;     // 32 x 32 tiles
+  if (N <= 64 && act == 0 && K % 256 == 0 && N % 32 == 0)   // the head projection, every M
+    return GemmLaunch{GEMM_KSPLIT, sx, sy, 256};
+  // one wave per 32 x 32 tile while the tiled grid would leave CUs without a workgroup
+  if ((int64_t)tx * ty < ncu && K % 64 == 0 && N % 32 == 0) return GemmLaunch{GEMM_ONE_WAVE, sx, sy, 64};
+  return GemmLaunch{GEMM_TILED, tx, ty, 256};
+}
+
+std::vector<GemmRow> plan_gemm_launches(const Model& m, const Tuning& t, const ForwardPlan& p, int ncu) {
+  std::vector<GemmRow> rows;
+  const int M = p.M, T3 = (int)p.g.Ts;
+  const bool deep = m.depth == 14;
+  // launch_linear's rows are planned; the 9-layer families' GEMMs run launch_linear_x3 in x3 mode
+  auto fp32 = [&](int stage, int K, int N, int act) {
+    rows.push_back(GemmRow{stage, M, K, N, act, plan_linear_launch(M, K, N, act, ncu)});
+  };
+  auto linear = [&](int stage, int N, int act) {
+    if (t.precision == SEDX_PRECISION_X3) rows.push_back(GemmRow{stage, M, 512, N, act, GemmLaunch{GEMM_X3, 0, 0, 0}});
+    else fp32(stage, 512, N, act);
+  };
+  auto cf = [&](int stage, int Mr, int K, int N) {
+    rows.push_back(GemmRow{stage, Mr, K, N, 0, GemmLaunch{GEMM_CONFORMER, 0, 0, 0}});
+  };
+  if (m.decision) {
+    // launch_decision pools inside its own fc1 staging: not a GEMM launcher's launch
+  } else if (deep) {
+    if (m.seq == SEQ_GRU) fp32(9, 2048, 6144, 0);
+    else fp32(9, 2048, 1536, 0), fp32(9, 512, 2048, 1);
+  } else if (m.seq == SEQ_CONFORMER) {
+    for (int b = 0; b < CF_BLOCKS; ++b) cf(9, T3, CF_D, CF_D);   // r_net of every block
+    cf(9, M, 512, CF_D);                                         // input layer
+    for (int b = 0; b < CF_BLOCKS; ++b) {
+      cf(9, M, CF_D, CF_FF), cf(9, M, CF_FF, CF_D);              // ffn1
+      cf(9, M, CF_D, 3 * CF_D), cf(9, M, CF_D, CF_D);            // mhsa: qkv_net, o_net
+      cf(9, M, CF_D, 2 * CF_D), cf(9, M, CF_D, CF_D);            // conv module: the two pointwise convs
+      cf(9, M, CF_D, CF_FF), cf(9, M, CF_FF, CF_D);              // ffn2
+    }
+  } else if (m.seq == SEQ_GRU) {
+    linear(9, 1536, 0);
+  } else if (m.seq == SEQ_MHA) {
+    linear(9, 1536, 0), linear(9, 512, 1);
+  }
+  // the head projection
+  if (m.seq == SEQ_CONFORMER) cf(10, M, CF_D, m.nac);
+  else if (deep) fp32(10, 2048, m.nac, 0);
+  else linear(10, m.nac, 0);
+  return rows;
+}
+
 const char* window_geometry(const Model& m, int64_t L_clip, const sedx_window_spec* spec, bool avg, WinGeom* wg) {
   if (!spec) return "null window spec";
   const int sr = m.cfg.sample_rate;

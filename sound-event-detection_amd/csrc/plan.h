@@ -2,8 +2,8 @@
 // layer and the recurrence, and where everything lives in the workspace.
 // api.cpp launches from it and sizes the workspace by it, so what a forward
 // writes and what sedx_workspace_size asks for cannot drift apart.  Also what
-// a Winograd conv launch looks like (plan_conv_launch: the launchers ask it), the
-// windowed drivers' loop, merge plan (windows.cpp) and device-area layout.
+// a Winograd conv launch looks like (plan_conv_launch: the launchers ask it), which
+// kernel an fp32 GEMM launch runs (plan_linear_launch), the windowed drivers' loop, merge plan (windows.cpp) and device-area layout.
 // Plain C++: no HIP header, so the plans build and run without a GPU
 // (tests/native/asan_driver.cpp).
 #pragma once
@@ -157,6 +157,31 @@ ConvLaunch plan_conv_launch(WinoFamily family, int ncu, int64_t B, int T, int F,
 // the Winograd launcher of stage 2 + i of a forward plan; false: the exact or
 // x3 launchers run it (they keep their own shape choice)
 bool conv_launch_family(const ForwardPlan& p, int i, WinoFamily* family);
+
+// ---- one fp32 GEMM launch (seq.hip launch_linear) ----------------------------
+// Which of launch_linear's kernels runs C [M][N] = act(A [M][K] W^T + b) and on
+// what grid.  Every kernel chains an output's k in ascending pairs from zero
+// (the K-split one per K quarter), so the choice between the tiled and the
+// one-wave kernel changes no output bit; the K-split kernel takes the head
+// projection at every M.  No device: sedx_gemm_launch_plan answers for any CU count.
+enum GemmKernel {
+  GEMM_TILED = SEDX_GEMM_TILED,         // linear_kernel: 128 x 64 tiles, 256 threads
+  GEMM_ONE_WAVE = SEDX_GEMM_ONE_WAVE,   // linear_small_kernel<act, 1>: 32 x 32 tiles, one wave
+  GEMM_KSPLIT = SEDX_GEMM_KSPLIT,       // linear_small_kernel<0, 4>: 32 x 32 tiles, four waves on K quarters
+  GEMM_X3 = SEDX_GEMM_X3,               // launch_linear_x3 and launch_cf_gemm keep their own shape choice:
+  GEMM_CONFORMER = SEDX_GEMM_CONFORMER  // their rows carry the GEMM only
+};
+struct GemmLaunch {
+  int kernel = GEMM_TILED, grid_x = 0, grid_y = 0, threads = 0;
+};
+GemmLaunch plan_linear_launch(int M, int K, int N, int act, int ncu);
+// the GEMM launches of a forward plan's sequence layer (stage 9) and head
+// (stage 10) in run_body's launch order (api.cpp)
+struct GemmRow {
+  int stage, M, K, N, act;
+  GemmLaunch l;
+};
+std::vector<GemmRow> plan_gemm_launches(const Model& m, const Tuning& t, const ForwardPlan& p, int ncu);
 
 // ---- windowed drivers (windows.cpp) ------------------------------------------
 // loop control of predict.py:297-338 / main_strong.py:786-832: the sample

@@ -181,22 +181,19 @@ __global__ __launch_bounds__(64 * KS) void linear_small_kernel(const float* __re
 
 void launch_linear(const float* A, int M, int K, const float* W, int N, const float* bias,
                    float* C, int act, hipStream_t s) {
-  dim3 grid((M + 127) / 128, N / 64);
-  const int ncu = device_cus();
-  const dim3 g2((M + 31) / 32, N / 32);
-  if (N <= 64 && act == 0 && K % 256 == 0 && N % 32 == 0)   // the head projection, every M
-    return launch_kernel(linear_small_kernel<0, 4>, g2, 256, s, A, M, K, W, N, bias, C);
-  if ((int64_t)grid.x * grid.y < ncu && K % 64 == 0 && N % 32 == 0) {
-    if (act == 1)
-      launch_kernel(linear_small_kernel<1, 1>, g2, 64, s, A, M, K, W, N, bias, C);
-    else
-      launch_kernel(linear_small_kernel<0, 1>, g2, 64, s, A, M, K, W, N, bias, C);
-    return;
-  }
-  if (act == 1)
-    launch_kernel(linear_kernel<1>, grid, 256, s, A, M, K, W, N, bias, C);
+  // which kernel and grid: the host plan (plan.cpp), which sedx_gemm_launch_plan reads too
+  const GemmLaunch p = plan_linear_launch(M, K, N, act, device_cus());
+  const dim3 grid(p.grid_x, p.grid_y);
+  if (p.kernel == GEMM_KSPLIT)
+    launch_kernel(linear_small_kernel<0, 4>, grid, p.threads, s, A, M, K, W, N, bias, C);
+  else if (p.kernel == GEMM_ONE_WAVE && act == 1)
+    launch_kernel(linear_small_kernel<1, 1>, grid, p.threads, s, A, M, K, W, N, bias, C);
+  else if (p.kernel == GEMM_ONE_WAVE)
+    launch_kernel(linear_small_kernel<0, 1>, grid, p.threads, s, A, M, K, W, N, bias, C);
+  else if (act == 1)
+    launch_kernel(linear_kernel<1>, grid, p.threads, s, A, M, K, W, N, bias, C);
   else
-    launch_kernel(linear_kernel<0>, grid, 256, s, A, M, K, W, N, bias, C);
+    launch_kernel(linear_kernel<0>, grid, p.threads, s, A, M, K, W, N, bias, C);
 }
 
 // ---------------------------------------------------------------------------

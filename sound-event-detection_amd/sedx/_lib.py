@@ -25,7 +25,7 @@ EXPORTS = ['sedx_create', 'sedx_destroy', 'sedx_last_error', 'sedx_version', 'se
            'sedx_forward_i16', 'sedx_wav_parse', 'sedx_wav_decode_mono', 'sedx_resample_size',
            'sedx_resample_workspace_size', 'sedx_resample', 'sedx_gamma_workspace_size',
            'sedx_set_tuning', 'sedx_set_capture', 'sedx_window_starts', 'sedx_merge_host', 'sedx_check_error',
-           'sedx_abi_version', 'sedx_conv_launch_plan',
+           'sedx_abi_version', 'sedx_conv_launch_plan', 'sedx_gemm_launch_plan',
            'sedx_average_precision', 'sedx_average_precision_workspace_size', 'sedx_average_precision_device',
            'sedx_rank_tile']
 TUNE_GRU_KERNEL, TUNE_GRU_HANDOFF, TUNE_WINO_BLOCK1, TUNE_MEL_MFMA, TUNE_GRU_SPIN, TUNE_WINO_ORDER = 0, 1, 2, 3, 4, 5
@@ -78,6 +78,14 @@ class SedxConvLaunch(ctypes.Structure):
 CONV_FAMILY = {'exact': 0, 'x3': 1, 'f23': 2, 'f23_block1': 3, 'f43': 4}
 
 
+class SedxGemmLaunch(ctypes.Structure):
+    """sedx_gemm_launch: one GEMM launch of the sequence layer or the head (sedx_gemm_launch_plan)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ('stage', 'M', 'K', 'N', 'act', 'kernel', 'grid_x', 'grid_y')]
+
+
+GEMM_KERNEL = {'tiled': 0, 'one_wave': 1, 'ksplit': 2, 'x3': 3, 'conformer': 4}
+
+
 class SedxConfig(ctypes.Structure):
     _fields_ = [('model_type', ctypes.c_int32), ('feature_type', ctypes.c_int32),
                 ('sample_rate', ctypes.c_int32), ('window_size', ctypes.c_int32),
@@ -119,6 +127,7 @@ def lib():
         'sedx_output_geometry': ([P, I64, PI64, PI64], I32),
         'sedx_workspace_size': ([P, I64, I64, PSZ], I32),
         'sedx_conv_launch_plan': ([P, I64, I64, I32, ctypes.POINTER(SedxConvLaunch), I32, ctypes.POINTER(I32)], I32),
+        'sedx_gemm_launch_plan': ([P, I64, I64, I32, ctypes.POINTER(SedxGemmLaunch), I32, ctypes.POINTER(I32)], I32),
         'sedx_forward': ([P, P, I64, I64, P, P, P, P, SZ, P], I32),
         'sedx_forward_features': ([P, P, I64, I64, P, P, P, P, SZ, P], I32),
         'sedx_forward_i16': ([P, P, I64, I64, P, P, P, P, SZ, P], I32),

@@ -144,6 +144,70 @@ def chain_conv_fp32(sd, k, j, x, pixels):
     return F.relu(acc + b[None, :])
 
 
+# ---------------------------------------------------------------------------
+# the 14-layer GRU's summation order, emulated in fp32 on the CPU
+# ---------------------------------------------------------------------------
+def _fma_chains(a, w):
+    """[..., N, K] x [..., M, K] -> [..., N, M] fp32: every output ONE in-order
+    fma chain from zero over k ascending (v_mfma_f32_32x32x2_f32 applied to
+    ascending k pairs: D = fma(a_k1, b_k1, fma(a_k0, b_k0, C))).  An fma is a
+    float64 product (exact for fp32 operands) and sum rounded to fp32."""
+    a64 = np.ascontiguousarray(np.moveaxis(np.asarray(a, np.float64), -1, 0))      # [K, ..., N]
+    w64 = np.ascontiguousarray(np.moveaxis(np.asarray(w, np.float64), -1, 0))      # [K, ..., M]
+    acc64 = np.zeros(a64.shape[1:] + w64.shape[-1:], np.float64)
+    acc32 = acc64.astype(np.float32)
+    tmp = np.empty_like(acc64)
+    for k in range(a64.shape[0]):
+        np.multiply(a64[k][..., :, None], w64[k][..., None, :], out=tmp)
+        np.add(acc64, tmp, out=acc64)
+        acc32[...] = acc64
+        acc64[...] = acc32
+    return acc32
+
+
+def emulate_gru14(sd, x, clip, n):
+    """Stage 9 of Cnn_14layers_Gru_FrameAtt on stage 43 ``x`` [B, 2048, T5]
+    (fp32) the way the library sums it, for one clip: the forward direction's
+    first n = min(n, T5) frames and the reverse direction's last n (each
+    direction's h_t needs only the frames it has already walked).
+      input projection (csrc/seq.hip, both GEMM kernels): per output ONE
+        in-order fma chain over the 2048 k from zero, then + b_ih;
+      recurrent product (csrc/gru1024.hip): four chains, one per K quarter of
+        256, combined ((q0 + q1) + q2) + q3; step 0 has no product;
+      gates as the kernel writes them, in fp32: r = sigmoid(gr + (ar + br)),
+        z likewise, n = tanh(gn + r (an + bn)), h = n + z (h_prev - n), with
+        numpy's fp32 exp / tanh (the device's differ by an ulp or two).
+    ``sd`` float64.  Returns (fwd [n, 1024], rev [n, 1024]) fp32: frames
+    0 .. n-1 of H[:, :1024] and frames T5-n .. T5-1 of H[:, 1024:]."""
+    f32 = np.float32
+    xt = x[clip].t().contiguous().numpy().astype(f32)                  # [T5, 2048]
+    T5 = xt.shape[0]
+    n = min(n, T5)
+    sig = lambda v: (f32(1) / (f32(1) + np.exp(-v, dtype=f32))).astype(f32)
+    out = []
+    for sfx, rows in (('', xt[:n]), ('_reverse', xt[T5 - n:][::-1])):
+        g = lambda name: O._t(sd['gru.' + name + '_l0' + sfx]).numpy().astype(f32)
+        wih, whh, bih, bhh = g('weight_ih'), g('weight_hh'), g('bias_ih'), g('bias_hh')
+        G = _fma_chains(rows, wih) + bih[None, :]                        # [n, 3072], in walking order
+        wq = np.ascontiguousarray(whh.reshape(3072, 4, 256).transpose(1, 0, 2))   # [4, 3072, 256]
+        h = np.zeros(1024, f32)
+        hs = []
+        for s in range(n):
+            if s == 0:
+                a = np.zeros(3072, f32)
+            else:
+                p = _fma_chains(h.reshape(4, 1, 256), wq)[:, 0, :]     # [4, 3072]
+                a = ((p[0] + p[1]) + p[2]) + p[3]
+            ab = a + bhh
+            r = sig(G[s, :1024] + ab[:1024])
+            z = sig(G[s, 1024:2048] + ab[1024:2048])
+            nn = np.tanh(G[s, 2048:] + r * ab[2048:], dtype=f32)
+            h = (nn + z * (h - nn)).astype(f32)
+            hs.append(h)
+        out.append(np.stack(hs))
+    return torch.from_numpy(out[0]), torch.from_numpy(out[1][::-1].copy())
+
+
 def emulate_step(sd, nxt, k, x, n_pix, seed=0):
     """The library's output of conv step -> ``nxt`` at up to ``n_pix`` sampled
     OUTPUT pixels, from chain_conv_fp32 and the kernel's epilogue

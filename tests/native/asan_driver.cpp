@@ -19,7 +19,10 @@
 //  * the Winograd conv launch plan (plan_conv_launch): over families, layers,
 //    batch sizes, lengths, CU counts and knobs, every launch of a split batch
 //    inside the kernels' 32-bit offsets, the grid and the item order within
-//    what the item decode assumes, and every refusal an expected one.
+//    what the item decode assumes, and every refusal an expected one;
+//  * the fp32 GEMM launch plan (plan_linear_launch): over the sequence and head
+//    GEMMs, row counts at every kernel switch and CU counts, the grid covering
+//    the output exactly in the chosen kernel's tiles.
 // Any memory error, undefined behaviour or failed check aborts the process
 // (non-zero exit).
 #include <cmath>
@@ -762,6 +765,32 @@ int check_launch_plans() {
                 }
   return n;
 }
+
+// plan_linear_launch over the sequence and head GEMMs at both sides of every
+// kernel switch: the grid covers C [M][N] exactly once in the kernel's tiles,
+// and the kernel's own conditions on K and N hold
+int check_gemm_plans() {
+  struct Gemm { int K, N, act; };
+  static const Gemm gemms[7] = {{2048, 6144, 0}, {2048, 1536, 0}, {512, 2048, 1}, {2048, 64, 0},
+                                {512, 1536, 0},  {512, 512, 1},   {512, 128, 0}};
+  int n = 0;
+  for (const Gemm& g : gemms)
+    for (int M : {1, 128, 256, 257, 896, 897, 1280, 1281, 1408})
+      for (int ncu : {1, 7, 8, 64, 256, 304}) {
+        const GemmLaunch p = plan_linear_launch(M, g.K, g.N, g.act, ncu);
+        const bool tiled = p.kernel == GEMM_TILED;
+        CHECK(tiled || p.kernel == GEMM_ONE_WAVE || p.kernel == GEMM_KSPLIT, "kernel %d", p.kernel);
+        const int tm = tiled ? 128 : 32, tn = tiled ? 64 : 32;
+        CHECK(p.grid_x >= 1 && (int64_t)p.grid_x * tm >= M && (int64_t)(p.grid_x - 1) * tm < M, "M %d: %d row tiles of %d", M, p.grid_x, tm);
+        CHECK(p.grid_y * tn == g.N, "N %d: %d column tiles of %d", g.N, p.grid_y, tn);
+        CHECK(p.threads == (p.kernel == GEMM_ONE_WAVE ? 64 : 256), "threads %d", p.threads);
+        CHECK(g.K % (tiled ? 16 : p.kernel == GEMM_KSPLIT ? 256 : 64) == 0, "K %d in kernel %d", g.K, p.kernel);
+        CHECK((p.kernel == GEMM_KSPLIT) == (g.N <= 64 && g.act == 0), "K-split at N %d act %d", g.N, g.act);
+        CHECK(p.kernel == GEMM_KSPLIT || tiled == ((int64_t)((M + 127) / 128) * (g.N / 64) >= ncu), "M %d N %d on %d CUs: kernel %d", M, g.N, ncu, p.kernel);
+        ++n;
+      }
+  return n;
+}
 }  // namespace
 
 int main() {
@@ -831,7 +860,9 @@ int main() {
   const int weight_checks = check_weights();
   const int plan_checks = check_plans();
   const int launch_checks = check_launch_plans();
+  const int gemm_checks = check_gemm_plans();
   std::printf("asan_driver: %d wav_parse cases (%d accepted), %d vad cases, %d weight-pack checks, %d plan checks, "
-              "%d conv launch plans: clean\n", cases, ok, vad_cases, weight_checks, plan_checks, launch_checks);
+              "%d conv launch plans, %d GEMM launch plans: clean\n", cases, ok, vad_cases, weight_checks, plan_checks,
+              launch_checks, gemm_checks);
   return 0;
 }

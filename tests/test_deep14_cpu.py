@@ -109,6 +109,24 @@ def test_abi_and_enum_values():
             L.sedx_destroy(h)
 
 
+@pytest.mark.parametrize('T5,n', [(1, 16), (5, 3)])
+def test_emulated_gru_order_is_the_gru_step(T5, n):
+    """deep14_refs.emulate_gru14 (the library's summation order in fp32, the
+    e_alg of tests/test_gpu_deep14_seq.py) computes the float64 step: both
+    directions' sampled frames within fp32 rounding of it (outputs <= 1; the
+    2048-term chains round at most 2048 2^-24 relative, far above what is seen)."""
+    s64 = D.state(D.GRU14, torch.float64)
+    x = torch.rand(2, 2048, T5, generator=torch.Generator().manual_seed(T5))
+    with torch.no_grad():
+        r = D.step_seq(s64, D.GRU14, x.double())
+    fwd, rev = D.emulate_gru14(s64, x, 1, n)
+    k = min(n, T5)
+    assert fwd.shape == rev.shape == (k, 1024) and fwd.dtype == torch.float32
+    e = max(float((fwd.double() - r[1, :k, :1024]).abs().max()), float((rev.double() - r[1, T5 - k:, 1024:]).abs().max()))
+    print('emulated order vs float64: max|d| = %.3g' % e)
+    assert 0 < e <= 1e-5
+
+
 @pytest.mark.skipif(shutil.which('g++') is None, reason='needs g++')
 def test_host_side_under_sanitizers():
     r = subprocess.run(['make', '-s', '-C', PKG, 'asan-deep14'], capture_output=True, text=True, timeout=600)

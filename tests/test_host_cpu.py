@@ -279,6 +279,113 @@ def test_conv_launch_plan_refusals():
     assert b'capacity' in _lib.lib().sedx_last_error(LP._h())
 
 
+GEMM_MS = (1, 128, 256, 257, 896, 897, 1280, 1281, 1408)
+
+
+def _gemm_rule(M, K, N, act, ncu):
+    """The fp32 GEMM launcher's rule, restated: (kernel, grid_x, grid_y)."""
+    up = lambda a, b: (a + b - 1) // b
+    if N <= 64 and act == 0 and K % 256 == 0 and N % 32 == 0:      # the head projection, every M
+        return 'ksplit', up(M, 32), N // 32
+    if up(M, 128) * (N // 64) < ncu and K % 64 == 0 and N % 32 == 0:   # the 128 x 64 tiles leave CUs empty
+        return 'one_wave', up(M, 32), N // 32
+    return 'tiled', up(M, 128), N // 64
+
+
+def test_gemm_launch_plan_is_the_restated_rule():
+    """sedx_gemm_launch_plan (no GPU) equals, field by field, the launcher's
+    rule written out above, at 256 CUs (and 64, 304) for M at both sides of
+    every switch between the one-wave and the tiled kernel, on the two 14-layer
+    handles and a 9-layer one; M = B clips of one sequence frame, and the same
+    M as B / 32 clips of 32 sequence frames."""
+    import launch_plan as LP
+    gemms = {LP.GRU14: [(9, 2048, 6144, 0), (10, 2048, 64, 0)],
+             LP.TRF14: [(9, 2048, 1536, 0), (9, 512, 2048, 1), (10, 2048, 64, 0)],
+             LP.GRU9: [(9, 512, 1536, 0), (10, 512, 64, 0)]}
+    for mt, want in gemms.items():
+        t1 = 8 if mt == LP.GRU9 else 32                     # frames of one sequence frame
+        for ncu in (256, 64, 304):
+            for M in GEMM_MS:
+                shapes = [(M, t1)] + ([(M // 32, 32 * t1)] if M % 32 == 0 else [])
+                for B, T in shapes:
+                    st, rows, n = LP.gemm_launches(mt, B, T, ncu)
+                    assert st == 0 and n == len(rows) == len(want), (mt, B, T, st, n)
+                    for r, (stage, K, N, act) in zip(rows, want):
+                        kern, gx, gy = _gemm_rule(M, K, N, act, ncu)
+                        assert r == {'stage': stage, 'M': M, 'K': K, 'N': N, 'act': act, 'kernel': kern,
+                                     'grid_x': gx, 'grid_y': gy}, (mt, B, T, ncu, r)
+
+
+def test_gemm_kernel_thresholds_at_256_cus():
+    """Where the tiled kernel takes over on a 256-CU device, as literals: the
+    14-layer GRU projection (N = 6144) from M = 257, the 14-layer Transformer's
+    q|k|v projection (N = 1536) from 1281 and its fc (N = 2048) from 897, the
+    9-layer projections (K = 512, N = 1536) from 1281; the head projection is
+    the K-split kernel at every M."""
+    import launch_plan as LP
+    first_tiled = {(LP.GRU14, 'gru-proj'): 257, (LP.TRF14, 'mha-qkv'): 1281, (LP.TRF14, 'mha-fc'): 897,
+                   (LP.GRU9, 'gru-proj'): 1281}
+    for (mt, name), m0 in first_tiled.items():
+        t1 = 8 if mt == LP.GRU9 else 32
+        for M in GEMM_MS + (m0 - 1, m0, 2048):
+            k = LP.gemm_kernels(mt, M, t1, 256)
+            assert k[name] == ('tiled' if M >= m0 else 'one_wave'), (mt, name, M, k)
+            assert k['head'] == 'ksplit'
+    # a batch of 32 ten-second clips (T5 = 31, M = 992)
+    assert LP.gemm_kernels(LP.GRU14, 32, 1001, 256) == {'gru-proj': 'tiled', 'head': 'ksplit'}
+    assert LP.gemm_kernels(LP.TRF14, 32, 1001, 256) == {'mha-qkv': 'one_wave', 'mha-fc': 'tiled', 'head': 'ksplit'}
+    assert LP.gemm_reachable(LP.GRU14, 256) == {('gru-proj', 'one_wave'), ('gru-proj', 'tiled'), ('head', 'ksplit')}
+    assert LP.gemm_reachable(LP.TRF14, 256) == {('mha-qkv', 'one_wave'), ('mha-qkv', 'tiled'), ('mha-fc', 'one_wave'),
+                                                ('mha-fc', 'tiled'), ('head', 'ksplit')}
+
+
+def test_gemm_launch_plan_answers_for_every_model_family():
+    """One row per GEMM launch of the sequence layer and head of every model
+    type, in launch order; the split-bf16 and Conformer launchers' rows carry
+    the GEMM only."""
+    import launch_plan as LP
+    # model type -> (stage, K, N, act) rows at 25 classes
+    proj, fc, att, fch = (9, 512, 1536, 0), (9, 512, 512, 1), (10, 512, 64, 0), (10, 512, 64, 0)
+    cf_block = [(9, 144, 576, 0), (9, 576, 144, 0), (9, 144, 432, 0), (9, 144, 144, 0), (9, 144, 288, 0),
+                (9, 144, 144, 0), (9, 144, 576, 0), (9, 576, 144, 0)]
+    cf = [(9, 144, 144, 0)] * 3 + [(9, 512, 144, 0)] + cf_block * 3 + [(10, 144, 64, 0)]
+    want = {0: [proj, att], 1: [proj, fc, att], 2: [fch], 3: [fch], 4: [att], 5: [proj, fch], 6: [proj, fc, fch],
+            7: cf, 8: cf, 10: [(9, 2048, 6144, 0), (10, 2048, 64, 0)],
+            11: [(9, 2048, 1536, 0), (9, 512, 2048, 1), (10, 2048, 64, 0)], 13: [(10, 2048, 64, 0)]}
+    B, T = 3, 65                                            # T3 = 8, T5 = 2; not a multiple of 32 (model 13)
+    for mt, gemms in want.items():
+        M = B * (2 if mt >= 10 else 8)
+        for prec in ('winograd', 'x3'):
+            st, rows, n = LP.gemm_launches(mt, B, T, 256, precision=prec)
+            assert st == 0 and n == len(rows) == len(gemms), (mt, prec, st, n)
+            assert [(r['stage'], r['K'], r['N'], r['act']) for r in rows] == gemms, (mt, prec)
+            for i, r in enumerate(rows):
+                m_row = 8 if mt in (7, 8) and i < 3 else M          # r_net runs on one clip's positions
+                kern = 'conformer' if mt in (7, 8) else 'x3' if prec == 'x3' and mt < 7 else \
+                    _gemm_rule(M, r['K'], r['N'], r['act'], 256)[0]
+                assert r['M'] == m_row and r['kernel'] == kern, (mt, prec, r)
+                assert (r['grid_x'] > 0) == (kern in ('tiled', 'one_wave', 'ksplit')), (mt, prec, r)
+
+
+def test_gemm_launch_plan_refusals():
+    """The conv query's contract: a shape the forward refuses and a row buffer
+    that is too small are SEDX_EINVAL, the latter still reporting the row count."""
+    import ctypes
+    import launch_plan as LP
+    from sedx import _lib
+    assert LP.gemm_launches(LP.TRF14, 2, 31, 256)[0] == 1            # T5 = 0
+    assert LP.gemm_launches(LP.GRU9, 2, 7, 256)[0] == 1              # T3 = 0
+    st, rows, n = LP.gemm_launches(LP.TRF14, 2, 32, 256, capacity=2)
+    assert (st, len(rows), n) == (1, 2, 3)
+    assert b'capacity' in _lib.lib().sedx_last_error(LP.gemm_handle(LP.TRF14))
+    assert LP.gemm_launches(LP.TRF14, 2, 32, 256, capacity=0)[::2] == (1, 3)
+    L, h, k = _lib.lib(), LP.gemm_handle(LP.TRF14), ctypes.c_int32()
+    assert L.sedx_gemm_launch_plan(h, 0, 31 * 160, 256, None, 0, ctypes.byref(k)) == 1    # no clip
+    assert L.sedx_gemm_launch_plan(h, 2, 31 * 160, 256, None, 4, ctypes.byref(k)) == 1    # capacity without rows
+    assert L.sedx_gemm_launch_plan(h, 2, 31 * 160, 256, None, 0, None) == 1
+    assert L.sedx_gemm_launch_plan(None, 2, 31 * 160, 256, None, 0, ctypes.byref(k)) == 1
+
+
 def test_invalid_setter_values_are_einval_before_any_device_call():
     """sedx_set_pipelined / sedx_set_profiling range-check `on` before they
     touch HIP: without a GPU an invalid value is SEDX_EINVAL (1), not the

@@ -8,7 +8,8 @@
 //
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -fno-slp-vectorize -fno-vectorize -Wno-unused-result \
 //     -Isound-event-detection_amd/csrc -o decision_bench tools/decision_bench.cpp \
-//     sound-event-detection_amd/csrc/decision.hip sound-event-detection_amd/csrc/seq.hip
+//     sound-event-detection_amd/csrc/decision.hip sound-event-detection_amd/csrc/seq.hip \
+//     sound-event-detection_amd/csrc/plan.cpp sound-event-detection_amd/csrc/windows.cpp
 //   decision_bench [B ...]        (default 1 32; T5 = 31, a 10 s clip)
 #include <hip/hip_runtime.h>
 #include <cmath>
