@@ -97,7 +97,40 @@ typedef enum {
    * The pooling, fc1 and the head are fp32 in every precision mode; captures:
    * 43 is the pooling's input, 9 is fc1's output [items][T/32][2048], and the
    * timed stage 9 is the one pooling + fc1 launch. */
-  SEDX_MODEL_CNN14_DECISIONLEVELATT = 13
+  SEDX_MODEL_CNN14_DECISIONLEVELATT = 13,
+  /* 14 is not assigned (probed as the first unknown id after 13) */
+  /* The transfer-learning models on the VGGish trunk, pytorch/models.py:2219-2592.
+   * The trunk is six 3x3 convs with bias and ReLU and no BatchNorm (1 -> 64 ->
+   * 128 -> 256 -> 256 -> 512 -> 512) with max_pool2d(2x2) after convs 1, 2, 4
+   * and 6, on the raw log-mel: bn0 is in the state_dict and never applied.  fp32
+   * in every precision mode (sedx_set_precision and the Winograd knobs are
+   * accepted and change nothing in it); the GRU and the head projection run as
+   * on the 9-layer models.  feature_type must be LOGMEL; classes_num is the
+   * head's width (the reference's head has 25 outputs whatever its constructor
+   * is given, and sedx.models passes 25).
+   *   geometry   T = L / hop + 1 frames; each pool floors: seq_len = T / 16;
+   *              out_frames = 1000 always.  The FrameAtt models repeat every
+   *              sequence frame x12, VGGish_FrameAvg x(1000 / seq_len), then the
+   *              last frame is repeated up to 1000 frames; VGGish_FrameAvg's
+   *              clipwise output is the mean over all 1000 padded frames.
+   *   refusals   T < 16 (the fourth pool has no output); seq_len > 83 for the
+   *              two FrameAtt models (the reference's padding count is negative
+   *              and it raises); seq_len > 1000 for VGGish_FrameAvg (a
+   *              deviation: the reference returns an empty tensor and NaN):
+   *              SEDX_EINVAL from the forwards, sedx_output_geometry,
+   *              sedx_workspace_size, the launch plans and the windowed drivers
+   *   keys       the frontend buffers, bn0.* (accepted, unused),
+   *              vggish.0.{0,3,6,8,11,13}.{weight,bias}, gru.* (read by
+   *              VGGISH_GRU_FRAMEATT; accepted and unused by the other two),
+   *              att_block.* or fc.{weight [C][512], bias}
+   *   outputs    d_embedding: cla [B, C, seq_len] (FrameAtt models), the trunk's
+   *              output [B, 512, seq_len] (VGGISH_FRAMEAVG)
+   * Captures 0, 50-55, 8, 9 (sedx_set_capture); timed stages: 1 is conv1 with
+   * its pool, 2-6 the launches of conv2, conv3_1, conv3_2, conv4_1 and conv4_2
+   * (7 and 8 are empty), 9 the GRU, 10 the head. */
+  SEDX_MODEL_VGGISH_FRAMEATT = 15,        /* VGGish_FrameAtt  :2284-2383: AttBlock(512, 25) */
+  SEDX_MODEL_VGGISH_GRU_FRAMEATT = 16,    /* VGGish_Gru_FrameAtt  :2386-2485: nn.GRU(512, 256, bidirectional), AttBlock(512, 25) */
+  SEDX_MODEL_VGGISH_FRAMEAVG = 17         /* VGGish_FrameAvg  :2487-2592: Linear(512, 25), sigmoid */
 } sedx_model;
 
 typedef enum { SEDX_FEATURE_LOGMEL = 0, SEDX_FEATURE_GAMMA = 1 } sedx_feature;
@@ -123,7 +156,7 @@ typedef struct sedx_handle sedx_handle;
  * and the constructors of the other sedx_model values).  feature_type GAMMA is
  * Cnn_9layers_Gru_FrameAtt's alone (Cnn_9layers_Gru_FrameAvg takes the argument
  * and ignores it, :512-518); any other model_type with it is SEDX_EINVAL
- * (the 14-layer models included).  classes_num: 1..256, and up to 527 for
+ * (the 14-layer and the VGGish models included).  classes_num: 1..256, and up to 527 for
  * SEDX_MODEL_CNN14_DECISIONLEVELATT. */
 sedx_status sedx_create(const sedx_config* cfg, int device, sedx_handle** out);
 void sedx_destroy(sedx_handle* h);
@@ -182,7 +215,9 @@ typedef enum sedx_conv_family {
 } sedx_conv_family;
 typedef struct sedx_conv_launch {
   int32_t stage, family;              /* 2..8 (sedx_stage_times' numbering), sedx_conv_family */
-  int32_t T, F, cin, cout, epi;       /* the layer: rows, columns, channels; 0 store, 1 2x2 pool, 2 freq mean */
+  int32_t T, F, cin, cout, epi;       /* the layer: rows, columns, channels; 0 store, 1 2x2 pool, 2 freq mean;
+                                       * the VGGish trunk's rows (stages 2..6, the exact launcher): 3 2x2 max pool,
+                                       * 4 2x2 max pool + mean of the 4 pooled bins */
   int32_t clips;                      /* clips of this launch */
   int32_t tg, nt, c4;                 /* item: tile groups, channel tiles; chunk-of-4 layout */
   int32_t tb_per_clip, ngroups;       /* tile blocks per clip, channel groups */
@@ -569,6 +604,19 @@ sedx_status sedx_set_pipelined(sedx_handle* h, int32_t on);
  * 5-6; stage 9 is the sequence layer alone.  SEDX_MODEL_CNN14_DECISIONLEVELATT
  * has no sequence layer: its 9 is relu(fc1) [items][T/32][2048], computed from
  * 43 by the one pooling + fc1 launch that stage 9 times.
+ * The VGGish models (channels-last):
+ *    0  log-mel (no bn0)              [items][T][64]
+ *   50  conv1 + ReLU + max pool       [items][T/2][32][64]
+ *   51  conv2 + ReLU + max pool       [items][T/4][16][128]
+ *   52  conv3_1 + ReLU                [items][T/4][16][256]
+ *   53  conv3_2 + ReLU + max pool     [items][T/8][8][256]
+ *   54  conv4_1 + ReLU                [items][T/8][8][512]
+ *   55  conv4_2 + ReLU + max pool, before the mean   [items][T/16][4][512]
+ *       (capture-only: one more launch, straight into d_buf, which must hold the whole tensor)
+ *    8  the mean of 55's 4 bins       [items][T/16][512] (the sequence input)
+ *    9  the GRU output (VGGISH_GRU_FRAMEATT), else the same as 8
+ * Their timed stages: 1 conv1, 2..6 the launches 51..54 and 8 in this order, 7
+ * and 8 empty, 9 the GRU, 10 the head.
  * stage < 0 or d_buf == NULL switches capture off. */
 sedx_status sedx_set_capture(sedx_handle* h, int32_t stage, float* d_buf, size_t bytes);
 sedx_status sedx_set_profiling(sedx_handle* h, int32_t on);

@@ -189,6 +189,8 @@ sedx_status query_geometry(const sedx_handle* h, int64_t L_or_T, Geometry* g) {
   // avg_pool2d raises): the queries reject what the forward rejects
   if (h->depth == 14 && g->Ts < 1) return fail(h, SEDX_EINVAL, "input too short for the 5 pooling stages");
   if (decision_pad_negative(*h, g->T)) return fail(h, SEDX_EINVAL, DECISION_PAD_REFUSAL, (long long)g->T);
+  char why[96];   // the VGGish models: what plan_forward refuses, the queries refuse
+  if (vgg_refusal(*h, g->T, why, sizeof(why))) return fail(h, SEDX_EINVAL, "%s", why);
   return SEDX_OK;
 }
 
@@ -287,6 +289,7 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
       case B1_PAD_EXACT:
       case B1_PAD_X3: launch_pad_x0(X0, iB, (int)g.T, A, s); break;
       case B1_F23_FUSED: break;   // conv1 inside the stage-2 launch
+      case B1_VGG: launch_vgg_conv1(X0, iB, (int)g.T, w.c1_w, w.c1_b, A, s); break;   // conv1 + ReLU + max pool
     }
   };
   // the claim counters (the workspace comes from the caller): zeroed once per
@@ -298,11 +301,25 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
   mark(h, 1, s);
   capture(h, 0, X0, (size_t)B * g.T * 64, s);
   if (!first_early) block1_first();
+  if (h->vgg) capture(h, 50, A, (size_t)B * g.T1 * 32 * 64, s);
   for (int i = 0; i < p.nlayers; ++i) {
     const ConvLayer& c = p.layers[i];
     const int k = i + 1;   // the layer's weights
     float* in = ws + c.in;
     float* out = ws + c.out;
+    if (h->vgg) {
+      // VGGish trunk: conv2 .. conv4_2 on the exact fp32 kernel in every mode (stages 2-6; captures 51-54, 8)
+      mark(h, 2 + i, s);
+      launch_conv3x3(in, iB, c.T, c.F, c.cin, c.cout, w.wp[k], w.cb[k], out, c.epi, w.zero, s);
+      capture(h, i == 4 ? 8 : 51 + i, out, (size_t)B * c.To * c.Fo * c.cout, s);
+      // capture 55, conv4_2's pooled output before the mean: the same layer once more with the pool alone,
+      // straight into a buffer that holds all of it
+      const size_t n55 = (size_t)B * c.To * (c.F / 2) * c.cout;
+      if (i == 4 && h->cap_stage == 55 && h->cap_buf && h->cap_bytes >= n55 * sizeof(float))
+        launch_conv3x3(in, iB, c.T, c.F, c.cin, c.cout, w.wp[k], w.cb[k], h->cap_buf, EPI_MAXPOOL2, w.zero, s);
+      if (i == 4) mark(h, 7, s), mark(h, 8, s);   // no launches of their own: stage 6 ends here
+      continue;
+    }
     if (i >= p.first_deep) {
       // 14-layer trunk: block 4's pooled conv2 (stage 8, reading block 4 conv1's
       // layout) and blocks 5-6 (timed inside stage 8; captures 40..43), fp32 in every mode
@@ -442,7 +459,11 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
     launch_linear(HI, M, 2048, w.wac, h->nac, w.bac, LG, 0, s);
   else
     linear(HI, w.wac, w.wac_x3, h->nac, 64, w.bac, LG, 0);
-  if (h->head == HEAD_ATT)
+  if (h->vgg && h->head == HEAD_ATT)   // x12, padded to 1000 frames
+    launch_vgg_att_head(LG, iB, T3, h->cfg.classes_num, h->nac, (int)g.out_frames, g.rep, d_fw, d_clip, d_emb, s);
+  else if (h->vgg)                     // x(1000 // seq_len), padded to 1000 frames, the mean over all of them
+    launch_vgg_fc_head(LG, iB, T3, h->cfg.classes_num, h->nac, (int)g.out_frames, g.rep, d_fw, d_clip, s);
+  else if (h->head == HEAD_ATT)
     launch_att_head(LG, iB, T3, h->cfg.classes_num, h->nac, (int)g.out_frames, d_fw, d_clip,
                     h->emb_cla && !h->decision ? d_emb : nullptr, s, g.rep);
   else
@@ -494,7 +515,9 @@ sedx_status sedx_set_capture(sedx_handle* h, int32_t stage, float* d_buf, size_t
   }
   const bool cf_stage = h->seq == SEQ_CONFORMER && stage >= 20 && stage <= 20 + 4 * CF_BLOCKS;
   const bool deep_stage = h->depth == 14 && stage >= 40 && stage <= 43;   // blocks 5-6 of the 14-layer trunk
-  if (stage == 1 || (stage > 9 && !cf_stage && !deep_stage)) return fail(h, SEDX_EINVAL, "stage %d cannot be captured", (int)stage);
+  const bool vgg_stage = h->vgg && stage >= 50 && stage <= 55;            // the VGGish trunk's launches
+  if (h->vgg && stage >= 1 && stage <= 7) return fail(h, SEDX_EINVAL, "stage %d cannot be captured", (int)stage);
+  if (stage == 1 || (stage > 9 && !cf_stage && !deep_stage && !vgg_stage)) return fail(h, SEDX_EINVAL, "stage %d cannot be captured", (int)stage);
   h->cap_stage = stage;
   h->cap_buf = d_buf;
   h->cap_bytes = bytes;

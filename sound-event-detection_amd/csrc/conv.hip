@@ -9,6 +9,18 @@
 //   EPI_POOL2  avg_pool2d(2x2), floor on odd T (conv2 of blocks 1..3)
 //   EPI_FMEAN  pool 1x1 + torch.mean over the 8 freq bins (conv2 of block 4,
 //              models.py:666-668)
+// and for the VGGish trunk (models.py:2219-2250: conv with bias + ReLU, no BN,
+// so `bias` is the conv's own and the weights are unfolded):
+//   EPI_MAXPOOL2        max_pool2d(2x2), floor on odd T: the maximum of the four
+//                       ReLU outputs of a window (conv2 at F = 32, conv3_2 at
+//                       F = 16; F = 8 for the capture of conv4_2's pooled output)
+//   EPI_MAXPOOL2_FMEAN  the same pool at F = 8, then torch.mean over the 4
+//                       pooled bins p0..p3: (((p0 + p1) + p2) + p3) * 0.25f, one
+//                       fp32 chain in bin order (conv4_2: [B][T/2][Cout])
+// Summation order of every output, whatever the epilogue and the wave-tile
+// shape: chunks of 4 input channels in ascending order; inside a chunk tap
+// 0..8 (tap = 3 dt + df); inside a tap the chunk's channels in ascending
+// order; one fma chain from zero, acc = fma(x, w, acc); then + bias, ReLU.
 //
 // conv3x3_kernel is an implicit GEMM: M = output pixels (a tile = TT rows of
 // t x all F freq bins = 256 pixels; 512 in block 1), N = output channels
@@ -127,12 +139,14 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 && WT == 64 ? 2 : 1) void co
   using accv = typename std::conditional<WT == 16, f32x4, f32x16>::type;
   // WT = 32 pooled: a wave's 32 rows are 2 t-rows x 16 bins, so a 2x2
   // window is registers r, r+1, r+8, r+9 of one lane (as at F = 16)
-  constexpr bool SEG16 = WT == 32 && EPI == EPI_POOL2;
+  constexpr bool MAXP = EPI == EPI_MAXPOOL2 || EPI == EPI_MAXPOOL2_FMEAN;   // the window's maximum, not its average
+  constexpr bool POOLED = EPI == EPI_POOL2 || MAXP;
+  constexpr bool SEG16 = WT == 32 && POOLED;
   // WT = 16: a wave's 16 rows are 2 t-rows x 8 bins; lane quarter q holds rows
   // 4q..4q+3 (t-row q >> 1, bins 4 (q & 1) + r): a 2x2 window spans lanes l
   // and l + 32, an 8-bin mean lanes l and l ^ 16
   constexpr bool SEG8 = WT == 16;
-  static_assert(TT * F == BM && (EPI != EPI_POOL2 || TT % 2 == 0), "tile = whole (pairs of) t-rows");
+  static_assert(TT * F == BM && (!POOLED || TT % 2 == 0), "tile = whole (pairs of) t-rows");
 
   // ALL LDS in one array (a second __shared__ object can make hipcc drain
   // vmcnt before the fragment reads)
@@ -388,7 +402,61 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 && WT == 64 ? 2 : 1) void co
   // EPI_POOL2 / EPI_FMEAN: bias + ReLU, then the 2x2 average / the 8-bin mean
   // in registers (plus one lane-32 swap for the mean) and 128-B row stores;
   // EPI_STORE: through LDS in two passes (float4 stores). ----
-  if constexpr (EPI == EPI_POOL2 && WT == 16) {
+  // the maximum of a 2x2 window's four ReLU outputs (the VGGish trunk's epilogues, first in the chain; the
+  // averaging epilogues below are as they were)
+  [[maybe_unused]] auto max4 = [](float a, float b, float c, float d) { return fmaxf(fmaxf(fmaxf(a, b), c), d); };
+  if constexpr (EPI == EPI_MAXPOOL2 && WT == 16) {
+    // as EPI_POOL2 at WT = 16: rows (t, f), (t, f+1) in registers r, r+1; t-row t+1 in lane l + 32
+    constexpr int FO = F / 2;
+    const int To = T / 2;
+    const int n = n0 + wn * 16 + (lane & 15);
+    const float bv = bias[n];
+    float v4[4], p4[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v4[r] = fmaxf(acc[0][0][r] + bv, 0.0f);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) p4[r] = __shfl_xor(v4[r], 32);
+    if (lane < 32)
+#pragma unroll
+      for (int r = 0; r < 4; r += 2) {
+        const float v = max4(v4[r], v4[r + 1], p4[r], p4[r + 1]);
+        const int m = drow(r);
+        const int to = t0 / 2 + (pix_t(0, m) >> 1), fo = pix_f(0, m) >> 1;
+        if (to < To) out[(((int64_t)b * To + to) * FO + fo) * Cout + n] = v;
+      }
+  } else if constexpr (EPI == EPI_MAXPOOL2 && F >= 16) {
+    // as EPI_POOL2 at WT = 32 / 64: the same registers of one lane hold a window
+    constexpr int FO = F / 2;
+    const int To = T / 2;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      const int n = n0 + wn * WT + nt * 32 + (lane & 31);
+      const float bv = bias[n];
+      auto rl = [&](int mt, int r) { return fmaxf(acc[mt][nt][r] + bv, 0.0f); };
+      if constexpr (F == 16 || SEG16) {
+        // rows m, m+1 (bins), m+16 (next t-row): registers r, r+1, r+8, r+9
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+          for (int r = 0; r < 8; r += 2) {
+            const float v = max4(rl(mt, r), rl(mt, r + 1), rl(mt, r + 8), rl(mt, r + 9));
+            const int m = (r & 3) + 8 * (r >> 2) + 4 * khalf;
+            const int to = t0 / 2 + (pix_t(mt, m) >> 1), fo = pix_f(mt, m) >> 1;
+            if (to < To) out[(((int64_t)b * To + to) * FO + fo) * Cout + n] = v;
+          }
+      } else {
+        // F = 32, 64 x 64 wave tiles: rows m, m+1 (bins) in registers r, r+1; t-rows in mt 0, 1
+        static_assert(MT == 2 && F == 32, "max-pool epilogue: two MFMA row tiles of one t-row each");
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) {
+          const float v = max4(rl(0, r), rl(0, r + 1), rl(1, r), rl(1, r + 1));
+          const int m = (r & 3) + 8 * (r >> 2) + 4 * khalf;
+          const int to = t0 / 2 + (pix_t(0, m) >> 1), fo = pix_f(0, m) >> 1;
+          if (to < To) out[(((int64_t)b * To + to) * FO + fo) * Cout + n] = v;
+        }
+      }
+    }
+  } else if constexpr (EPI == EPI_POOL2 && WT == 16) {
     // rows (t, f), (t, f+1) in registers r, r+1; t-row t+1 in lane l + 32
     constexpr int FO = F / 2;
     const int To = T / 2;
@@ -407,6 +475,24 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 && WT == 64 ? 2 : 1) void co
         const int to = t0 / 2 + (pix_t(0, m) >> 1), fo = pix_f(0, m) >> 1;
         if (to < To) out[(((int64_t)b * To + to) * FO + fo) * Cout + n] = v;
       }
+  } else if constexpr (EPI == EPI_MAXPOOL2_FMEAN && WT == 16) {
+    // lane quarter q: t-row q >> 1, bins 4 (q & 1) + r; the window's other t-row in lane l ^ 32, so a lane
+    // pools bins 2 (q & 1) and 2 (q & 1) + 1 of its row pair; the other two pooled bins in lane l ^ 16
+    static_assert(F == 8, "max-pool + mean epilogue: F = 8");
+    const int To = T / 2;
+    const int n = n0 + wn * 16 + (lane & 15);
+    const float bv = bias[n];
+    float v4[4], p4[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v4[r] = fmaxf(acc[0][0][r] + bv, 0.0f);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) p4[r] = __shfl_xor(v4[r], 32);
+    const float pa = max4(v4[0], v4[1], p4[0], p4[1]), pb = max4(v4[2], v4[3], p4[2], p4[3]);
+    const float oa = __shfl_xor(pa, 16), ob = __shfl_xor(pb, 16);
+    // torch.mean over the 4 pooled bins in order: lane quarter 0 holds p0, p1 and receives p2, p3
+    const float v = (((pa + pb) + oa) + ob) * 0.25f;
+    const int to = t0 / 2 + (pix_t(0, 0) >> 1);
+    if (lane < 16 && to < To) out[((int64_t)b * To + to) * Cout + n] = v;
   } else if constexpr (EPI == EPI_FMEAN && WT == 16) {
     // a lane's 4 bins of one t-row; the other 4 bins in lane l ^ 16
     static_assert(F == 8, "freq-mean epilogue: F = 8");
@@ -420,6 +506,38 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 8 && WT == 64 ? 2 : 1) void co
     const float v = ((q & 1) ? o4 + s4 : s4 + o4) * (1.0f / F);
     const int t = t0 + pix_t(0, 4 * q);
     if ((q & 1) == 0 && t < T) out[((int64_t)b * T + t) * Cout + n] = v;
+  } else if constexpr (MAXP && F == 8) {
+    // a 32-row tile = 4 t-rows x 8 bins: register r of a lane is bin (r & 3) + 4 khalf of t-row r >> 2, so
+    // a lane holds the windows of pooled bins 2 khalf and 2 khalf + 1 of t-row pairs (0, 1) and (2, 3)
+    static_assert(WT == 64, "F = 8 max pool: 64 x 64 wave tiles (or the WT = 16 branches above)");
+    const int To = T / 2;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      const int n = n0 + wn * WT + nt * 32 + (lane & 31);
+      const float bv = bias[n];
+      auto rl = [&](int mt, int r) { return fmaxf(acc[mt][nt][r] + bv, 0.0f); };
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int q = 0; q < 4; q += 2) {
+          const float pa = max4(rl(mt, 4 * q), rl(mt, 4 * q + 1), rl(mt, 4 * q + 4), rl(mt, 4 * q + 5));
+          const float pb = max4(rl(mt, 4 * q + 2), rl(mt, 4 * q + 3), rl(mt, 4 * q + 6), rl(mt, 4 * q + 7));
+          const int to = (t0 + pix_t(mt, 8 * q)) >> 1;
+          if constexpr (EPI == EPI_MAXPOOL2) {
+            if (to < To) {
+              float* o = out + (((int64_t)b * To + to) * 4 + 2 * khalf) * Cout + n;
+              o[0] = pa;
+              o[Cout] = pb;
+            }
+          } else {
+            // torch.mean over the 4 pooled bins p0..p3 in order, (((p0 + p1) + p2) + p3) * 0.25f: half-wave 0
+            // holds p0, p1, half-wave 1 p2, p3 (lane ^ 32); the two row pairs are stored by one half each
+            const float oa = __shfl_xor(pa, 32), ob = __shfl_xor(pb, 32);
+            const float v = (khalf ? ((oa + ob) + pa) + pb : ((pa + pb) + oa) + ob) * 0.25f;
+            if (khalf == (q >> 1) && to < To) out[((int64_t)b * To + to) * Cout + n] = v;
+          }
+        }
+    }
   } else if constexpr (EPI == EPI_POOL2) {
     static_assert(F >= 16, "pooled epilogue: F in {16, 32, 64}");
     constexpr int FO = F / 2;
@@ -529,6 +647,14 @@ static void launch_f_bn_w(const float* in, int B, int T, int Cin, int Cout, cons
     if (epi == EPI_FMEAN) SEDX_EX_LAUNCH(EPI_FMEAN);
   } else {
     if (epi == EPI_POOL2) SEDX_EX_LAUNCH(EPI_POOL2);
+  }
+  // the VGGish trunk's: the max pool at F = 32 (conv2), 16 (conv3_2) and 8 (conv4_2's capture), and
+  // conv4_2's max pool + mean at F = 8
+  if constexpr (!FUSE && F != 64) {
+    if (epi == EPI_MAXPOOL2) SEDX_EX_LAUNCH(EPI_MAXPOOL2);
+  }
+  if constexpr (!FUSE && F == 8) {
+    if (epi == EPI_MAXPOOL2_FMEAN) SEDX_EX_LAUNCH(EPI_MAXPOOL2_FMEAN);
   }
 #undef SEDX_EX_LAUNCH
   note_launch_error(hipErrorInvalidValue);

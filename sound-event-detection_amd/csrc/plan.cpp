@@ -17,6 +17,15 @@ Geometry geometry_from_T(const Model& m, int64_t T) {
   g.T3 = g.T2 / 2;
   g.T4 = g.T3 / 2;
   g.T5 = g.T4 / 2;
+  if (m.vgg) {
+    // four flooring max pools; x12 (models.py:2342, :2444) or x(1000 // seq_len) (:2578), then the last frame
+    // repeated up to exactly 1000 frames (:2376, :2478, :2580-2582).  Shapes no forward runs keep rep 1.
+    g.Ts = g.T4;
+    g.rep = m.head == HEAD_ATT ? VGG_ATT_REPEAT : g.Ts >= 1 && g.Ts <= VGG_OUT_FRAMES ? (int)(VGG_OUT_FRAMES / g.Ts) : 1;
+    g.fw_len = g.rep * g.Ts;
+    g.out_frames = VGG_OUT_FRAMES;
+    return g;
+  }
   const bool deep = m.depth == 14;
   g.Ts = deep ? g.T5 : g.T3;
   g.rep = deep ? 32 : 8;   // interpolate_ratio (models.py:741, :1133)
@@ -36,6 +45,18 @@ Geometry geometry_from_T(const Model& m, int64_t T) {
   return g;
 }
 
+const char* vgg_refusal(const Model& m, int64_t T, char* buf, size_t n) {
+  if (!m.vgg) return nullptr;
+  const int64_t seq = T / 16;
+  if (seq < 1) snprintf(buf, n, "%lld frames: the VGGish trunk's 4 pooling stages need 16", (long long)T);
+  else if (m.head == HEAD_ATT && seq > VGG_ATT_MAX_SEQ)
+    snprintf(buf, n, "%lld sequence frames: x12 passes the 1000-frame output (at most %d)", (long long)seq, VGG_ATT_MAX_SEQ);
+  else if (seq > VGG_OUT_FRAMES)
+    snprintf(buf, n, "%lld sequence frames: VGGish_FrameAvg has 1000 output frames", (long long)seq);
+  else return nullptr;
+  return buf;
+}
+
 namespace {
 // the next region of `floats` floats (or ints)
 Region take(size_t& end, size_t floats) { return Region{carve(end, floats * 4) / 4, floats}; }
@@ -47,8 +68,8 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
   p->B = B;
   p->M = (int)(B * g.Ts);
   const bool deep = m.depth == 14;
-  p->nlayers = deep ? 11 : 7;
-  p->first_deep = deep ? 6 : 7;
+  p->nlayers = m.vgg ? VGG_LAYERS - 1 : deep ? 11 : 7;
+  p->first_deep = m.vgg ? p->nlayers : deep ? 6 : 7;
   // ---- which kernels ----
   const bool wino = t.precision == SEDX_PRECISION_WINOGRAD, x3 = t.precision == SEDX_PRECISION_X3;
   // Winograd block 1 (SEDX_TUNE_WINO_BLOCK1): 1 = conv1's activation
@@ -62,6 +83,8 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
   p->family = x3 ? CONV_X3 : !wino ? CONV_EXACT : t.wino_f43 ? CONV_WINO43 : CONV_WINO;
   p->c4 = wino && t.wino_f43 && t.wino_block1 == 2;
   p->claims = x3 || (p->family == CONV_WINO43 && B >= 8);
+  // the VGGish trunk: launch_vgg_conv1, then launch_conv3x3 on every layer, in every precision mode
+  if (m.vgg) p->block1 = B1_VGG, p->family = CONV_EXACT, p->c4 = false, p->claims = false;
   // AUTO: 16 slices (half the recurrence's serial product); on a pipelined
   // handle dealt over every XCD (spread, below): beside the next batch's conv
   // stack the shorter recurrence then costs it less than the 8-slice kernel's
@@ -79,7 +102,8 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
   p->x0 = take(end, (size_t)B * T * 64);
   const size_t a0 = end;   // A starts here; its three phases (conv stack, head, Conformer) each carve from it
   // conv stack: block 1's first launch into A, then the layers ping-pong P / A
-  size_t a_conv = p->block1 == B1_F23_FUSED                             ? 0
+  size_t a_conv = p->block1 == B1_VGG                                   ? (size_t)B * g.T1 * 32 * 64
+                  : p->block1 == B1_F23_FUSED                           ? 0
                   : p->block1 == B1_PAD_EXACT || p->block1 == B1_PAD_X3 ? block1_pad_floats((int)B, (int)T)
                                                                          : (size_t)B * T * 64 * 64;
   size_t p_conv = 0;
@@ -93,7 +117,18 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
     size_t& ext = i % 2 ? a_conv : p_conv;
     ext = std::max(ext, (size_t)B * p->layers[i].To * p->layers[i].Fo * cout);
   }
-  for (int i = 0; i < (deep ? 6 : 7); ++i) {
+  // VGGish trunk: conv2 .. conv4_2 at (T1, 32), (T2, 16) x 2, (T3, 8) x 2; max pools after conv2, conv3_2 and
+  // conv4_2, the last with the mean of its 4 pooled bins.  A layer's T is the pooled row count of the one
+  // before it, so a row that a flooring pool dropped is nowhere: the next layer's bottom halo is zeros
+  for (int i = 0; m.vgg && i < p->nlayers; ++i) {
+    const int l = i + 1, cout = VGG_COUT[l], blk = (i + 1) / 2, F = 32 >> blk, last = i == 4, pool = i % 2 == 0;
+    const int Tl = (int)(blk == 0 ? g.T1 : blk == 1 ? g.T2 : g.T3);
+    p->layers[i] = ConvLayer{Tl, F, VGG_CIN[l], cout, last ? EPI_MAXPOOL2_FMEAN : pool ? EPI_MAXPOOL2 : EPI_STORE,
+                             pool ? Tl / 2 : Tl, last ? 1 : pool ? F / 2 : F, 0, 0, 0};
+    size_t& ext = i % 2 ? a_conv : p_conv;
+    ext = std::max(ext, (size_t)B * p->layers[i].To * p->layers[i].Fo * cout);
+  }
+  for (int i = 0; !m.vgg && i < (deep ? 6 : 7); ++i) {
     const int blk = (i + 1) / 2, cout = 64 << blk, Tl = (int)Ts[blk], F = 64 >> blk, pool = i % 2 == 0 && i < 6;
     p->layers[i] = ConvLayer{Tl, F, i == 0 ? 64 : i % 2 ? cout / 2 : cout, cout,
                              i == 6 ? EPI_FMEAN : pool ? EPI_POOL2 : EPI_STORE,
@@ -134,7 +169,8 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
   if (p->block1 == B1_F23_FUSED) p->layers[0].in = p->x0.off;
   // ---- shapes no forward runs ----
   p->reject[0] = 0;
-  if (g.T3 < 1) snprintf(p->reject, sizeof(p->reject), "input too short for the 3 pooling stages");
+  if (vgg_refusal(m, T, p->reject, sizeof(p->reject))) {
+  } else if (g.T3 < 1) snprintf(p->reject, sizeof(p->reject), "input too short for the 3 pooling stages");
   else if (g.Ts < 1) snprintf(p->reject, sizeof(p->reject), "input too short for the 5 pooling stages");
   else if (decision_pad_negative(m, T)) snprintf(p->reject, sizeof(p->reject), DECISION_PAD_REFUSAL, (long long)T);
   else if (seq_too_long(m, g.T3))
@@ -314,6 +350,7 @@ ConvLaunch plan_conv_launch(WinoFamily family, int ncu, int64_t B, int T, int F,
 }
 
 bool conv_launch_family(const ForwardPlan& p, int i, WinoFamily* family) {
+  if (p.block1 == B1_VGG) return false;   // launch_conv3x3 on every layer
   const bool b1 = i == 0 && p.block1 != B1_PAD_EXACT && p.block1 != B1_PAD_X3;   // a Winograd stage 2
   if (b1) *family = p.block1 == B1_F23_FUSED ? WINO_F23_BLOCK1 : p.block1 == B1_CONV1_F23 ? WINO_F23 : WINO_F43;
   else *family = p.family == CONV_WINO ? WINO_F23 : WINO_F43;
@@ -403,6 +440,7 @@ const char* window_geometry(const Model& m, int64_t L_clip, const sedx_window_sp
       g.len = len;
       g.g = geometry_from_T(m, conv_T(m, len));
       if (g.g.Ts < 1) return refuse("window %d too short for the CNN", w, 0, 0);
+      if (vgg_refusal(m, g.g.T, wg->reject, sizeof(wg->reject))) return wg->reject;
       if (decision_pad_negative(m, g.g.T))
         return refuse("window %d has %lld frames, a multiple of 32: Cnn14_DecisionLevelAtt has no output for it", w,
                       (long long)g.g.T, 0);

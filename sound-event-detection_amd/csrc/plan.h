@@ -26,7 +26,9 @@ inline size_t carve(size_t& end, size_t bytes) {
 }
 
 // ---- launch contracts the plan shares with the kernels ----------------------
-enum ConvEpi { EPI_STORE = 0, EPI_POOL2 = 1, EPI_FMEAN = 2 };
+// EPI_MAXPOOL2 / EPI_MAXPOOL2_FMEAN: the VGGish trunk's max_pool2d(2x2) (floor on an odd T), the second followed by
+// the mean of the 4 pooled bins at F = 8 (conv.hip; the exact fp32 kernel only)
+enum ConvEpi { EPI_STORE = 0, EPI_POOL2 = 1, EPI_FMEAN = 2, EPI_MAXPOOL2 = 3, EPI_MAXPOOL2_FMEAN = 4 };
 constexpr int CONV_SCHED_INTS = 256;   // per conv launch: 8 tile-claim counters, 128 B apart
 // the zero-bordered bn0 output [B][T+2][66] (launch_pad_x0)
 constexpr size_t block1_pad_floats(int B, int T) { return (size_t)B * (T + 2) * 66; }
@@ -52,6 +54,13 @@ Geometry geometry_from_T(const Model& m, int64_t T);
 inline bool decision_pad_negative(const Model& m, int64_t T) { return m.decision && T >= 32 && T % 32 == 0; }
 constexpr const char* DECISION_PAD_REFUSAL =   // fits ForwardPlan::reject
     "%lld frames: a multiple of 32 has no output (the reference pads by -1 frames)";
+// The VGGish models (models.py:2284-2592): four flooring max pools, T / 16 sequence frames, always 1000 output
+// frames.  Fewer than 16 frames: the fourth pool has no output.  The two FrameAtt models repeat x12 and pad to
+// 1000: past 83 sequence frames the pad count is negative and the reference raises.  VGGish_FrameAvg repeats
+// x(1000 // seq_len): past 1000 sequence frames the reference returns an empty tensor and NaN, refused here.
+constexpr int VGG_OUT_FRAMES = 1000, VGG_ATT_REPEAT = 12, VGG_ATT_MAX_SEQ = VGG_OUT_FRAMES / VGG_ATT_REPEAT;
+// nullptr, or why no VGGish forward runs T frames (written into buf; fits ForwardPlan::reject)
+const char* vgg_refusal(const Model& m, int64_t T, char* buf, size_t n);
 
 // ---- what the handle's setters store ----------------------------------------
 struct Tuning {
@@ -84,6 +93,7 @@ enum Block1Form {
   B1_CONV1_F23,     // launch_conv1_nhwc + launch_conv3x3_wino
   B1_CONV1_F43,     // launch_conv1_nhwc + launch_conv3x3_wino43
   B1_CONV1C4_F43,   // launch_conv1_c4 + launch_conv3x3_wino43 in the chunk-of-4 layout
+  B1_VGG,           // launch_vgg_conv1 (conv 1 -> 64 + bias + ReLU + 2x2 max pool), then launch_conv3x3 on conv2
 };
 enum ConvFamily { CONV_EXACT, CONV_X3, CONV_WINO, CONV_WINO43 };   // layers 2-7
 constexpr int MAX_CONV_LAYERS = 11;   // conv launches after block 1's first: 7, or 11 on the 14-layer trunk
@@ -97,7 +107,8 @@ struct ForwardPlan {
   Geometry g{};
   int64_t B = 0;
   int M = 0;                       // B * Ts: rows of the sequence / head GEMMs
-  // conv launches after block 1's first: 7; the 14-layer trunk's 11, of which
+  // conv launches after block 1's first: 7 (the VGGish trunk's: 5, conv2 .. conv4_2, all launch_conv3x3 in
+  // every precision mode, after launch_vgg_conv1); the 14-layer trunk's 11, of which
   // layers[first_deep ..] run launch_conv3x3_deep (fp32 in every mode; block
   // 4's conv2 reads block 4 conv1's layout, then NHWC)
   int nlayers = 7, first_deep = 7;

@@ -108,6 +108,21 @@ void launch_conv3x3(const float* in, int B, int T, int F, int Cin, int Cout,
                     const float* wp, const float* bias, float* out, int epi,
                     const float* zero16, hipStream_t s);
 
+// The VGGish trunk (models.py:2219-2250; the Model::vgg handles) runs launch_conv3x3 on its convs 2-6 with
+// epi EPI_MAXPOOL2 ([B][T/2][F/2][Cout], F in {32, 16, 8}) and EPI_MAXPOOL2_FMEAN (F = 8: [B][T/2][Cout], the
+// mean of the 4 pooled bins) besides EPI_STORE; bias is then the conv's own (no BN).  Its first layer
+// (conv_vgg.hip): conv 1 -> 64 (w1 [64][9] = vggish.0.0.weight, b1 [64]) + ReLU + max_pool2d(2x2) in one
+// launch: x [B][T][64] (the raw log-mel) -> out [B][T/2][32][64]; the full-resolution activation is never stored.
+void launch_vgg_conv1(const float* x, int B, int T, const float* w1, const float* b1, float* out, hipStream_t s);
+// The VGGish heads (conv_vgg.hip), out_frames = 1000: every one of the T sequence frames `ratio` times, then
+// the last frame up to out_frames.  att: AttBlock's finish on logits [B][T][ldl] (0..C-1 att, C..2C-1 cla),
+// emb_cla [B][C][T] nullable; fc: sigmoid of columns 0..C-1, clipwise = the mean over all out_frames frames.
+// The file's header states every sum's order.
+void launch_vgg_att_head(const float* logits, int B, int T, int C, int ldl, int out_frames, int ratio,
+                         float* framewise, float* clipwise, float* emb_cla, hipStream_t s);
+void launch_vgg_fc_head(const float* logits, int B, int T, int C, int ldl, int out_frames, int ratio,
+                        float* framewise, float* clipwise, hipStream_t s);
+
 // Same contract as fp32 Winograd F(2x2, 3x3) (conv_wino.hip): U from
 // pack_conv_wino (weights.cpp; wf = BN-folded weights [Cout][Cin][9] in float64);
 // F in {64, 32, 16, 8}, Cout % 32 == 0 (F = 64: block 1's conv2, fed by

@@ -28,6 +28,9 @@ static bool model_parts(int32_t model_type, int* seq, int* head) {
     case SEDX_MODEL_GRU14_FRAMEATT: *seq = SEQ_GRU, *head = HEAD_ATT; return true;
     case SEDX_MODEL_TRANSFORMER14_FRAMEATT: *seq = SEQ_MHA, *head = HEAD_ATT; return true;
     case SEDX_MODEL_CNN14_DECISIONLEVELATT: *seq = SEQ_NONE, *head = HEAD_ATT; return true;
+    case SEDX_MODEL_VGGISH_FRAMEATT: *seq = SEQ_NONE, *head = HEAD_ATT; return true;
+    case SEDX_MODEL_VGGISH_GRU_FRAMEATT: *seq = SEQ_GRU, *head = HEAD_ATT; return true;
+    case SEDX_MODEL_VGGISH_FRAMEAVG: *seq = SEQ_NONE, *head = HEAD_FC_AVG; return true;
     default: return false;
   }
 }
@@ -40,12 +43,17 @@ bool make_model(const sedx_config& cfg, Model* m) {
                      m->decision
                  ? 14
                  : 9;
+  m->vgg = cfg.model_type == SEDX_MODEL_VGGISH_FRAMEATT || cfg.model_type == SEDX_MODEL_VGGISH_GRU_FRAMEATT ||
+           cfg.model_type == SEDX_MODEL_VGGISH_FRAMEAVG;
+  if (m->vgg) m->depth = VGG_LAYERS;
   m->hw = m->depth == 14 ? 2048 : m->seq == SEQ_CONFORMER ? CF_D : 512;
   m->nac = (((m->head == HEAD_ATT ? 2 : 1) * cfg.classes_num + 63) / 64) * 64;
   return true;
 }
 
 bool ignored_key(const Model& m, const std::string& k) {
+  // every VGGish class builds nn.GRU(512, 256) (models.py:2318, :2521); only VGGish_Gru_FrameAtt calls it
+  if (m.vgg && m.seq != SEQ_GRU) return k.compare(0, 4, "gru.") == 0;
   if (m.seq != SEQ_CONFORMER) return false;
   return k == "classifier.weight" || k == "classifier.bias" || k == "linear_emb.weight" || k == "linear_emb.bias";
 }
@@ -119,9 +127,14 @@ std::map<std::string, std::vector<int64_t>> expected_params(const Model& m) {
   e["spectrogram_extractor.stft.conv_real.weight"] = {K, 1, m.cfg.window_size};
   e["spectrogram_extractor.stft.conv_imag.weight"] = {K, 1, m.cfg.window_size};
   e["logmel_extractor.melW"] = {K, m.cfg.mel_bins};
-  add_bn(e, "bn0", 64);
+  add_bn(e, "bn0", 64);   // the VGGish models: in the state_dict, never applied (models.py:2347-2349)
   const bool deep = m.depth == 14;
-  for (int k = 1; k <= (deep ? 6 : 4); ++k) {
+  for (int l = 0; m.vgg && l < VGG_LAYERS; ++l) {
+    const std::string p = "vggish.0." + std::to_string(VGG_SEQ_INDEX[l]);
+    e[p + ".weight"] = {VGG_COUT[l], VGG_CIN[l], 3, 3};
+    e[p + ".bias"] = {VGG_COUT[l]};
+  }
+  for (int k = 1; !m.vgg && k <= (deep ? 6 : 4); ++k) {
     const std::string p = "conv_block" + std::to_string(k);
     e[p + ".conv1.weight"] = {CONV_CH[k], CONV_CH[k - 1], 3, 3};
     e[p + ".conv2.weight"] = {CONV_CH[k], CONV_CH[k], 3, 3};
@@ -297,6 +310,14 @@ void pack_conv_exact(const double* wf, int Cin, int Cout, float* out) {
         const int chunk = i / 4, kc = i % 4, ks = kc >> 1, kh = kc & 1;
         out[((((size_t)chunk * 9 + t) * 2 + kh) * Cout + o) * 2 + ks] = (float)wf[((size_t)o * Cin + i) * 9 + t];
       }
+}
+
+// a VGGish conv's weight [Cout][Cin][3][3] as it stands -> pack_conv_exact's layout (fp32 values unchanged)
+std::vector<float> pack_vgg_conv(const float* w, int Cin, int Cout) {
+  const std::vector<double> wf(w, w + (size_t)Cout * Cin * 9);
+  std::vector<float> pk((size_t)Cin * 9 * Cout);
+  pack_conv_exact(wf.data(), Cin, Cout, pk.data());
+  return pk;
 }
 
 static void split_bf16(float x, uint16_t* hi, uint16_t* lo) {
@@ -479,6 +500,8 @@ sedx_status prepare_weights(const Model& m, const Params& P, DevWeights* Wp, Wei
     std::vector<float> mu0, bi0, sc0f(64);
     bn_fold(P, "bn0", 64, s0, mu0, bi0);
     for (int i = 0; i < 64; ++i) sc0f[i] = (float)s0[i];
+    // the VGGish models feed the raw log-mel to the trunk: the frontend's fused multiply-add gets the identity
+    if (m.vgg) sc0f.assign(64, 1.0f), mu0.assign(64, 0.0f), bi0.assign(64, 0.0f);
     blob->add(&W.bn0_scale, sc0f.data(), 64);
     blob->add(&W.bn0_mean, mu0.data(), 64);
     blob->add(&W.bn0_bias, bi0.data(), 64);
@@ -487,7 +510,25 @@ sedx_status prepare_weights(const Model& m, const Params& P, DevWeights* Wp, Wei
   // ---- conv stack: BN folded into the weights in float64, then each layout ----
   const bool deep = m.depth == 14;
   std::vector<float> deep_w, deep_b;
-  for (int k = 1; k <= (deep ? 6 : 4); ++k)
+  // the VGGish trunk: no BatchNorm, the convs' own biases; fp32 in every precision mode, so the exact pack
+  // only.  conv1 in block 1 conv1's slots, convs 2-6 in wp[1..5] / cb[1..5]
+  for (int l = 0; m.vgg && l < VGG_LAYERS; ++l) {
+    const std::string p = "vggish.0." + std::to_string(VGG_SEQ_INDEX[l]);
+    const auto& wt = get(p + ".weight");
+    const auto& bias = get(p + ".bias");
+    if (l == 0) {
+      blob->add(&W.c1_w, wt.data(), wt.size());   // [64][9]
+      blob->add(&W.c1_b, bias.data(), bias.size());
+      const std::vector<float> zeros(std::max(ZERO_BLOCK_FLOATS, 64 * 128), 0.f);
+      blob->add(&W.zero, zeros.data(), (size_t)ZERO_BLOCK_FLOATS);
+      blob->add(&W.trash, zeros.data(), (size_t)64 * 128);
+      continue;
+    }
+    const std::vector<float> pk = pack_vgg_conv(wt.data(), VGG_CIN[l], VGG_COUT[l]);
+    blob->add(&W.wp[l], pk.data(), pk.size());
+    blob->add(&W.cb[l], bias.data(), bias.size());
+  }
+  for (int k = 1; !m.vgg && k <= (deep ? 6 : 4); ++k)
     for (int j = 1; j <= 2; ++j) {
       const std::string p = "conv_block" + std::to_string(k);
       const int cin = (j == 1) ? CONV_CH[k - 1] : CONV_CH[k], cout = CONV_CH[k];

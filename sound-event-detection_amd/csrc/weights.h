@@ -61,7 +61,16 @@ struct Model {
   // Cnn14_DecisionLevelAtt: between the trunk and the head, max + avg pooling over 3 sequence frames and
   // fc1 = Linear(2048, 2048) + ReLU (decision.hip); T - 1 framewise frames, no embedding output
   bool decision = false;
+  // VGGish_FrameAtt / VGGish_Gru_FrameAtt / VGGish_FrameAvg (models.py:2284-2592): the trunk is six 3x3 convs
+  // with bias and ReLU, no BatchNorm (bn0 is never applied either), max pools after convs 1, 2, 4 and 6
+  // (conv_vgg.hip, conv.hip's max-pool epilogues); T / 16 sequence frames, always 1000 output frames
+  bool vgg = false;
 };
+// the VGGish trunk: vggish.0.<VGG_SEQ_INDEX[l]>.{weight, bias} is conv l (nn.Sequential indices of VGGish.features)
+constexpr int VGG_LAYERS = 6;
+constexpr int VGG_SEQ_INDEX[VGG_LAYERS] = {0, 3, 6, 8, 11, 13};
+constexpr int VGG_CIN[VGG_LAYERS] = {1, 64, 128, 256, 256, 512};
+constexpr int VGG_COUT[VGG_LAYERS] = {64, 128, 256, 256, 512, 512};
 // cfg -> Model (seq, head, hw, nac); false for an unknown model_type
 bool make_model(const sedx_config& cfg, Model* m);
 // keys of modules the Conformer models build and never call at inference
@@ -125,6 +134,8 @@ struct DevWeights {
   // 14-layer trunk (conv_deep.hip): wp[7] holds pack_conv_deep of b4c2, b5c1, b5c2, b6c1, b6c2 back to
   // back (layer l at deep_w_off(l)) and cb[7] their folded biases (at deep_b_off(l)); block 4's conv2
   // has no other pack on such a handle and blocks 5-6 no other slot
+  // VGGish trunk (Model::vgg): c1_w / c1_b hold vggish.0.0's weight [64][9] and bias as they stand, wp[l] /
+  // cb[l] (l = 1..5) pack_vgg_conv of conv l and its own bias; bn0_* the identity; no x3 / Winograd packs
   float* w_ih = nullptr;   // [1536][512]; 14-layer: [6144][2048]
   float* b_ih = nullptr;   // [1536]; [6144]
   float* whhT = nullptr;   // [2][256][768] (9-layer only)
@@ -177,6 +188,11 @@ struct WeightBlob {
 // ---- packed layouts (weights.cpp) -------------------------------------------
 // wf = BN-folded weights [Cout][Cin][9] in float64 for the three conv packers
 void pack_conv_exact(const double* wf, int Cin, int Cout, float* out);    // out: Cin * 9 * Cout floats
+std::vector<float> pack_vgg_conv(const float* w, int Cin, int Cout);     // a VGGish conv [Cout][Cin][9] -> the exact layout
+// where pack_conv_exact puts weight (o, i, tap): [Cin/4][9][khalf 2][Cout][ks 2], channel 2 ks + khalf of a chunk
+inline size_t exact_pack_index(int Cout, int o, int i, int tap) {
+  return ((((size_t)(i / 4) * 9 + tap) * 2 + (i & 1)) * Cout + o) * 2 + ((i % 4) >> 1);
+}
 void pack_conv_wino(const double* wf, int Cin, int Cout, float* U);       // U: Cin * Cout * 16 floats
 void pack_conv_wino43(const double* wf, int Cin, int Cout, float* U);     // U: 2 * Cin * Cout * 36 floats
 void pack_conv_deep(const double* wf, int Cin, int Cout, float* out);     // out: Cin * 9 * Cout floats

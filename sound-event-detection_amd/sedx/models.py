@@ -19,7 +19,10 @@ mask=None)``), and the two models on the 14-layer trunk
 constructor arguments, 25 classes), and ``Cnn14_DecisionLevelAtt`` (the PANNs
 architecture: seven constructor arguments, up to 527 classes,
 ``forward(input, mixup_lambda=None)`` returning the reference's two keys, no
-``'embedding'``).  The submodules are parameter containers; the whole eval-mode forward runs in
+``'embedding'``), and the three transfer-learning models on the VGGish trunk
+(``VGGish_FrameAtt``, ``VGGish_Gru_FrameAtt``, ``VGGish_FrameAvg``: ten
+constructor arguments with ``checkpoint_path`` and ``freeze``, 25 classes, always
+1000 output frames).  The submodules are parameter containers; the whole eval-mode forward runs in
 libsedx (HIP kernels for gfx950) through the C ABI in include/sedx.h.  There
 is no CPU or eager-PyTorch fallback: a non-HIP input raises.
 
@@ -46,6 +49,7 @@ from .stft import Spectrogram, LogmelFilterBank
 
 __all__ = ['Cnn_9layers_Gru_FrameAtt', 'Cnn_9layers_Transformer_FrameAtt',
            'Cnn_14layers_Gru_FrameAtt', 'Cnn_14layers_Transformer_FrameAtt', 'Cnn14_DecisionLevelAtt',
+           'VGGish', 'VGGish_FrameAtt', 'VGGish_Gru_FrameAtt', 'VGGish_FrameAvg',
            'Cnn_9layers_FrameMax', 'Cnn_9layers_FrameAvg', 'Cnn_9layers_FrameAtt',
            'Cnn_9layers_Gru_FrameAvg', 'Cnn_9layers_Transformer_FrameAvg',
            'Cnn_9layers_Conformer_FrameAtt', 'Cnn_9layers_Conformer_FrameAvg', 'ConformerEncoder', 'ConvBlock',
@@ -58,7 +62,8 @@ MODEL_IDS = {'Cnn_9layers_Gru_FrameAtt': 0, 'Cnn_9layers_Transformer_FrameAtt': 
              'Cnn_9layers_Gru_FrameAvg': 5, 'Cnn_9layers_Transformer_FrameAvg': 6,
              'Cnn_9layers_Conformer_FrameAtt': 7, 'Cnn_9layers_Conformer_FrameAvg': 8,
              'Cnn_14layers_Gru_FrameAtt': 10, 'Cnn_14layers_Transformer_FrameAtt': 11,   # 9 is not assigned
-             'Cnn14_DecisionLevelAtt': 13}                                              # nor is 12
+             'Cnn14_DecisionLevelAtt': 13,                                              # nor is 12
+             'VGGish_FrameAtt': 15, 'VGGish_Gru_FrameAtt': 16, 'VGGish_FrameAvg': 17}   # nor is 14
 FEATURE_IDS = {'logmel': 0, 'gamma': 1}
 
 
@@ -401,6 +406,7 @@ class _SedModel(nn.Module):
     _embedding_cla = False
     _embedding_width = 512     # 144 after the Conformer encoder
     _has_embedding = True      # False: the reference's forward returns no 'embedding' (Cnn14_DecisionLevelAtt)
+    _cnn9_trunk = True         # False: the class registers its own trunk (the VGGish models)
 
     def __init__(self, sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num,
                  feature_type='logmel'):
@@ -418,10 +424,11 @@ class _SedModel(nn.Module):
                                                  n_mels=mel_bins, fmin=fmin, fmax=fmax, ref=1.0,
                                                  amin=1e-10, top_db=None, freeze_parameters=True)
         self.bn0 = nn.BatchNorm2d(64)
-        self.conv_block1 = ConvBlock(1, 64)
-        self.conv_block2 = ConvBlock(64, 128)
-        self.conv_block3 = ConvBlock(128, 256)
-        self.conv_block4 = ConvBlock(256, 512)
+        if self._cnn9_trunk:
+            self.conv_block1 = ConvBlock(1, 64)
+            self.conv_block2 = ConvBlock(64, 128)
+            self.conv_block3 = ConvBlock(128, 256)
+            self.conv_block4 = ConvBlock(256, 512)
         self._natives = _HandleCache(self)
         self.precision = 'winograd'
         self.pipelined = False
@@ -856,3 +863,115 @@ class Cnn14_DecisionLevelAtt(_SedModel):
 
     def forward(self, input, mixup_lambda=None):
         return super().forward(input, mixup_lambda=mixup_lambda)
+
+
+class VGGish(nn.Module):
+    """pytorch/models.py:2219-2267 (weights only): ``features`` is the conv
+    trunk, six 3x3 convs with bias and ReLU and four 2x2 max pools; ``fc`` is the
+    embedding stack that the three models below drop.  A fresh instance holds
+    the 290 MB of ``fc`` weights a VGGish checkpoint holds."""
+
+    def __init__(self):
+        super().__init__()
+        self.features = _vggish_features()
+        self.fc = nn.Sequential(
+            nn.Linear(512 * 24, 4096), nn.ReLU(inplace=True),
+            nn.Linear(4096, 4096), nn.ReLU(inplace=True),
+            nn.Linear(4096, 128), nn.ReLU(inplace=True))
+
+    def forward(self, x):
+        raise RuntimeError('VGGish is a parameter container: its trunk runs inside the native model forward')
+
+
+def _vggish_features():
+    """VGGish.features (models.py:2230-2250): the Sequential indices 0, 3, 6, 8,
+    11 and 13 are the convs."""
+    return nn.Sequential(
+        nn.Conv2d(1, 64, 3, stride=1, padding=1), nn.ReLU(inplace=True), nn.MaxPool2d(2, stride=2),
+        nn.Conv2d(64, 128, 3, stride=1, padding=1), nn.ReLU(inplace=True), nn.MaxPool2d(2, stride=2),
+        nn.Conv2d(128, 256, 3, stride=1, padding=1), nn.ReLU(inplace=True),
+        nn.Conv2d(256, 256, 3, stride=1, padding=1), nn.ReLU(inplace=True), nn.MaxPool2d(2, stride=2),
+        nn.Conv2d(256, 512, 3, stride=1, padding=1), nn.ReLU(inplace=True),
+        nn.Conv2d(512, 512, 3, stride=1, padding=1), nn.ReLU(inplace=True), nn.MaxPool2d(2, stride=2))
+
+
+class _VGGishModel(_SedModel):
+    """The three transfer-learning classes (pytorch/models.py:2284-2592): the
+    reference's ten constructor arguments and ``forward(input,
+    mixup_lambda=None, timeshift=False, spec_augment=True)``.  The trunk is
+    ``VGGish.features`` on the raw log-mel (``bn0`` is in the state_dict and is
+    never applied), four flooring 2x2 max pools: ``T // 16`` sequence frames of
+    512 channels for ``T = data_length // hop + 1``.  The head has 25 outputs
+    whatever ``classes_num`` is (:2323, :2425, :2526) and ``feature_type`` is
+    ignored.  Every class builds ``nn.GRU(512, 256, bidirectional)``; only
+    ``VGGish_Gru_FrameAtt`` calls it.  The framewise output always has 1000
+    frames.  The trunk runs fp32 in every precision mode.
+
+    ``checkpoint_path`` is loaded as the reference does (``init_weights``:
+    ``torch.load`` of a full ``VGGish().state_dict()``, ``features.*`` kept as
+    ``vggish.0.*``, ``fc.*`` dropped).  ``checkpoint_path=None`` skips the load
+    (an extension, for callers that load a full state_dict afterwards).
+    ``freeze`` sets ``requires_grad = False`` on the trunk's parameters."""
+    _cnn9_trunk = False
+
+    def __init__(self, sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num, feature_type,
+                 checkpoint_path, freeze=False):
+        super().__init__(sample_rate, window_size, hop_size, mel_bins, fmin, fmax, 25, 'logmel')
+        self.checkpoint_path = checkpoint_path
+        self.freeze = freeze
+        feature_sample_rate = 1.0 / (hop_size / sample_rate)
+        self.example_window_length = int(round(0.96 * feature_sample_rate))
+        self.example_hop_length = int(round(0.96 * feature_sample_rate))
+        self.gru = nn.GRU(input_size=512, hidden_size=256, num_layers=1, bias=True,
+                          batch_first=True, bidirectional=True)
+        self.vggish = nn.Sequential(_vggish_features())   # keys vggish.0.<index>.*
+        self._build_head()
+        self.init_weights()
+
+    def init_weights(self):
+        init_bn(self.bn0)
+        if self.checkpoint_path is not None:
+            checkpoint = torch.load(self.checkpoint_path, map_location='cpu')
+            full = {'features.' + k for k in self.vggish[0].state_dict()}
+            missing = sorted(full - set(checkpoint))
+            unexpected = sorted(k for k in checkpoint if k not in full and not k.startswith('fc.'))
+            if missing or unexpected:   # VGGish().load_state_dict(checkpoint) is strict
+                raise RuntimeError('VGGish checkpoint: missing keys %s, unexpected keys %s' % (missing, unexpected))
+            self.vggish[0].load_state_dict({k[len('features.'):]: v for k, v in checkpoint.items()
+                                            if k.startswith('features.')})
+        if self.freeze:
+            for param in self.vggish.parameters():
+                param.requires_grad = False
+
+
+class VGGish_FrameAtt(_VGGishModel):
+    """pytorch/models.py:2284-2383: trunk, ``AttBlock(512, 25)``; every sequence
+    frame x12, then the last frame up to 1000; embedding = cla (batch, 25, seq).
+    16 <= T < 1344 (at most 83 sequence frames), as the reference."""
+    _model_name = 'VGGish_FrameAtt'
+    _embedding_cla = True
+
+    def _build_head(self):
+        self.att_block = AttBlock(n_in=512, n_out=25, activation='sigmoid')
+
+
+class VGGish_Gru_FrameAtt(_VGGishModel):
+    """pytorch/models.py:2386-2485: as ``VGGish_FrameAtt`` with the bi-GRU between
+    the trunk and the head."""
+    _model_name = 'VGGish_Gru_FrameAtt'
+    _embedding_cla = True
+
+    def _build_head(self):
+        self.att_block = AttBlock(n_in=512, n_out=25, activation='sigmoid')
+
+
+class VGGish_FrameAvg(_VGGishModel):
+    """pytorch/models.py:2487-2592: trunk, ``sigmoid(Linear(512, 25))``; every
+    sequence frame x(1000 // seq), then the last frame up to 1000; clipwise = the
+    mean over the 1000 padded frames; embedding = the trunk's output (batch, 512,
+    seq).  Up to 1000 sequence frames (beyond, the reference returns an empty
+    tensor and NaN; this class raises)."""
+    _model_name = 'VGGish_FrameAvg'
+
+    def _build_head(self):
+        self.fc = nn.Linear(512, 25, bias=True)

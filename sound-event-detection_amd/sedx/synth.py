@@ -87,6 +87,17 @@ DEEP14_GOLDEN_SEEDS = {
 CNN14_GOLDEN_SEEDS = {
     'Cnn14_DecisionLevelAtt': 0,
 }
+# the three VGGish models' (tests/golden/vggish_*): ``pytorch/models.py:2284-2592``.  Seeds at which the
+# reference's windowed output keeps every event-deciding value at least 1e-4 from its threshold
+# (tools/make_golden_vggish.py walks the waveform seed, asserts the margin and records it in vggish_meta.json)
+VGGISH_GOLDEN_SEEDS = {
+    'VGGish_FrameAtt': 20,
+    'VGGish_Gru_FrameAtt': 21,
+    'VGGish_FrameAvg': 22,
+}
+VGGISH_HEADS = {'VGGish_FrameAtt': 'att', 'VGGish_Gru_FrameAtt': 'att', 'VGGish_FrameAvg': 'fc'}
+# VGGish.features' convs: nn.Sequential index, (cin, cout) (models.py:2230-2250)
+VGGISH_CONVS = [(0, 1, 64), (3, 64, 128), (6, 128, 256), (8, 256, 256), (11, 256, 512), (13, 512, 512)]
 CONFORMER_DIM, CONFORMER_FF, CONFORMER_BLOCKS, CONFORMER_HEADS, CONFORMER_KERNEL = 144, 576, 3, 4, 7
 
 
@@ -140,6 +151,38 @@ def _conformer_encoder(rng):
     return sd
 
 
+def _vggish_state_dict(model_type, seed):
+    """The non-frontend tensors of a VGGish model in the reference's state_dict order: ``bn0.*`` (never
+    applied), ``gru.*`` (every class builds it, :2318; only ``VGGish_Gru_FrameAtt`` calls it),
+    ``vggish.0.*``, the 25-class head.  The trunk reads the log-mel as it is (values from about -100 dB to
+    +30 dB, no bn0), so conv1's weights are U(+-1/80): nine taps of such an input sum to O(1).  The deeper
+    convs draw U(+-sqrt(6 / fan_in)) (He uniform), which keeps the ReLU / max-pool activations at about 1.5 at
+    most from layer to layer; biases U(+-0.1)."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+    sd.update(_bn(rng, 'bn0', 64, mean_range=(-45.0, -35.0), var_range=(300.0, 500.0)))
+    for sfx in ('', '_reverse'):
+        b_ih, b_hh = np.sqrt(3.0 / 512), np.sqrt(3.0 / 256)
+        sd['gru.weight_ih_l0' + sfx] = rng.uniform(-b_ih, b_ih, (768, 512)).astype(np.float32)
+        sd['gru.weight_hh_l0' + sfx] = rng.uniform(-b_hh, b_hh, (768, 256)).astype(np.float32)
+        sd['gru.bias_ih_l0' + sfx] = rng.uniform(-0.1, 0.1, 768).astype(np.float32)
+        sd['gru.bias_hh_l0' + sfx] = rng.uniform(-0.1, 0.1, 768).astype(np.float32)
+    for idx, cin, cout in VGGISH_CONVS:
+        a = 1.0 / 80.0 if cin == 1 else np.sqrt(6.0 / (9 * cin))
+        sd['vggish.0.%d.weight' % idx] = rng.uniform(-a, a, (cout, cin, 3, 3)).astype(np.float32)
+        sd['vggish.0.%d.bias' % idx] = rng.uniform(-0.1, 0.1, cout).astype(np.float32)
+    if VGGISH_HEADS[model_type] == 'fc':
+        sd['fc.weight'] = _xavier_uniform(rng, (25, 512), 512, 25)
+        sd['fc.bias'] = rng.uniform(-0.5, 0.0, 25).astype(np.float32)
+    else:
+        sd['att_block.att.weight'] = _xavier_uniform(rng, (25, 512, 1), 512, 25)
+        sd['att_block.att.bias'] = rng.uniform(-0.1, 0.1, 25).astype(np.float32)
+        sd['att_block.cla.weight'] = _xavier_uniform(rng, (25, 512, 1), 512, 25)
+        sd['att_block.cla.bias'] = rng.uniform(-0.5, 0.0, 25).astype(np.float32)
+        sd.update(_bn(rng, 'att_block.bn_att', 25))
+    return sd
+
+
 def make_state_dict(model_type, classes_num=25, seed=0):
     """Return {key: np.ndarray} for the non-frontend parameters of one of the
     nine 9-layer models, the two 14-layer ones or ``Cnn14_DecisionLevelAtt`` (``MODEL_PARTS``).  Draw order: the trunk, the
@@ -149,7 +192,10 @@ def make_state_dict(model_type, classes_num=25, seed=0):
     has ``Cnn_9layers_Conformer_FrameAtt``'s (:1288).  The Conformer models get
     every encoder tensor drawn (LayerNorm weights and biases and the two
     relative-position biases included, which PyTorch initialises to constants),
-    then the head, then the two modules they never call."""
+    then the head, then the two modules they never call.  The three VGGish
+    models (``VGGISH_HEADS``) have their own draws (``_vggish_state_dict``)."""
+    if model_type in VGGISH_HEADS:   # their own draws (25 classes whatever classes_num is): none above moves
+        return _vggish_state_dict(model_type, seed)
     if model_type not in MODEL_PARTS:
         raise ValueError('unknown model_type %r' % model_type)
     seq, head = MODEL_PARTS[model_type]
