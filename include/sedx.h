@@ -301,6 +301,23 @@ sedx_status sedx_gamma_features(sedx_handle* h, const float* d_audio, int64_t B,
                                 float* d_feat, int64_t* T_out, void* d_workspace,
                                 size_t workspace_bytes, void* stream);
 sedx_status sedx_gamma_workspace_size(const sedx_handle* h, int64_t B, int64_t L, size_t* bytes);
+/* Where sedx_gamma_features keeps its stages in the workspace (byte offsets
+ * from its base; a debugging and test aid, the contents are only defined
+ * after a call on that workspace has completed):
+ *   mag [B][T][kp] float64   |FFT| of the windowed frames; bins nfft/2+1 .. kp-1
+ *                            and the rows T_fill .. T-1 of every clip are 0
+ *   db  [B][64][T] float64   10 log10(max(1e-10, W . mag / nfft))
+ *   mm  [B][2]     uint64    per-clip max / min of db as order-preserving keys
+ * T = 1 + floor((L - nfft) / hop) columns, of which the reference's specgram
+ * loop range(0, L - nfft, hop) fills the first T_fill (T - 1 when hop divides
+ * L - nfft).  total_bytes is what sedx_gamma_workspace_size reports.  The
+ * sizes follow from the configuration alone: no weights or device needed. */
+typedef struct {
+  int64_t T, T_fill;
+  int32_t nfft, hop, kp, reserved;
+  size_t mag_offset, db_offset, mm_offset, total_bytes;
+} sedx_gamma_layout;
+sedx_status sedx_gamma_workspace_layout(const sedx_handle* h, int64_t B, int64_t L, sedx_gamma_layout* out);
 
 /* Windowed drivers: pytorch/predict.py:297-349 (`predict`) and
  * pytorch/main_strong.py:786-835 (`inference_prob_overlap`) / :1052-1100

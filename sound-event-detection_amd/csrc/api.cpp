@@ -853,17 +853,16 @@ sedx_status sedx_gamma_features(sedx_handle* h, const float* d_audio, int64_t B,
   if (h->cfg.feature_type != SEDX_FEATURE_GAMMA)
     return fail(h, SEDX_EINVAL, "handle was not created with feature_type=gamma");
   if (L < h->g_nfft) return fail(h, SEDX_EINVAL, "clip shorter than the gammatone FFT");
-  const int64_t T = 1 + (L - h->g_nfft) / h->g_hop;
+  const GammaLayout lay = gamma_layout(B > 0 ? B : 1, L, h->g_nfft, h->g_hop);
+  const int64_t T = lay.T;
   if (T_out) *T_out = T;
   if (!d_feat) return SEDX_OK;   // geometry query
   if (!d_audio || B <= 0) return fail(h, SEDX_EINVAL, "null pointer or empty batch");
   if (B > INT32_MAX / 64 || B * T > INT32_MAX / 64) return fail(h, SEDX_EINVAL, "batch too large");
-  const int64_t fill = (L - h->g_nfft + h->g_hop - 1) / h->g_hop;   // len(range(0, s-n, h))
   DeviceGuard dg(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const size_t need = gamma_workspace_bytes(B, T, h->g_nfft);
   float* ws = nullptr;
-  sedx_status st = get_ws(h, need, d_workspace, workspace_bytes, &ws);
+  sedx_status st = get_ws(h, lay.total_bytes, d_workspace, workspace_bytes, &ws);
   if (st != SEDX_OK) return st;
   char* base = reinterpret_cast<char*>(ws);
   GammaParams p{};
@@ -871,18 +870,16 @@ sedx_status sedx_gamma_features(sedx_handle* h, const float* d_audio, int64_t B,
   p.L = L;
   p.B = (int32_t)B;
   p.T = (int32_t)T;
-  p.T_fill = (int32_t)std::min<int64_t>(fill, T);
+  p.T_fill = (int32_t)lay.T_fill;
   p.hop = h->g_hop;
   p.nfft = h->g_nfft;
-  p.kp = gamma_kp(h->g_nfft);
+  p.kp = lay.kp;
   p.twiddle = reinterpret_cast<const double2*>(h->w.g_twiddle);
   p.window = h->w.g_window;
   p.weightsT = h->w.g_weightsT;
-  p.mag = reinterpret_cast<double*>(base);
-  base += align256((size_t)B * T * p.kp * sizeof(double));
-  p.db = reinterpret_cast<double*>(base);
-  base += align256((size_t)B * 64 * T * sizeof(double));
-  p.mm = reinterpret_cast<unsigned long long*>(base);
+  p.mag = reinterpret_cast<double*>(base + lay.mag_off);
+  p.db = reinterpret_cast<double*>(base + lay.db_off);
+  p.mm = reinterpret_cast<unsigned long long*>(base + lay.mm_off);
   p.out = d_feat;
   launch_gamma(p, s, h->tune.gamma_spec);
   return launch_status(h);
@@ -895,7 +892,31 @@ sedx_status sedx_gamma_workspace_size(const sedx_handle* h, int64_t B, int64_t L
     return fail(h, SEDX_EINVAL, "handle was not created with feature_type=gamma");
   if (!h->finalized) return fail(h, SEDX_ESTATE, "weights not finalised");
   if (L < h->g_nfft) return fail(h, SEDX_EINVAL, "clip shorter than the gammatone FFT");
-  *bytes = gamma_workspace_bytes(B, 1 + (L - h->g_nfft) / h->g_hop, h->g_nfft);
+  *bytes = gamma_layout(B, L, h->g_nfft, h->g_hop).total_bytes;
+  return SEDX_OK;
+}
+
+sedx_status sedx_gamma_workspace_layout(const sedx_handle* h, int64_t B, int64_t L, sedx_gamma_layout* out) {
+  if (!h) return SEDX_EINVAL;
+  if (!out || B <= 0) return fail(h, SEDX_EINVAL, "null layout pointer or empty batch");
+  if (h->cfg.feature_type != SEDX_FEATURE_GAMMA)
+    return fail(h, SEDX_EINVAL, "handle was not created with feature_type=gamma");
+  // the sizes follow from the configuration alone: no weights, no device
+  GammaGeom gg;
+  if (!gamma_geometry(h->cfg.sample_rate, h->cfg.window_size, h->cfg.hop_size, &gg))
+    return fail(h, SEDX_EINVAL, "gammatone nfft %d unsupported", gg.nfft);
+  if (L < gg.nfft) return fail(h, SEDX_EINVAL, "clip shorter than the gammatone FFT");
+  const GammaLayout lay = gamma_layout(B, L, gg.nfft, gg.hop);
+  out->T = lay.T;
+  out->T_fill = lay.T_fill;
+  out->nfft = gg.nfft;
+  out->hop = gg.hop;
+  out->kp = lay.kp;
+  out->reserved = 0;
+  out->mag_offset = lay.mag_off;
+  out->db_offset = lay.db_off;
+  out->mm_offset = lay.mm_off;
+  out->total_bytes = lay.total_bytes;
   return SEDX_OK;
 }
 

@@ -1205,14 +1205,11 @@ __global__ __launch_bounds__(256) void gamma_quant_kernel(GammaParams p) {
     const double maxabs = fmax(fabs(mx), fabs(lo));    // np.max(np.abs(x)) after the clamp
     double x = fmax(p.db[i], floor_db);
     if (maxabs > 1.0) x = x / maxabs;
-    const double q = trunc(x * 32767.0);
+    // + 0.0: astype(int16) has no negative zero, so a value in (-1, 0) comes
+    // back as +0.0 from the reference, not the -0.0 that trunc alone leaves
+    const double q = trunc(x * 32767.0) + 0.0;
     p.out[i] = (float)(q / 32767.0);
   }
-}
-
-size_t gamma_workspace_bytes(int64_t B, int64_t T, int nfft) {
-  return align256((size_t)B * T * gamma_kp(nfft) * sizeof(double)) + align256((size_t)B * 64 * T * sizeof(double)) +
-         align256((size_t)B * 2 * sizeof(unsigned long long));
 }
 
 template <int NFFT>

@@ -5,12 +5,15 @@
 //   make_erb_filters (width = 1)   utils/gammatone/filters.py:90-193
 //   fft_weights                    utils/gammatone/fftweight.py:63-123
 //   specgram_window                utils/gammatone/fftweight.py:15-30
+// and the front end's geometry and workspace layout (gamma_geometry,
+// gamma_layout), which follow from the configuration alone.
 // Complex arithmetic follows numpy's float64 complex loops: product
 // (ar br - ai bi, ar bi + ai br) with a real operand promoted to x + 0j,
 // Smith's division, integer powers by repeated squaring, abs = hypot.
 #include <cmath>
 #include <vector>
 
+#include "plan.h"
 #include "weights.h"
 
 namespace sedx {
@@ -48,8 +51,32 @@ double zabs(Z a) { return std::hypot(a.r, a.i); }
 
 }  // namespace
 
+bool gamma_geometry(int sample_rate, int window_size, int hop_size, GammaGeom* g) {
+  const double fs = sample_rate;
+  const double win_t = (double)window_size / fs, hop_t = (double)hop_size / fs;
+  const int nfft = (int)std::pow(2.0, std::ceil(std::log2(2 * win_t * fs)));
+  auto rhaz = [](double x) { return (x > 0 ? 1.0 : (x < 0 ? -1.0 : 0.0)) * std::floor(std::fabs(x) + 0.5); };
+  g->nfft = nfft;
+  g->nwin = (int)rhaz(win_t * fs);
+  g->hop = (int)rhaz(hop_t * fs);
+  return nfft == 512 || nfft == 1024 || nfft == 2048;
+}
+
+GammaLayout gamma_layout(int64_t B, int64_t L, int nfft, int hop) {
+  GammaLayout g;
+  g.T = 1 + (L - nfft) / hop;
+  const int64_t fill = (L - nfft + hop - 1) / hop;   // len(range(0, L - nfft, hop))
+  g.T_fill = fill < g.T ? fill : g.T;
+  g.kp = gamma_kp(nfft);
+  g.mag_off = 0;
+  g.db_off = g.mag_off + align256((size_t)B * g.T * g.kp * sizeof(double));
+  g.mm_off = g.db_off + align256((size_t)B * 64 * g.T * sizeof(double));
+  g.total_bytes = g.mm_off + align256((size_t)B * 2 * sizeof(unsigned long long));
+  return g;
+}
+
 void gamma_tables(double fs, int nfft, int nwin, int nfilts, double fmin, std::vector<double>& weightsT,
-                  int kp, std::vector<double>& twiddle, std::vector<double>& window) {
+                  int kp, std::vector<double>& twiddle, std::vector<double>& window, GammaTrace* trace) {
   const double ear_q = 9.26449, min_bw = 24.7;
   const double fmax = fs / 2;
   const int NB = nfft / 2 + 1;
@@ -69,6 +96,11 @@ void gamma_tables(double fs, int nfft, int nwin, int nfilts, double fmin, std::v
     ucirc[k] = zexp(div(Z{0.0, im}, zr((double)nfft)));
   }
   weightsT.assign((size_t)kp * nfilts, 0.0);
+  if (trace) {
+    *trace = GammaTrace();
+    trace->cf = cf;
+    for (const Z& u : ucirc) trace->ucirc.insert(trace->ucirc.end(), {u.r, u.i});
+  }
   const double T = 1 / fs;
   const double rt_pos = std::sqrt(3 + std::pow(2.0, 1.5)), rt_neg = std::sqrt(3 - std::pow(2.0, 1.5));
   for (int c = 0; c < nfilts; ++c) {
@@ -99,6 +131,22 @@ void gamma_tables(double fs, int nfft, int nwin, int nfilts, double fmin, std::v
     const double theta = 2 * M_PI * cf[c] / fs;
     const Z pole = mul(zr(r), zexp(mul(Z{0.0, 1.0}, zr(theta))));
     const Z pconj = Z{pole.r, -pole.i};
+    if (trace) {
+      GammaTrace& t = *trace;
+      t.erb.push_back(erb);
+      t.B.push_back(B);
+      t.arg.push_back(arg);
+      t.vec.insert(t.vec.end(), {vec.r, vec.i});
+      t.common.push_back(common);
+      t.k1.insert(t.k1.end(), {k11, k12, k13, k14});
+      t.A1.insert(t.A1.end(), {A11, A12, A13, A14});
+      t.gain_arg.insert(t.gain_arg.end(), {gain_arg.r, gain_arg.i});
+      t.gain.push_back(gain);
+      t.B2.push_back(B2);
+      t.r.push_back(r);
+      t.theta.push_back(theta);
+      t.pole.insert(t.pole.end(), {pole.r, pole.i});
+    }
     for (int k = 0; k < NB; ++k) {
       const Z u = ucirc[k];
       const double den4 = std::pow(zabs(mul(mul(zr(fs), sub(pole, u)), sub(pconj, u))), -4.0);

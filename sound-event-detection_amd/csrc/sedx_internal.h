@@ -84,7 +84,7 @@ struct GammaParams {
   unsigned long long* mm;  // [B][2] workspace: ordered max / min of db per clip
   float* out;              // [B][64][T] dequantised features
 };
-size_t gamma_workspace_bytes(int64_t B, int64_t T, int nfft);
+// (the workspace layout of mag / db / mm: gamma_layout, weights.h)
 // spec_variant (nfft 2048): 0 the workgroup Stockham spectrum, 1 one wave per frame
 void launch_gamma(const GammaParams& p, hipStream_t s, int spec_variant = 0);
 

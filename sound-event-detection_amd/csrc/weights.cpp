@@ -707,14 +707,9 @@ sedx_status prepare_weights(const Model& m, const Params& P, DevWeights* Wp, Wei
   if (m.cfg.feature_type == SEDX_FEATURE_GAMMA) {
     // fft_gtgram (fftweight.py:151-152) + gtgram_strides (gtgram.py:23-40)
     const double fs = m.cfg.sample_rate;
-    const double win_t = (double)m.cfg.window_size / fs, hop_t = (double)m.cfg.hop_size / fs;
-    const int nfft_g = (int)std::pow(2.0, std::ceil(std::log2(2 * win_t * fs)));
-    auto rhaz = [](double x) { return (x > 0 ? 1.0 : (x < 0 ? -1.0 : 0.0)) * std::floor(std::fabs(x) + 0.5); };
-    if (nfft_g != 512 && nfft_g != 1024 && nfft_g != 2048)
-      return fail(err, SEDX_EINVAL, "gammatone nfft %d unsupported", nfft_g);
-    gamma->nfft = nfft_g;
-    gamma->nwin = (int)rhaz(win_t * fs);
-    gamma->hop = (int)rhaz(hop_t * fs);
+    if (!gamma_geometry(m.cfg.sample_rate, m.cfg.window_size, m.cfg.hop_size, gamma))
+      return fail(err, SEDX_EINVAL, "gammatone nfft %d unsupported", gamma->nfft);
+    const int nfft_g = gamma->nfft;
     std::vector<double> g_tw, g_win, g_wT;
     gamma_tables(fs, nfft_g, gamma->nwin, 64, m.cfg.fmin, g_wT, gamma_kp(nfft_g), g_tw, g_win);
     blob->add(&W.g_twiddle, g_tw.data(), g_tw.size());

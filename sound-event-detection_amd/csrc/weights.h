@@ -209,11 +209,30 @@ void pack_head(const Model& m, const Params& P, std::vector<float>* wac, std::ve
 // gammatone tables (gamma_weights.cpp); gamma_kp: bins nfft / 2 + 1 padded to a multiple of 32
 inline int gamma_kp(int nfft) { return ((nfft / 2 + 1) + 31) / 32 * 32; }
 // host: ERB weights [kp][nfilts] (zero rows past nfft/2), twiddles [2 nfft], window [nfft]
+// trace (tests/native/gamma_tables_driver.cpp): the intermediates of erb_space, make_erb_filters and
+// fft_weights per channel (complex values as re, im pairs), for a step-by-step comparison with numpy
+struct GammaTrace {
+  std::vector<double> cf, ucirc, erb, B, arg, vec, common, k1, A1, gain_arg, gain, B2, r, theta, pole;
+};
 void gamma_tables(double fs, int nfft, int nwin, int nfilts, double fmin, std::vector<double>& weightsT,
-                  int kp, std::vector<double>& twiddle, std::vector<double>& window);
+                  int kp, std::vector<double>& twiddle, std::vector<double>& window, GammaTrace* trace = nullptr);
 struct GammaGeom {
   int nfft = 0, nwin = 0, hop = 0;
 };
+// fft_gtgram's sizes (fftweight.py:151-152, gtgram.py:23-40) from the
+// handle's sample_rate / window_size / hop_size; false: nfft not 512 / 1024 / 2048
+bool gamma_geometry(int sample_rate, int window_size, int hop_size, GammaGeom* g);
+// The gammatone workspace of B clips of L >= nfft samples, byte offsets from
+// its base: mag [B][T][kp] f64, db [B][64][T] f64, mm [B][2] u64 (per-clip
+// max / min keys).  The forward carves by it and the size query returns
+// total_bytes.  T = 1 + (L - nfft) / hop columns, of which specgram's loop
+// range(0, L - nfft, hop) fills the first T_fill.
+struct GammaLayout {
+  int64_t T = 0, T_fill = 0;
+  int kp = 0;
+  size_t mag_off = 0, db_off = 0, mm_off = 0, total_bytes = 0;
+};
+GammaLayout gamma_layout(int64_t B, int64_t L, int nfft, int hop);
 
 // Everything sedx_finalize_weights uploads: checks that params holds every key
 // of expected_params(m), fills the image, records where every pointer of *W

@@ -27,7 +27,7 @@ EXPORTS = ['sedx_create', 'sedx_destroy', 'sedx_last_error', 'sedx_version', 'se
            'sedx_set_tuning', 'sedx_set_capture', 'sedx_window_starts', 'sedx_merge_host', 'sedx_check_error',
            'sedx_abi_version', 'sedx_conv_launch_plan', 'sedx_gemm_launch_plan',
            'sedx_average_precision', 'sedx_average_precision_workspace_size', 'sedx_average_precision_device',
-           'sedx_rank_tile']
+           'sedx_rank_tile', 'sedx_gamma_workspace_layout']
 TUNE_GRU_KERNEL, TUNE_GRU_HANDOFF, TUNE_WINO_BLOCK1, TUNE_MEL_MFMA, TUNE_GRU_SPIN, TUNE_WINO_ORDER = 0, 1, 2, 3, 4, 5
 TUNE_GAMMA_SPEC = 6
 TUNE_WINO_F43 = 7
@@ -86,6 +86,14 @@ class SedxGemmLaunch(ctypes.Structure):
 GEMM_KERNEL = {'tiled': 0, 'one_wave': 1, 'ksplit': 2, 'x3': 3, 'conformer': 4}
 
 
+class SedxGammaLayout(ctypes.Structure):
+    """sedx_gamma_layout: where sedx_gamma_features keeps mag / db / mm in its workspace."""
+    _fields_ = [('T', ctypes.c_int64), ('T_fill', ctypes.c_int64),
+                ('nfft', ctypes.c_int32), ('hop', ctypes.c_int32), ('kp', ctypes.c_int32), ('reserved', ctypes.c_int32),
+                ('mag_offset', ctypes.c_size_t), ('db_offset', ctypes.c_size_t), ('mm_offset', ctypes.c_size_t),
+                ('total_bytes', ctypes.c_size_t)]
+
+
 class SedxConfig(ctypes.Structure):
     _fields_ = [('model_type', ctypes.c_int32), ('feature_type', ctypes.c_int32),
                 ('sample_rate', ctypes.c_int32), ('window_size', ctypes.c_int32),
@@ -133,6 +141,7 @@ def lib():
         'sedx_forward_i16': ([P, P, I64, I64, P, P, P, P, SZ, P], I32),
         'sedx_gamma_features': ([P, P, I64, I64, P, PI64, P, SZ, P], I32),
         'sedx_gamma_workspace_size': ([P, I64, I64, PSZ], I32),
+        'sedx_gamma_workspace_layout': ([P, I64, I64, ctypes.POINTER(SedxGammaLayout)], I32),
         'sedx_set_tuning': ([P, I32, I32], I32),
         'sedx_check_error': ([P], I32),
         'sedx_set_capture': ([P, I32, P, SZ], I32),
