@@ -493,7 +493,8 @@ sedx_status sedx_set_precision(sedx_handle* h, int32_t mode);
  *                         0: block 1 as the direct fused fp32 kernel.
  *                         With SEDX_TUNE_WINO_F43 2 (its default) 1 and 2
  *                         both run conv1's own launch + the F(4x4,3x3) conv2
- *                         (2: conv1 in the chunk-of-4 layout, 1: NHWC;
+ *                         (2: conv1 channel-planar — or in the chunk-of-4
+ *                         layout, SEDX_TUNE_WINO_ORDER 3 — 1: NHWC;
  *                         bit-identical).
  *  SEDX_TUNE_GRU_SPIN     bound of every GRU hand-off spin, in polls (default
  *                         2^24 = 16777216).  A spin that runs out turns that
@@ -519,7 +520,11 @@ sedx_status sedx_set_precision(sedx_handle* h, int32_t mode);
  *                         0: tile block major; 2: as 1, and block 1's F(4x4,3x3)
  *                         conv2 gives each XCD a contiguous range of tile
  *                         blocks (neighbouring items' shared halo rows read
- *                         once into that XCD's L2).  Bit-identical outputs.
+ *                         once into that XCD's L2); 3: as 1, and block 1's
+ *                         conv1 writes the chunk-of-4 layout that its
+ *                         F(4x4,3x3) conv2 then stages plane by plane (the
+ *                         default: channel-planar, staged by 16-byte LDS-DMAs;
+ *                         the A/B of the two).  Bit-identical outputs.
  *  SEDX_TUNE_WINO_F43     (winograd) 2 (default): block 1's conv2 and the
  *                         six conv layers of blocks 2-4 as fp32 Winograd
  *                         F(4x4,3x3) (36 multiplies per 4x4 tile,

@@ -283,7 +283,10 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
   // else after it (stage 1)
   auto block1_first = [&]() {
     switch (p.block1) {
-      case B1_CONV1C4_F43: launch_conv1_c4(X0, iB, (int)g.T, w.c1_w, w.c1_b, A, s); break;
+      case B1_CONV1C4_F43:
+        if (p.b1_planar) launch_conv1_planar(X0, iB, (int)g.T, w.c1_w, w.c1_b, A, s);
+        else launch_conv1_c4(X0, iB, (int)g.T, w.c1_w, w.c1_b, A, s);
+        break;
       case B1_CONV1_F23:
       case B1_CONV1_F43: launch_conv1_nhwc(X0, iB, (int)g.T, w.c1_w, w.c1_b, A, s); break;
       case B1_PAD_EXACT:
@@ -343,7 +346,7 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
       launch_conv3x3_wino(in, iB, c.T, c.F, c.cin, c.cout, w.wu[k], w.cb[k], out, c.epi, w.zero, w.trash, s, c.order);
     else if (wino)   // in block 1 on conv1's activation (B1_CONV1_F43, B1_CONV1C4_F43)
       launch_conv3x3_wino43(in, iB, c.T, c.F, c.cin, c.cout, w.wu43[k], w.cb[k], out, c.epi, w.trash, s, c.order,
-                            p.c4, 0, claim);
+                            p.c4, 0, claim, i == 0 && p.b1_planar);
     else if (i == 0 && p.block1 == B1_PAD_X3)
       launch_block1_fused_x3(nullptr, iB, c.T, in, w.c1_wt, w.c1_b, w.wx3[k], w.cb[k], out, claim, s);
     else if (i == 0)   // B1_PAD_EXACT
@@ -534,7 +537,7 @@ sedx_status sedx_set_tuning(sedx_handle* h, int32_t knob, int32_t value) {
                {SEDX_TUNE_WINO_BLOCK1, 0, 2, &Tuning::wino_block1},
                {SEDX_TUNE_MEL_MFMA, 0, 1, &Tuning::mel_mfma},
                {SEDX_TUNE_GRU_SPIN, 0, INT32_MAX, &Tuning::gru_spin},
-               {SEDX_TUNE_WINO_ORDER, 0, 2, &Tuning::wino_order},
+               {SEDX_TUNE_WINO_ORDER, 0, 3, &Tuning::wino_order},
                {SEDX_TUNE_GAMMA_SPEC, 0, 1, &Tuning::gamma_spec},
                {SEDX_TUNE_WINO_F43, 0, 2, &Tuning::wino_f43}};
   for (const auto& k : knobs) {

@@ -989,6 +989,61 @@ void launch_conv1_c4(const float* x0, int B, int T, const float* w1, const float
   hipLaunchKernelGGL(conv1_c4_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x0, T, rb, w1, b1, out);
 }
 
+// Block 1's conv1 channel-planar, [B][64][T][64] (the planar-input F(4x4,3x3)
+// block-1 conv2, conv_wino43.hip): a workgroup computes C1_ROWS t-rows of one
+// clip, a thread four consecutive bins of one row for the 16 channels of its
+// wave (lane: row lane >> 4, bins 4 (lane & 15) ..+3), so a wave's 16-byte
+// stores cover the C1_ROWS rows of a plane in one contiguous 1-KiB run — the
+// run length of conv1_c4_kernel's stores, and as many store instructions.
+// Per channel and pixel the same fma chain as conv1_nhwc_kernel: bit-identical values.
+__global__ __launch_bounds__(256) void conv1_planar_kernel(const float* __restrict__ x0, int T, int rb_per_clip,
+                                                           const float* __restrict__ w1, const float* __restrict__ b1,
+                                                           float* __restrict__ out) {
+  __shared__ float s_w[64 * 9], s_b[64];
+  __shared__ float s_x[C1_ROWS + 2][66];
+  const int b = blockIdx.x / rb_per_clip;
+  const int t0 = (blockIdx.x - b * rb_per_clip) * C1_ROWS;
+  for (int i = threadIdx.x; i < 64 * 9; i += 256) s_w[i] = w1[i];
+  if (threadIdx.x < 64) s_b[threadIdx.x] = b1[threadIdx.x];
+  const float* xb = x0 + (int64_t)b * T * 64;
+  for (int i = threadIdx.x; i < (C1_ROWS + 2) * 66; i += 256) {
+    const int r = i / 66, c = i - r * 66;
+    const int t = t0 - 1 + r, f = c - 1;
+    s_x[r][c] = (t >= 0 && t < T && f >= 0 && f < 64) ? xb[t * 64 + f] : 0.0f;
+  }
+  __syncthreads();
+  static_assert(C1_ROWS * 16 == 64, "a wave covers the rows' 4-bin groups");
+  const int lane = threadIdx.x & 63, cq = threadIdx.x >> 6;   // the wave's channels 16 cq ..+15
+  const int r = lane >> 4, f0 = 4 * (lane & 15);
+  if (t0 + r >= T) return;   // (a row past T would land in the next plane)
+  float xv[3][6];
+#pragma unroll
+  for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+    for (int dx = 0; dx < 6; ++dx) xv[dy][dx] = s_x[r + dy][f0 + dx];
+  float* ob = out + (((int64_t)b * 64 + 16 * cq) * T + t0 + r) * 64 + f0;
+  for (int c = 0; c < 16; ++c) {
+    const float* wc = s_w + (16 * cq + c) * 9;
+    const float bc = s_b[16 * cq + c];
+    float y[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      float acc = 0.0f;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) acc = fmaf(xv[k / 3][p + k % 3], wc[k], acc);
+      y[p] = fmaxf(acc + bc, 0.0f);
+    }
+    *reinterpret_cast<float4*>(ob + (int64_t)c * T * 64) = make_float4(y[0], y[1], y[2], y[3]);
+  }
+}
+
+void launch_conv1_planar(const float* x0, int B, int T, const float* w1, const float* b1, float* out, hipStream_t s) {
+  const int rb = (T + C1_ROWS - 1) / C1_ROWS;
+  const int64_t blocks = (int64_t)B * rb;
+  if (B <= 0 || T <= 0 || blocks > INT32_MAX || (int64_t)T * 64 > INT32_MAX) return note_launch_error(hipErrorInvalidValue);
+  hipLaunchKernelGGL(conv1_planar_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x0, T, rb, w1, b1, out);
+}
+
 #ifdef SEDX_WINO_STAMPS
 // diagnostic builds: the stamp sums (host side, this translation unit)
 void wino_stamps_rw(unsigned long long* h, bool reset) {

@@ -86,6 +86,11 @@ typedef float w43_f32x4 __attribute__((ext_vector_type(4)));
 #ifndef SEDX_W43_DMA_SPLIT
 #define SEDX_W43_DMA_SPLIT 5
 #endif
+// planar input (block 1): the wave's one halo piece goes where the default
+// placement puts plane 0 (after MFMA position 1) or plane 2 (after position 2)
+#ifndef SEDX_W43_PL_AT
+#define SEDX_W43_PL_AT 0
+#endif
 
 // Diagnostic builds only (SEDX_W43_STAMPS, tools/wino43_bench.cpp): per-wave
 // s_memtime intervals summed over every wave of every 16th workgroup:
@@ -171,20 +176,33 @@ __device__ __forceinline__ void w43_at(const float (&m)[6], float (&z)[4]) {
 // eight XCDs (channel tile g on XCD g mod 8, every tile block of it there):
 // at one clip the 512-channel layers have 2 tile blocks, which the tile
 // block-major decode put on two XCDs.
-template <int F, int EPI, int ROW, bool C4, int NT, int TG>
+//
+// PL (block 1 only, F = 64, C4 output): the input is channel-planar
+// [B][64][T][64] (conv1_planar_kernel, conv_wino.hip).  A halo row of a plane
+// is then 64 contiguous floats, and the halo is staged by 16-byte LDS-DMAs,
+// four pixels per lane, straight into the same [k][row][RS] plane image: one
+// 1-KiB piece per wave per step — wave w the third w % 3 of plane w / 3 —
+// instead of four 256-byte planes (12 pieces per step per workgroup, not 44).
+// The row image is [4 zero][64 pixels][4 zero], one dword into the plane so
+// that a patch starts on an even dword (W43Geom); the two zero groups, the
+// rows outside the clip and a piece's tail past row 9 are written by the
+// range check like every other halo zero.  Same patch reads, transforms
+// and MFMAs as the C4 input: bit-identical outputs.
+template <int F, int EPI, int ROW, bool C4, int NT, int TG, bool PL = false>
 __device__ __forceinline__ void w43_body(const float* __restrict__ in, int B, int T, int Cin, int Cout,
                                          const float* __restrict__ U, int u_bytes, const float* __restrict__ bias,
                                          float* __restrict__ out, float* __restrict__ trash, int tb_per_clip,
                                          int ngroups, int order2d, int* __restrict__ sched, int wv) {
-  using G = W43Geom<F, TG>;
+  using G = W43Geom<F, TG, PL>;
   constexpr int RS = G::RS, PS = G::PS;
   static_assert(TG == 2 || (NT == 1 && (F == 16 || F == 8)), "16-tile items: 16-channel, F = 16 / 8 only");
   static_assert(NT == 4 || NT == 1, "channel tiles per item");
+  static_assert(!PL || (C4 && F == 64 && TG == 2), "planar input: block 1's conv2, chunk-of-4 output");
   // a U fragment: the lane's words of its NT channel tiles
   using UF = typename std::conditional<NT == 4, w43_f32x4, float>::type;
   // DMAs per wave per step: U units + 4 halo planes (NT 1: 9 units over
-  // the waves, TG 1: two per wave)
-  constexpr int VM = NT == 4 ? G::VM : TG == 2 ? 5 : 6;
+  // the waves, TG 1: two per wave; PL: one halo piece instead of 4 planes)
+  constexpr int VM = NT == 4 ? G::VM : PL ? 2 : TG == 2 ? 5 : 6;
   extern __shared__ __attribute__((aligned(16))) float smem[];   // G::LDS_BYTES (dynamic)
 
   // the lane from mbcnt (rematerialised where needed) and the wave from one
@@ -276,6 +294,19 @@ __device__ __forceinline__ void w43_body(const float* __restrict__ in, int B, in
   const int nchunks = Cin / 4;
   // halo block wv of each plane: LDS positions q = 64 wv + lane of [row][RS]
   auto halo_off = [&](int b_, int t0_) -> uint32_t {
+    if constexpr (PL) {
+      // the lane's four pixels: group q of the plane's [row][18 groups], q =
+      // 64 (wv % 3) + lane; plane 0 of clip b_ (a plane adds T F 4 bytes: soffset)
+      // (opaque: row and group are recomputed at each item's top — hoisted out
+      // of the item loop they are two VGPRs the main loop does not have)
+      int l_ = lane;
+      asm volatile("" : "+v"(l_));
+      const int q = 64 * (wv % 3) + l_;
+      const int row = q / 18, g = q - (q / 18) * 18;
+      const int t = t0_ - 1 + row;
+      const bool ok = row < G::RT && g >= 1 && g <= 16 && t >= 0 && t < T;
+      return ok ? (uint32_t)((((b_ * Cin * T + t) * F + 4 * (g - 1)) * 4)) : 0x80000000u;
+    }
     const int q = 64 * wv + lane;
     const int row = q / RS, col = q - (q / RS) * RS;
     const int t = t0_ - 1 + row, f = col - 1;
@@ -318,6 +349,18 @@ __device__ __forceinline__ void w43_body(const float* __restrict__ in, int B, in
   auto dma_h_planes = [&](uint32_t hof, int cc, int hslot, auto p0_tag, auto p1_tag) {
     if constexpr (SEDX_W43_ABL & 1) return;
     constexpr int P0 = decltype(p0_tag)::value, P1 = decltype(p1_tag)::value;
+    if constexpr (PL) {
+      // the wave's one piece, issued with the plane range that holds plane
+      // SEDX_W43_PL_AT (the step's placements split the planes in 0-1 | 2-3)
+      if constexpr (P0 <= SEDX_W43_PL_AT && SEDX_W43_PL_AT < P1) {
+        const int k = wv / 3;   // the wave's plane of the chunk
+        const uint32_t so = __builtin_amdgcn_readfirstlane((uint32_t)((4 * cc + k) * T * F * 4));
+        const uint32_t m0 = __builtin_amdgcn_readfirstlane(
+            w43_lds_addr(smem + G::H_OFF + hslot * G::HALO + k * PS + 1 + 256 * (wv - 3 * k)));
+        w43_dma16(hof, r_in, so, m0);
+      }
+      return;
+    }
     const uint32_t so = __builtin_amdgcn_readfirstlane((uint32_t)(16 * (C4 ? cc * T * F : cc)));
     // wave 11 (no block: its lanes' offsets are all out of range, halo_off)
     // writes its four zero DMAs into the trash block — a select, not a branch
@@ -364,7 +407,8 @@ __device__ __forceinline__ void w43_body(const float* __restrict__ in, int B, in
   }
 
   // the lane's patch in a halo slot: plane kk, tile (tr, tf)
-  const int p_base = kk * PS + 4 * tr * RS + 4 * tf;
+  // (PL: column -1 of the row image is index 4)
+  const int p_base = kk * PS + 4 * tr * RS + 4 * tf + (PL ? 4 : 0);
   // e = (B^T d)_ROW as a fold over the patch rows, in the order they are
   // read: e = init(row PA[, row PB]), e = fma(CC, row PC, e), e = fma(CD, row PD, e)
   //   ROW 0: d4;      -5 d2, 4 d0      ROW 1: d3 + d4; -4 d2, -4 d1
@@ -856,7 +900,9 @@ __device__ __forceinline__ void w43_body(const float* __restrict__ in, int B, in
             float* dst;
             if constexpr (EPI == EPI_POOL2) {
               const int to = 2 * trg + (ROW >> 1), fo = 2 * tf + (ROW & 1);
-              dst = to < T / 2 ? opix(to, fo, n, T / 2, F / 2) : tr_lane;
+              // (PL: the trash address from the opaque lane, not a pointer pair live across the main loop)
+              dst = to < T / 2 ? opix(to, fo, n, T / 2, F / 2)
+                               : (PL ? trash + (blockIdx.x & 31) * 256 + 4 * le : tr_lane);
               if constexpr (SEDX_W43_ABL & 32) dst = tr_lane;   // timing: coalesced pool stores
             } else {
               const int t = 4 * trg + ROW;
@@ -888,22 +934,21 @@ __device__ __forceinline__ void w43_body(const float* __restrict__ in, int B, in
 #endif
 }
 
-#define SEDX_W43_ROWS(F_, EPI_, C4_, NT_, TG_, ...)                         \
+#define SEDX_W43_ROWS(F_, EPI_, C4_, NT_, TG_, PL_, ...)                    \
   switch (TG_ == 2 ? wv >> 1 : wv) {                                       \
-    case 0: w43_body<F_, EPI_, 0, C4_, NT_, TG_>(__VA_ARGS__); break;      \
-    case 1: w43_body<F_, EPI_, 1, C4_, NT_, TG_>(__VA_ARGS__); break;      \
-    case 2: w43_body<F_, EPI_, 2, C4_, NT_, TG_>(__VA_ARGS__); break;      \
-    case 3: w43_body<F_, EPI_, 3, C4_, NT_, TG_>(__VA_ARGS__); break;      \
-    case 4: w43_body<F_, EPI_, 4, C4_, NT_, TG_>(__VA_ARGS__); break;      \
-    default: w43_body<F_, EPI_, 5, C4_, NT_, TG_>(__VA_ARGS__); break;     \
+    case 0: w43_body<F_, EPI_, 0, C4_, NT_, TG_, PL_>(__VA_ARGS__); break; \
+    case 1: w43_body<F_, EPI_, 1, C4_, NT_, TG_, PL_>(__VA_ARGS__); break; \
+    case 2: w43_body<F_, EPI_, 2, C4_, NT_, TG_, PL_>(__VA_ARGS__); break; \
+    case 3: w43_body<F_, EPI_, 3, C4_, NT_, TG_, PL_>(__VA_ARGS__); break; \
+    case 4: w43_body<F_, EPI_, 4, C4_, NT_, TG_, PL_>(__VA_ARGS__); break; \
+    default: w43_body<F_, EPI_, 5, C4_, NT_, TG_, PL_>(__VA_ARGS__); break; \
   }
 
-template <int F, int EPI, bool C4, int NT = 4, int TG = 2>
-__global__ __launch_bounds__(384 * TG, 1) void conv3x3_wino43_kernel(const float* __restrict__ in, int B, int T, int Cin,
-                                                                int Cout, const float* __restrict__ U, int u_bytes,
-                                                                const float* __restrict__ bias, float* __restrict__ out,
-                                                                float* __restrict__ trash, int tb_per_clip,
-                                                                int ngroups, int order2d, int* __restrict__ sched) {
+template <int F, int EPI, bool C4, int NT, int TG, bool PL>
+__device__ __forceinline__ void w43_entry(const float* __restrict__ in, int B, int T, int Cin, int Cout,
+                                          const float* __restrict__ U, int u_bytes, const float* __restrict__ bias,
+                                          float* __restrict__ out, float* __restrict__ trash, int tb_per_clip,
+                                          int ngroups, int order2d, int* __restrict__ sched) {
   const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
 #if SEDX_W43_PRIO == 1
   if (wv >= 8) __builtin_amdgcn_s_setprio(1);   // the youngest wave of each SIMD
@@ -924,19 +969,58 @@ __global__ __launch_bounds__(384 * TG, 1) void conv3x3_wino43_kernel(const float
     while (__builtin_amdgcn_s_memtime() - t0_ < (unsigned long long)SEDX_W43_DELAY) __builtin_amdgcn_s_sleep(8);
   }
 #endif
-  SEDX_W43_ROWS(F, EPI, C4, NT, TG, in, B, T, Cin, Cout, U, u_bytes, bias, out, trash, tb_per_clip, ngroups, order2d,
+  SEDX_W43_ROWS(F, EPI, C4, NT, TG, PL, in, B, T, Cin, Cout, U, u_bytes, bias, out, trash, tb_per_clip, ngroups, order2d,
                 sched, wv)
 }
 #undef SEDX_W43_ROWS
+
+template <int F, int EPI, bool C4, int NT = 4, int TG = 2>
+__global__ __launch_bounds__(384 * TG, 1) void conv3x3_wino43_kernel(const float* __restrict__ in, int B, int T, int Cin,
+                                                                int Cout, const float* __restrict__ U, int u_bytes,
+                                                                const float* __restrict__ bias, float* __restrict__ out,
+                                                                float* __restrict__ trash, int tb_per_clip,
+                                                                int ngroups, int order2d, int* __restrict__ sched) {
+  w43_entry<F, EPI, C4, NT, TG, false>(in, B, T, Cin, Cout, U, u_bytes, bias, out, trash, tb_per_clip, ngroups, order2d,
+                                       sched);
+}
+
+// block 1's conv2 on the channel-planar conv1 activation (w43_body's PL): F = 64, 2 x 2 pool, chunk-of-4
+// output, 64- (NT 4) or 16-channel (NT 1) items of two tile groups
+template <int NT>
+__global__ __launch_bounds__(768, 1) void conv3x3_wino43_planar_kernel(const float* __restrict__ in, int B, int T,
+                                                                   int Cin, int Cout, const float* __restrict__ U,
+                                                                   int u_bytes, const float* __restrict__ bias,
+                                                                   float* __restrict__ out, float* __restrict__ trash,
+                                                                   int tb_per_clip, int ngroups, int order2d,
+                                                                   int* __restrict__ sched) {
+  w43_entry<64, EPI_POOL2, true, NT, 2, true>(in, B, T, Cin, Cout, U, u_bytes, bias, out, trash, tb_per_clip, ngroups,
+                                              order2d, sched);
+}
 
 // one launch of the plan's (plan.cpp, plan_conv_launch) p.clips clips with TG
 // tile groups per item and 16- (p.NT 1) or 64-channel items
 template <int F, int TG>
 static void launch_w43_g(const ConvLaunch& p, const float* in, int T, int Cin, int Cout, const float* U,
-                         const float* bias, float* out, int epi, float* trash, bool c4, int* sched, hipStream_t s) {
+                         const float* bias, float* out, int epi, float* trash, bool c4, bool planar, int* sched,
+                         hipStream_t s) {
   using G = W43Geom<F, TG>;
   const int u_bytes = 2 * Cin * Cout * 36 * 4;   // the NT 4 pack, then the NT 1 pack (< 2^31: the plan)
   int* const sched_k = p.claim ? sched : nullptr;
+  // block 1's conv2 on conv1's channel-planar activation (launch_conv1_planar): the same refusal of a
+  // build that spills as the chunk-of-4 kernels below
+  if (planar) {
+    if constexpr (F == 64 && TG == 2) {
+      using GP = W43Geom<64, 2, true>;
+      if (c4 && epi == EPI_POOL2) {
+        auto* k_ = p.NT == 1 ? conv3x3_wino43_planar_kernel<1> : conv3x3_wino43_planar_kernel<4>;
+        if (!launch_info(reinterpret_cast<const void*>(k_), GP::THREADS, GP::LDS_BYTES, true).ok) return;
+        hipLaunchKernelGGL(k_, dim3((unsigned)p.nwg), dim3(GP::THREADS), GP::LDS_BYTES, s, in, p.clips, T, Cin, Cout, U,
+                           u_bytes, bias, out, trash, p.tb_per_clip, p.ngroups, p.order2d, sched_k);
+        return;
+      }
+    }
+    return note_launch_error(hipErrorInvalidValue);   // no planar-input kernel for this layer
+  }
   // Counted vmcnt waits and spills: the chunk-of-4 builds (the product
   // path) are refused if the compiler ever makes them spill (launch_info
   // no_scratch; 0 bytes in this build, -Rpass-analysis / the ISA's
@@ -971,25 +1055,26 @@ static void launch_w43_g(const ConvLaunch& p, const float* in, int T, int Cin, i
 
 template <int F>
 static void launch_w43_f(const ConvLaunch& p, const float* in, int T, int Cin, int Cout, const float* U,
-                         const float* bias, float* out, int epi, float* trash, bool c4, int* sched, hipStream_t s) {
+                         const float* bias, float* out, int epi, float* trash, bool c4, bool planar, int* sched,
+                         hipStream_t s) {
   if constexpr (F == 16 || F == 8) {
-    if (p.TG == 1) return launch_w43_g<F, 1>(p, in, T, Cin, Cout, U, bias, out, epi, trash, c4, sched, s);
+    if (p.TG == 1) return launch_w43_g<F, 1>(p, in, T, Cin, Cout, U, bias, out, epi, trash, c4, planar, sched, s);
   }
-  launch_w43_g<F, 2>(p, in, T, Cin, Cout, U, bias, out, epi, trash, c4, sched, s);
+  launch_w43_g<F, 2>(p, in, T, Cin, Cout, U, bias, out, epi, trash, c4, planar, sched, s);
 }
 
 void launch_conv3x3_wino43(const float* in, int B, int T, int F, int Cin, int Cout, const float* U43,
                            const float* bias, float* out, int epi, float* trash, hipStream_t s, int order, bool c4,
-                           int nt_force, int* sched) {
+                           int nt_force, int* sched, bool planar_in) {
   do {   // the plan's launches over whole clips
     const ConvLaunch p = plan_conv_launch(WINO_F43, device_cus(), B, T, F, Cin, Cout, epi, order, c4, nt_force,
                                           sched != nullptr);
     if (p.reject) return note_launch_error(hipErrorInvalidValue);
     switch (F) {
-      case 64: launch_w43_f<64>(p, in, T, Cin, Cout, U43, bias, out, epi, trash, c4, sched, s); break;
-      case 32: launch_w43_f<32>(p, in, T, Cin, Cout, U43, bias, out, epi, trash, c4, sched, s); break;
-      case 16: launch_w43_f<16>(p, in, T, Cin, Cout, U43, bias, out, epi, trash, c4, sched, s); break;
-      default: launch_w43_f<8>(p, in, T, Cin, Cout, U43, bias, out, epi, trash, c4, sched, s); break;
+      case 64: launch_w43_f<64>(p, in, T, Cin, Cout, U43, bias, out, epi, trash, c4, planar_in, sched, s); break;
+      case 32: launch_w43_f<32>(p, in, T, Cin, Cout, U43, bias, out, epi, trash, c4, planar_in, sched, s); break;
+      case 16: launch_w43_f<16>(p, in, T, Cin, Cout, U43, bias, out, epi, trash, c4, planar_in, sched, s); break;
+      default: launch_w43_f<8>(p, in, T, Cin, Cout, U43, bias, out, epi, trash, c4, planar_in, sched, s); break;
     }
     in += p.clips * p.in_clip, out += p.clips * p.out_clip, B -= p.clips;
   } while (B > 0);

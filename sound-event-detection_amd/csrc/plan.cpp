@@ -82,9 +82,12 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
   else p->block1 = t.wino_block1 == 2 ? B1_F23_FUSED : B1_CONV1_F23;
   p->family = x3 ? CONV_X3 : !wino ? CONV_EXACT : t.wino_f43 ? CONV_WINO43 : CONV_WINO;
   p->c4 = wino && t.wino_f43 && t.wino_block1 == 2;
+  // block 1's chunk-of-4 pair stays reachable for A/B: SEDX_TUNE_WINO_ORDER 3 (every launch's order as 1)
+  p->b1_planar = p->block1 == B1_CONV1C4_F43 && t.wino_order != 3;
+  const int wino_order = t.wino_order == 3 ? 1 : t.wino_order;
   p->claims = x3 || (p->family == CONV_WINO43 && B >= 8);
   // the VGGish trunk: launch_vgg_conv1, then launch_conv3x3 on every layer, in every precision mode
-  if (m.vgg) p->block1 = B1_VGG, p->family = CONV_EXACT, p->c4 = false, p->claims = false;
+  if (m.vgg) p->block1 = B1_VGG, p->family = CONV_EXACT, p->c4 = false, p->b1_planar = false, p->claims = false;
   // AUTO: 16 slices (half the recurrence's serial product); on a pipelined
   // handle dealt over every XCD (spread, below): beside the next batch's conv
   // stack the shorter recurrence then costs it less than the 8-slice kernel's
@@ -133,7 +136,7 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
     p->layers[i] = ConvLayer{Tl, F, i == 0 ? 64 : i % 2 ? cout / 2 : cout, cout,
                              i == 6 ? EPI_FMEAN : pool ? EPI_POOL2 : EPI_STORE,
                              pool ? Tl / 2 : Tl, i == 6 ? 1 : pool ? F / 2 : F, 0, 0,
-                             i == 0 && p->block1 == B1_CONV1_F23 ? 0 : t.wino_order};
+                             i == 0 && p->block1 == B1_CONV1_F23 ? 0 : wino_order};
     size_t& ext = i % 2 ? a_conv : p_conv;
     ext = std::max(ext, (size_t)B * p->layers[i].To * p->layers[i].Fo * cout);
   }

@@ -69,7 +69,8 @@ struct Tuning {
   int gru_handoff = SEDX_GRU_HANDOFF_AUTO;
   int wino_block1 = 2;                       // SEDX_TUNE_WINO_BLOCK1 (2: conv1 inside the Winograd launch)
   int wino_f43 = 2;                          // SEDX_TUNE_WINO_F43 (2: blocks 1-4 as F(4x4,3x3), 1: blocks 2-4)
-  int wino_order = 1;                        // SEDX_TUNE_WINO_ORDER (4 x 8 rounds on the 512-channel layers)
+  int wino_order = 1;                        // SEDX_TUNE_WINO_ORDER (4 x 8 rounds on the 512-channel layers;
+                                             // 3: as 1 with block 1's chunk-of-4 conv1 + conv2 pair)
   int mel_mfma = 0;                          // SEDX_TUNE_MEL_MFMA (measured slower: opt-in)
   int gamma_spec = 0;                        // SEDX_TUNE_GAMMA_SPEC
   int gru_spin = 1 << 24;                    // SEDX_TUNE_GRU_SPIN: bound of every GRU hand-off spin (polls)
@@ -92,7 +93,9 @@ enum Block1Form {
   B1_F23_FUSED,     // launch_block1_wino: conv1 inside the F(2x2,3x3) launch
   B1_CONV1_F23,     // launch_conv1_nhwc + launch_conv3x3_wino
   B1_CONV1_F43,     // launch_conv1_nhwc + launch_conv3x3_wino43
-  B1_CONV1C4_F43,   // launch_conv1_c4 + launch_conv3x3_wino43 in the chunk-of-4 layout
+  // launch_conv1_planar + launch_conv3x3_wino43 with planar_in (ForwardPlan::b1_planar, the default), or
+  // launch_conv1_c4 + launch_conv3x3_wino43 in the chunk-of-4 layout (SEDX_TUNE_WINO_ORDER 3)
+  B1_CONV1C4_F43,
   B1_VGG,           // launch_vgg_conv1 (conv 1 -> 64 + bias + ReLU + 2x2 max pool), then launch_conv3x3 on conv2
 };
 enum ConvFamily { CONV_EXACT, CONV_X3, CONV_WINO, CONV_WINO43 };   // layers 2-7
@@ -117,6 +120,9 @@ struct ForwardPlan {
   // winograd with F(4x4,3x3): block 1 and blocks 2-4 keep their activations
   // in the chunk-of-4 layout [B][C/4][T][F][4] (dense halo DMA)
   bool c4 = false;
+  // B1_CONV1C4_F43: conv1's activation channel-planar [B][64][T][64] in A (the same bytes as the
+  // chunk-of-4 one), staged by block 1's conv2 with one 16-byte LDS-DMA per wave per step
+  bool b1_planar = false;
   // claim counters zeroed once per forward and passed to the conv launches:
   // always in x3; F(4x4,3x3) from 8 clips (below: the static item order, same
   // outputs, and no memset: one fill launch less on the one-clip latency path)

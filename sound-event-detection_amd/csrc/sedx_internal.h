@@ -148,9 +148,12 @@ void launch_conv3x3_wino(const float* in, int B, int T, int F, int Cin, int Cout
 // clips, so B-major offsets hold in both layouts.  sched: CONV_SCHED_INTS
 // zeroed ints (item-claim counters; left zero by the launch) or nullptr =
 // the static item order — the same outputs either way.
+// planar_in (F = 64, c4, EPI_POOL2: block 1's conv2): the input is
+// channel-planar [B][Cin][T][64] (launch_conv1_planar); the output stays
+// chunk-of-4 and bit-identical to the chunk-of-4 input's.
 void launch_conv3x3_wino43(const float* in, int B, int T, int F, int Cin, int Cout, const float* U43,
                            const float* bias, float* out, int epi, float* trash, hipStream_t s, int order = 0,
-                           bool c4 = false, int nt_force = 0, int* sched = nullptr);
+                           bool c4 = false, int nt_force = 0, int* sched = nullptr, bool planar_in = false);
 // The 14-layer trunk's deep layers (conv_deep.hip): the same contract as fp32
 // direct conv, one in-order fma chain per output (order: the file's header),
 // fp32 in every precision mode.  (F, epi) in {(8, POOL2), (4, STORE), (4, POOL2),
@@ -175,6 +178,8 @@ void launch_conv1_nhwc(const float* x0, int B, int T, const float* w1, const flo
                        hipStream_t s);
 // the same conv1 into the chunk-of-4 layout [B][16][T][64][4] (conv_wino.hip)
 void launch_conv1_c4(const float* x0, int B, int T, const float* w1, const float* b1, float* out, hipStream_t s);
+// the same conv1 channel-planar, [B][64][T][64] (conv_wino.hip): the planar_in input of launch_conv3x3_wino43
+void launch_conv1_planar(const float* x0, int B, int T, const float* w1, const float* b1, float* out, hipStream_t s);
 
 // Same contract on bf16 MFMA with a 3-term hi/lo split (fp32-class accuracy).
 // wp = pack_x3's split weights (weights.cpp) [Cout/BN][Cin/16][9][BN][4 x 16 B]

@@ -85,7 +85,12 @@ struct WinoGeom {
 // TG: tile groups per item — 2 (32 tiles, 12 waves; every full-size launch)
 // or 1 (16 tiles, 6 waves: the one-clip grids of the 16-channel items at
 // F = 16 / 8, twice the items of 2 for the same work)
-template <int F, int TG = 2>
+// PL (block 1's conv2, F = 64 only): the input is channel-planar
+// [B][64][T][64] (conv1_planar_kernel), so a halo row of a plane is 64
+// contiguous floats and the halo is staged by 16-byte LDS-DMAs, four pixels
+// per lane: one 1-KiB piece per wave per step (wave w: third w % 3 of plane
+// w / 3) instead of four 256-byte planes.  The output layout is unchanged.
+template <int F, int TG = 2, bool PL = false>
 struct W43Geom {
   static constexpr int WAVES = 6 * TG, THREADS = 64 * WAVES;
   static constexpr int NT = 4, NCH = 64;             // channel tiles / output channels per item
@@ -100,13 +105,21 @@ struct W43Geom {
   // take the 16 even values mod 32 (b64 bank pairs): 2 RS = 8 (mod 32) for
   // 4 x 4 groups, 2 RS = 20 (mod 32) for 8 x 2
   // (F = 64, block 1: one tile row of 16 per group, 2 tf = 0, 2, .., 30 for any even RS)
-  static constexpr int RS = F == 64 ? 66 : F == 32 ? 36 : F == 16 ? 20 : 10;
+  // PL: a row image is [4 zero][64 pixels][4 zero] — 18 groups of 4 dwords,
+  // groups 0 and 17 zero-filled by the DMA's range check — written one dword
+  // into the plane (M0 + 4 bytes: measured fine for 16-byte LDS-DMAs,
+  // tools/oob_lds_probe.cpp), so column -1 is index 4 and column 64 index 69:
+  // a patch starts on an even dword.  (At index 3 the patch reads were
+  // ds_read_b64 at odd dwords — correct, and 17 times slower in that probe.)
+  static constexpr int RS = PL ? 72 : F == 64 ? 66 : F == 32 ? 36 : F == 16 ? 20 : 10;
   // a plane's halo in 64-dword DMA blocks, one per wave 0..HB-1 (RT RS <= 704
   // for every F); wave 11 issues its four halo DMAs into an LDS trash block,
   // so every wave has the same DMA count per step (TG 1: RT RS <= 384, a
   // block per wave, no trash wave)
   static constexpr int HB = TG == 2 ? 11 : 6;
-  static constexpr int PS = 64 * HB + 2;             // plane stride, = 2 mod 4 (odd bank pairs for odd k)
+  // PL: a plane is dword 0 (never read), then three 256-dword pieces (RT RS
+  // = 720 dwords of rows, the rest zero-filled)
+  static constexpr int PS = PL ? 3 * 256 + 2 : 64 * HB + 2;   // plane stride, = 2 mod 4 (odd bank pairs for odd k)
   static constexpr int HALO = 4 * PS;                // dwords per halo slot
   static constexpr int USZ1 = 36 * 4 * 16;           // NT 1: one 16-channel tile's slab ([p][k][m]), 9 KiB
   static constexpr int NB = 3;                       // ring depth (U and halo)
@@ -127,10 +140,12 @@ struct W43Geom {
   static constexpr int X2_OFF = HTRASH_OFF + 64, X2 = SEDX_W43_EPI2 && TG == 2 ? 3072 : 0;
   static constexpr int CL_OFF = X2_OFF + X2;         // item claims: the landed claim ([0]) and the first item ([1])
   static constexpr int LDS_BYTES = 4 * (CL_OFF + (SEDX_W43_CLAIM ? 4 : 0));
-  static constexpr int VM = 7;                       // DMAs per wave per step (3 U units + 4 halo planes)
+  static constexpr int VM = PL ? 4 : 7;              // DMAs per wave per step (3 U units + 4 halo planes; PL: + 1 piece)
 
   static_assert(F == 64 || F == 32 || F == 16 || F == 8, "F");
-  static_assert(RT * RS <= 64 * HB, "halo plane fits its DMA blocks");
+  static_assert(PL ? RT * RS <= 3 * 256 && 1 + 3 * 256 <= PS : RT * RS <= 64 * HB, "halo plane fits its DMA blocks");
+  static_assert(!PL || (F == 64 && TG == 2 && WAVES == 12 && RS == 4 * 18), "planar input: block 1, four planes x three pieces");
+  static_assert(PS % 4 == 2 && PS >= RT * RS, "plane stride");
   static_assert(TG == 1 || TG == 2, "TG");
   static_assert(TG == 1 ? HB == WAVES : HB == WAVES - 1, "halo blocks: one per wave (TG 2: wave 11 trash)");
   static_assert(TG == 1 || 36 % WAVES == 0, "U units per wave");

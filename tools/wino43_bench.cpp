@@ -40,7 +40,7 @@ int main(int argc, char** argv) {
                            {"e8m", 2, 67, 8, 64, 192, sedx::EPI_FMEAN, true},
                            {"e8s", 5, 3, 8, 16, 64, sedx::EPI_STORE, true},
                            {"e64p", 2, 37, 64, 64, 64, sedx::EPI_POOL2, true}};
-  float *d_in, *d_in4, *d_o1, *d_o2, *d_o3, *d_o4, *d_bias, *d_u, *d_u43, *d_zero, *d_trash;
+  float *d_in, *d_in4, *d_inp, *d_o1, *d_o2, *d_o3, *d_o4, *d_bias, *d_u, *d_u43, *d_zero, *d_trash;
   size_t max_in = 0, max_out = 0, max_w = 0;
   for (const Layer& l : LM) {
     max_in = std::max(max_in, (size_t)l.B * l.T * l.F * l.cin);
@@ -48,6 +48,7 @@ int main(int argc, char** argv) {
     max_w = std::max(max_w, (size_t)2 * l.cin * l.cout * 36);
   }
   hipMalloc(&d_in, max_in * 4); hipMalloc(&d_o1, max_out * 4); hipMalloc(&d_o2, max_out * 4);
+  hipMalloc(&d_inp, max_in * 4);
   hipMalloc(&d_in4, max_in * 4); hipMalloc(&d_o3, max_out * 4); hipMalloc(&d_o4, max_out * 4);
   hipMalloc(&d_bias, 512 * 4); hipMalloc(&d_u, max_w * 4); hipMalloc(&d_u43, max_w * 4);
   hipMalloc(&d_zero, 4096); hipMemset(d_zero, 0, 4096);
@@ -87,6 +88,17 @@ int main(int argc, char** argv) {
                   in[(((size_t)b * l.T + t) * l.F + f) * l.cin + c];
       hipMemcpy(d_in4, in4.data(), nin * 4, hipMemcpyHostToDevice);
     }
+    // block 1's shapes (F = 64, pooled): the same input channel-planar [B][C][T][F]
+    const bool planar = l.F == 64 && l.epi == sedx::EPI_POOL2;
+    if (planar) {
+      std::vector<float> inp(nin);
+      for (int b = 0; b < l.B; ++b)
+        for (int t = 0; t < l.T; ++t)
+          for (int f = 0; f < l.F; ++f)
+            for (int c = 0; c < l.cin; ++c)
+              inp[(((size_t)b * l.cin + c) * l.T + t) * l.F + f] = in[(((size_t)b * l.T + t) * l.F + f) * l.cin + c];
+      hipMemcpy(d_inp, inp.data(), nin * 4, hipMemcpyHostToDevice);
+    }
     hipMemcpy(d_bias, bias.data(), l.cout * 4, hipMemcpyHostToDevice);
     hipMemcpy(d_u, U.data(), U.size() * 4, hipMemcpyHostToDevice);
     hipMemcpy(d_u43, U43.data(), U43.size() * 4, hipMemcpyHostToDevice);
@@ -115,10 +127,25 @@ int main(int argc, char** argv) {
       sedx::launch_conv3x3_wino43(d_in4, l.B, l.T, l.F, l.cin, l.cout, d_u43, d_bias, o, l.epi, d_trash, 0, order,
                                   true, ntf, d_sched);
     };
+    // the planar-input launch (block 1): chunk-of-4 output, bit-identical to the chunk-of-4 input's
+    auto w4p = [&](int ntf, float* o) {
+      sedx::launch_conv3x3_wino43(d_inp, l.B, l.T, l.F, l.cin, l.cout, d_u43, d_bias, o, l.epi, d_trash, 0, order,
+                                  true, ntf, d_sched, true);
+    };
     if (with2) w2();
     w4();
     w4c();
-    size_t ntdiff = 0;
+    size_t ntdiff = 0, pldiff = 0;
+    for (int ntf : {0, 4, 1}) {   // planar input, each item shape, against the chunk-of-4 launch
+      if (!planar) break;
+      hipMemset(d_o4, 0xff, nout * 4);
+      w4p(ntf, d_o4);
+      hipDeviceSynchronize();
+      std::vector<float> a(nout), b(nout);
+      hipMemcpy(a.data(), d_o3, nout * 4, hipMemcpyDeviceToHost);
+      hipMemcpy(b.data(), d_o4, nout * 4, hipMemcpyDeviceToHost);
+      for (size_t i = 0; i < nout; ++i) pldiff += std::memcmp(&a[i], &b[i], 4) != 0;
+    }
     const bool tg1 = l.F == 16 || l.F == 8;
     for (int ntf : {4, 1, 2}) {   // each forced item shape against the launcher's choice
       if (ntf == 2 && !tg1) continue;
@@ -199,9 +226,9 @@ int main(int argc, char** argv) {
       ++nchk;
     }
     const double tol = 2e-4 * std::max(1.0, omax);
-    const bool lok = ke == hipSuccess && nan == 0 && e4max < tol && c4diff == 0 && ntdiff == 0;
+    const bool lok = ke == hipSuccess && nan == 0 && e4max < tol && c4diff == 0 && ntdiff == 0 && pldiff == 0;
     ok = ok && lok;
-    float m2 = 0, m4 = 0, m4c = 0, mn1 = 0, mn4 = 0, mt1 = 0;
+    float m2 = 0, m4 = 0, m4c = 0, mn1 = 0, mn4 = 0, mt1 = 0, m4p = 0;
     if (!l.full) {
       auto timeit = [&](auto fn) {
         fn();
@@ -226,8 +253,24 @@ int main(int argc, char** argv) {
              "per item: top %.0f steps %.0f epilogue %.0f\n",
              l.name, st[0] / waves, st[1] / waves, st[2] / waves, st[3] / waves, items / waves, st[0] / items,
              st[1] / items, st[2] / items);
+      if (planar) {
+        sedx::w43_stamps_rw(nullptr, true);
+        w4p(0, d_o4);
+        hipDeviceSynchronize();
+        sedx::w43_stamps_rw(st, false);
+        const double wp = (double)st[5], ip = (double)st[4];
+        printf("  stamps %s planar: per wave: item top %.0f, steps %.0f, epilogue %.0f, whole %.0f cycles; "
+               "items/wave %.2f; per item: top %.0f steps %.0f epilogue %.0f\n",
+               l.name, st[0] / wp, st[1] / wp, st[2] / wp, st[3] / wp, ip / wp, st[0] / ip, st[1] / ip, st[2] / ip);
+      }
 #endif
       m4c = timeit(w4c);
+      if (planar) {
+        m4p = timeit([&]() { w4p(0, d_o4); });
+        const float again_c = timeit(w4c), again_p = timeit([&]() { w4p(0, d_o4); });
+        printf("  %s planar input %.4f ms (chunk-of-4 input %.4f); again: planar %.4f, chunk-of-4 %.4f; "
+               "planar != chunk-of-4 outputs %zu\n", l.name, m4p, m4c, again_p, again_c, pldiff);
+      }
       mn4 = timeit([&]() { w4f(4, d_o4); });
       mn1 = timeit([&]() { w4f(1, d_o4); });
       if (tg1) mt1 = timeit([&]() { w4f(2, d_o4); });
@@ -285,6 +328,24 @@ int main(int argc, char** argv) {
             ndiff += std::memcmp(&a[(((size_t)b * T + t) * 64 + f) * 64 + c],
                                  &a4[((((size_t)b * 16 + c / 4) * T + t) * 64 + f) * 4 + c % 4], 4) != 0;
     ok = ok && ndiff == 0;
+    // conv1's planar layout against the NHWC one, and the planar pair's pooled output against the C4 pair's
+    float* d_ap;
+    hipMalloc(&d_ap, na * 4);
+    hipMemset(d_ap, 0xff, na * 4);
+    sedx::launch_conv1_planar(d_x0, B, T, d_w1, d_b1, d_ap, 0);
+    hipDeviceSynchronize();
+    size_t npdiff = 0;
+    {
+      std::vector<float> ap(na);
+      hipMemcpy(ap.data(), d_ap, na * 4, hipMemcpyDeviceToHost);
+      for (int b = 0; b < B; ++b)
+        for (int t = 0; t < T; ++t)
+          for (int f = 0; f < 64; ++f)
+            for (int c = 0; c < 64; ++c)
+              npdiff += std::memcmp(&a[(((size_t)b * T + t) * 64 + f) * 64 + c],
+                                    &ap[(((size_t)b * 64 + c) * T + t) * 64 + f], 4) != 0;
+    }
+    ok = ok && npdiff == 0;
     auto timeit = [&](auto fn) {
       fn();
       hipEventRecord(e0, 0);
@@ -303,9 +364,17 @@ int main(int argc, char** argv) {
       sedx::launch_conv3x3_wino43(d_a4, B, T, 64, 64, 64, d_u43, d_bias, d_ob, sedx::EPI_POOL2, d_trash, 0, order, true,
                                   0, d_sched);
     });
+    const float m_p1 = timeit([&]() { sedx::launch_conv1_planar(d_x0, B, T, d_w1, d_b1, d_ap, 0); });
+    const float m_p2 = timeit([&]() {
+      sedx::launch_conv3x3_wino43(d_ap, B, T, 64, 64, 64, d_u43, d_bias, d_ob, sedx::EPI_POOL2, d_trash, 0, order, true,
+                                  0, d_sched, true);
+    });
     printf("block1 B=%d T=%d  fused F(2,3) %.4f ms  conv1_c4 %.4f + F(4,3) conv2 %.4f = %.4f ms  (x%.2f)  "
            "conv1 c4 vs nhwc differing %zu\n",
            B, T, m_f23, m_c1, m_c2, m_c1 + m_c2, m_f23 / (m_c1 + m_c2), ndiff);
+    printf("block1 planar  conv1_planar %.4f + planar-input conv2 %.4f = %.4f ms  conv1 planar vs nhwc differing %zu\n",
+           m_p1, m_p2, m_p1 + m_p2, npdiff);
+    hipFree(d_ap);
     hipFree(d_x0); hipFree(d_w1); hipFree(d_b1); hipFree(d_a); hipFree(d_a4); hipFree(d_ob);
   }
   printf("total F(2,3) %.4f ms  F(4,3) nhwc %.4f ms  c4 %.4f ms  (x%.2f)  [c4 forced nt4 %.4f nt1 %.4f]  %s  "
