@@ -130,7 +130,43 @@ typedef enum {
    * (7 and 8 are empty), 9 the GRU, 10 the head. */
   SEDX_MODEL_VGGISH_FRAMEATT = 15,        /* VGGish_FrameAtt  :2284-2383: AttBlock(512, 25) */
   SEDX_MODEL_VGGISH_GRU_FRAMEATT = 16,    /* VGGish_Gru_FrameAtt  :2386-2485: nn.GRU(512, 256, bidirectional), AttBlock(512, 25) */
-  SEDX_MODEL_VGGISH_FRAMEAVG = 17         /* VGGish_FrameAvg  :2487-2592: Linear(512, 25), sigmoid */
+  SEDX_MODEL_VGGISH_FRAMEAVG = 17,        /* VGGish_FrameAvg  :2487-2592: Linear(512, 25), sigmoid */
+  /* 18 is not assigned (probed as the first unknown id after the VGGish models) */
+  /* Cnn_14layers_Conformer_FrameAtt  :1627-1801: the 14-layer trunk, then the
+   * Conformer encoder of ids 7 and 8 on its T/32 sequence frames of 2048
+   * channels -- ConformerEncoder(2048, adim 144, aheads 4, elayers 3, eunits
+   * 576, kernel 7): only encoder.input_layer.0.weight differs, (144, 2048) --
+   * and AttBlock(144, 25).  feature_type must be LOGMEL; classes_num is the
+   * head's width (25 in the reference whatever its constructor is given).
+   * The encoder and the head are fp32 in every precision mode.
+   *   geometry   T = L / hop + 1 frames; seq_len = T / 32; every sequence
+   *              frame is repeated 1000 / seq_len times (:1791-1792); unless
+   *              that gives 1000 frames, the last one is repeated up to the
+   *              next multiple of 100 (:1793-1794): seq_len 31 -> x32, 992 ->
+   *              1000; 15 -> x66, 990 -> 1000; 128 -> x7, 896 -> 900; 129 ->
+   *              x7, 903 -> 1000; 501 -> x1, 501 -> 600.  clipwise sums over
+   *              the seq_len sequence frames, not the padded ones.
+   *   refusals   T < 32 (the fifth pool has no output) and seq_len > 1000 (a
+   *              deviation: the ratio is 0 and the reference returns an empty
+   *              framewise tensor): SEDX_EINVAL from the forwards,
+   *              sedx_output_geometry, sedx_workspace_size, the launch plans
+   *              and the windowed drivers, before any launch
+   *   keys       the 14-layer trunk's, encoder.* as ids 7 and 8 with the
+   *              (144, 2048) input weight, att_block.{att,cla}.{weight
+   *              [C][144][1], bias}; att_block.bn_att.*, classifier.{weight
+   *              [n][144], bias [n]} and linear_emb.{weight [2048][1], bias
+   *              [2048]} are shape-checked and dropped.  n is the reference
+   *              constructor's classes_num, which this config does not carry
+   *              (classes_num here is the head's 25): any n >= 1 is taken,
+   *              and sedx.models checks n in its load_state_dict
+   *   outputs    d_embedding: the encoder output [B, 144, seq_len]
+   * Captures (sedx_set_capture): 0, 2..8 and 40..43 as the 14-layer models; 43
+   * [items][T/32][2048] is the encoder's input; 20 and 21 + 4b + j as ids 7 and
+   * 8, here [items][T/32][144]; 9 is the encoder's output [M][144], M = items x
+   * T/32 (the same tensor as 32); 44 is the head's logits [M][64]: columns
+   * 0..C-1 att, C..2C-1 cla, zeros beyond.  Timed stage 8 as the 14-layer
+   * models, 9 the encoder, 10 the head. */
+  SEDX_MODEL_CONFORMER14_FRAMEATT = 19
 } sedx_model;
 
 typedef enum { SEDX_FEATURE_LOGMEL = 0, SEDX_FEATURE_GAMMA = 1 } sedx_feature;
@@ -156,7 +192,7 @@ typedef struct sedx_handle sedx_handle;
  * and the constructors of the other sedx_model values).  feature_type GAMMA is
  * Cnn_9layers_Gru_FrameAtt's alone (Cnn_9layers_Gru_FrameAvg takes the argument
  * and ignores it, :512-518); any other model_type with it is SEDX_EINVAL
- * (the 14-layer and the VGGish models included).  classes_num: 1..256, and up to 527 for
+ * (the 14-layer and the VGGish models included, SEDX_MODEL_CONFORMER14_FRAMEATT too).  classes_num: 1..256, and up to 527 for
  * SEDX_MODEL_CNN14_DECISIONLEVELATT. */
 sedx_status sedx_create(const sedx_config* cfg, int device, sedx_handle** out);
 void sedx_destroy(sedx_handle* h);

@@ -183,8 +183,9 @@ sedx_status preflight(sedx_handle* h) {
 // the geometry the size queries answer for: L_or_T = samples (logmel) or frames (gamma)
 sedx_status query_geometry(const sedx_handle* h, int64_t L_or_T, Geometry* g) {
   *g = geometry_from_T(*h, h->cfg.feature_type == SEDX_FEATURE_GAMMA ? L_or_T : conv_T(*h, L_or_T));
-  if (seq_too_long(*h, g->T3))
-    return fail(h, SEDX_EINVAL, "%lld sequence frames: the Conformer encoder holds %d", (long long)g->T3, CF_MAX_T);
+  if (conformer14_too_long(*h, g->Ts)) return fail(h, SEDX_EINVAL, CF14_REFUSAL, (long long)g->Ts);
+  if (seq_too_long(*h, g->Ts))
+    return fail(h, SEDX_EINVAL, "%lld sequence frames: the Conformer encoder holds %d", (long long)g->Ts, CF_MAX_T);
   // the 14-layer models have no output below 32 frames (the reference's fifth
   // avg_pool2d raises): the queries reject what the forward rejects
   if (h->depth == 14 && g->Ts < 1) return fail(h, SEDX_EINVAL, "input too short for the 5 pooling stages");
@@ -387,18 +388,8 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
   if (h->decision) {
     // Cnn14_DecisionLevelAtt: max + avg pooling over 3 sequence frames inside fc1's A staging, + ReLU: one launch
     launch_decision(S, iB, T3, w.wfc, w.bfc, Hs, s);   // fc1 in the MultiHead fc's slots (weights.h)
-  } else if (h->depth == 14) {
-    // fp32 in every precision mode: the generic fp32 GEMM at the new widths
-    if (h->seq == SEQ_GRU) {
-      launch_linear(S, M, 2048, w.w_ih, 6144, w.b_ih, G, 0, s);
-      launch_gru1024(G, iB, T3, w.whh, w.bhh, Hs, s);
-    } else {
-      launch_linear(S, M, 2048, w.wqkv, 1536, w.bqkv, G, 0, s);
-      launch_mha(G, iB, T3, O, s);
-      launch_linear(O, M, 512, w.wfc, 2048, w.bfc, Hs, 1, s);
-    }
   } else if (h->seq == SEQ_CONFORMER) {
-    // fp32 in every precision mode; x is updated in place by the residual epilogues
+    // (on either trunk) fp32 in every precision mode; x is updated in place by the residual epilogues
     float* X = ws + p.X.off;
     float* Xn = ws + p.Xn.off;
     float* Hb = ws + p.Hb.off;
@@ -411,8 +402,8 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
     for (int b = 0; b < CF_BLOCKS; ++b)
       launch_cf_gemm(Rr + (size_t)b * T3 * CF_D, T3, CF_D, w.cf[b].rnet, CF_D, nullptr, nullptr,
                      RK + (size_t)b * T3 * CF_D, CF_EPI_NONE, s);
-    // input layer (conformer_encoder.py:22-28)
-    launch_cf_gemm(S, M, 512, w.cf_in_w, CF_D, w.cf_in_b, nullptr, Xn, CF_EPI_NONE, s);
+    // input layer (conformer_encoder.py:22-28): K = the trunk's width, 512 or (14-layer) 2048
+    launch_cf_gemm(S, M, h->sw, w.cf_in_w, CF_D, w.cf_in_b, nullptr, Xn, CF_EPI_NONE, s);
     launch_cf_input_norm(Xn, iB, T3, w.cf_in_g, w.cf_in_be, w.cf_pe, X, s);
     capture(h, 20, X, nx, s);
     for (int b = 0; b < CF_BLOCKS; ++b) {
@@ -441,6 +432,16 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
       capture(h, 24 + 4 * b, X, nx, s);
     }
     HI = X;
+  } else if (h->depth == 14) {
+    // fp32 in every precision mode: the generic fp32 GEMM at the new widths
+    if (h->seq == SEQ_GRU) {
+      launch_linear(S, M, 2048, w.w_ih, 6144, w.b_ih, G, 0, s);
+      launch_gru1024(G, iB, T3, w.whh, w.bhh, Hs, s);
+    } else {
+      launch_linear(S, M, 2048, w.wqkv, 1536, w.bqkv, G, 0, s);
+      launch_mha(G, iB, T3, O, s);
+      launch_linear(O, M, 512, w.wfc, 2048, w.bfc, Hs, 1, s);
+    }
   } else if (h->seq == SEQ_GRU) {
     linear(S, w.w_ih, w.w_ih_x3, 1536, 128, w.b_ih, G, 0);
     if (p.gru_variant < 0)
@@ -462,10 +463,13 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
     launch_linear(HI, M, 2048, w.wac, h->nac, w.bac, LG, 0, s);
   else
     linear(HI, w.wac, w.wac_x3, h->nac, 64, w.bac, LG, 0);
+  if (conformer14(*h)) capture(h, 44, LG, (size_t)M * h->nac, s);
   if (h->vgg && h->head == HEAD_ATT)   // x12, padded to 1000 frames
     launch_vgg_att_head(LG, iB, T3, h->cfg.classes_num, h->nac, (int)g.out_frames, g.rep, d_fw, d_clip, d_emb, s);
   else if (h->vgg)                     // x(1000 // seq_len), padded to 1000 frames, the mean over all of them
     launch_vgg_fc_head(LG, iB, T3, h->cfg.classes_num, h->nac, (int)g.out_frames, g.rep, d_fw, d_clip, s);
+  else if (conformer14(*h))            // x(1000 // seq_len), padded to 1000 or the next multiple of 100
+    launch_att_head_rep(LG, iB, T3, h->cfg.classes_num, h->nac, (int)g.out_frames, g.rep, d_fw, d_clip, s);
   else if (h->head == HEAD_ATT)
     launch_att_head(LG, iB, T3, h->cfg.classes_num, h->nac, (int)g.out_frames, d_fw, d_clip,
                     h->emb_cla && !h->decision ? d_emb : nullptr, s, g.rep);
@@ -519,8 +523,9 @@ sedx_status sedx_set_capture(sedx_handle* h, int32_t stage, float* d_buf, size_t
   const bool cf_stage = h->seq == SEQ_CONFORMER && stage >= 20 && stage <= 20 + 4 * CF_BLOCKS;
   const bool deep_stage = h->depth == 14 && stage >= 40 && stage <= 43;   // blocks 5-6 of the 14-layer trunk
   const bool vgg_stage = h->vgg && stage >= 50 && stage <= 55;            // the VGGish trunk's launches
+  const bool lg_stage = conformer14(*h) && stage == 44;                   // Cnn_14layers_Conformer_FrameAtt's logits
   if (h->vgg && stage >= 1 && stage <= 7) return fail(h, SEDX_EINVAL, "stage %d cannot be captured", (int)stage);
-  if (stage == 1 || (stage > 9 && !cf_stage && !deep_stage && !vgg_stage)) return fail(h, SEDX_EINVAL, "stage %d cannot be captured", (int)stage);
+  if (stage == 1 || (stage > 9 && !cf_stage && !deep_stage && !vgg_stage && !lg_stage)) return fail(h, SEDX_EINVAL, "stage %d cannot be captured", (int)stage);
   h->cap_stage = stage;
   h->cap_buf = d_buf;
   h->cap_bytes = bytes;
@@ -597,7 +602,11 @@ sedx_status sedx_load_param(sedx_handle* h, const char* key, const float* h_data
                             const int64_t* shape, int32_t ndim) {
   if (!h || !key || !h_data || (ndim > 0 && !shape) || ndim < 0 || ndim > 8) return SEDX_EINVAL;
   auto it = h->expected.find(key);
-  if (it == h->expected.end() && ignored_key(*h, key)) return SEDX_OK;
+  if (it == h->expected.end() && ignored_key(*h, key)) {
+    if (!ignored_key_shape_ok(*h, key, std::vector<int64_t>(shape, shape + ndim)))
+      return fail(h, SEDX_EKEY, "size mismatch for %s", key);
+    return SEDX_OK;
+  }
   if (it == h->expected.end()) return fail(h, SEDX_EKEY, "unexpected key in state_dict: %s", key);
   std::vector<int64_t> sh(shape, shape + ndim);
   if (sh != it->second) return fail(h, SEDX_EKEY, "size mismatch for %s", key);

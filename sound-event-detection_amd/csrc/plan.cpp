@@ -29,12 +29,14 @@ Geometry geometry_from_T(const Model& m, int64_t T) {
   const bool deep = m.depth == 14;
   g.Ts = deep ? g.T5 : g.T3;
   g.rep = deep ? 32 : 8;   // interpolate_ratio (models.py:741, :1133)
+  // Cnn_14layers_Conformer_FrameAtt: 1000 // seq_len (models.py:1791).  Shapes no forward runs keep 32.
+  if (conformer14(m) && g.Ts >= 1 && g.Ts <= CF14_FRAMES) g.rep = (int)(CF14_FRAMES / g.Ts);
   g.fw_len = g.rep * g.Ts;
   g.out_frames = g.fw_len;
   // pad_framewise_output(roundup) models.py:678-681: Cnn_9layers_Gru_FrameAtt
   // (Cnn_9layers_Gru_FrameAvg returns the 8 T3 frames, :551) and the two
   // Conformer models (:1359-1360, :1571-1572)
-  // and both 14-layer models (:783-784, :1176-1177)
+  // and the 14-layer models (:783-784, :1176-1177, :1793-1794)
   const bool pad100 = m.cfg.model_type == SEDX_MODEL_GRU_FRAMEATT || m.seq == SEQ_CONFORMER || deep;
   if (m.decision) {
     // Cnn14_DecisionLevelAtt: frames_num = T - 1 (models.py:2738, :2778), not a multiple of 100; where the
@@ -143,20 +145,25 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
   const size_t M = (size_t)p->M;
   size_t e_head = a0;
   // (Cnn14_DecisionLevelAtt: H [M][2048] and the logits only)
-  p->G = take(e_head, m.decision ? 0 : M * (deep && m.seq == SEQ_GRU ? 6144 : 1536));
-  p->Hs = take(e_head, M * (deep ? 2048 : 512));
-  p->O = take(e_head, m.decision ? 0 : M * 512);
+  // (Cnn_14layers_Conformer_FrameAtt: none of G / H / O; the encoder's regions below)
+  const bool cf14 = conformer14(m);
+  p->G = take(e_head, m.decision || cf14 ? 0 : M * (deep && m.seq == SEQ_GRU ? 6144 : 1536));
+  p->Hs = take(e_head, cf14 ? 0 : M * (deep ? 2048 : 512));
+  p->O = take(e_head, m.decision || cf14 ? 0 : M * 512);
   p->LG = take(e_head, M * m.nac);
   p->gru = take(e_head, deep ? 0 : gru_coop_workspace_bytes((int)B) / 4);   // gru1024.hip: no scratch
   size_t e_a = std::max(a0 + align256(a_conv * 4), e_head);
   if (m.seq == SEQ_CONFORMER) {
+    // from A's start: the conv stack is done and its last layer (the 9-layer trunk's block 4, the deep stack's
+    // block 6) wrote the sequence input into P, so on the 14-layer trunk these follow the deep stack's regions
+    // in time and share none of P
     size_t e_cf = a0;
     p->X = take(e_cf, M * CF_D);
     p->Xn = take(e_cf, M * CF_D);
     p->Hb = take(e_cf, M * CF_FF);
     p->AV = take(e_cf, M * CF_D);
-    p->Rr = take(e_cf, (size_t)CF_BLOCKS * g.T3 * CF_D);
-    p->RK = take(e_cf, (size_t)CF_BLOCKS * g.T3 * CF_D);
+    p->Rr = take(e_cf, (size_t)CF_BLOCKS * g.Ts * CF_D);
+    p->RK = take(e_cf, (size_t)CF_BLOCKS * g.Ts * CF_D);
     p->LG = take(e_cf, M * m.nac);
     e_a = std::max(e_a, e_cf);
   }
@@ -176,8 +183,9 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
   } else if (g.T3 < 1) snprintf(p->reject, sizeof(p->reject), "input too short for the 3 pooling stages");
   else if (g.Ts < 1) snprintf(p->reject, sizeof(p->reject), "input too short for the 5 pooling stages");
   else if (decision_pad_negative(m, T)) snprintf(p->reject, sizeof(p->reject), DECISION_PAD_REFUSAL, (long long)T);
-  else if (seq_too_long(m, g.T3))
-    snprintf(p->reject, sizeof(p->reject), "%lld sequence frames: the Conformer encoder holds %d", (long long)g.T3,
+  else if (conformer14_too_long(m, g.Ts)) snprintf(p->reject, sizeof(p->reject), CF14_REFUSAL, (long long)g.Ts);
+  else if (seq_too_long(m, g.Ts))
+    snprintf(p->reject, sizeof(p->reject), "%lld sequence frames: the Conformer encoder holds %d", (long long)g.Ts,
              CF_MAX_T);
   else if (B * g.T > INT32_MAX / 64) snprintf(p->reject, sizeof(p->reject), "batch too large");   // 32-bit launch sizes
   return p->reject[0] ? p->reject : nullptr;
@@ -388,18 +396,18 @@ std::vector<GemmRow> plan_gemm_launches(const Model& m, const Tuning& t, const F
   };
   if (m.decision) {
     // launch_decision pools inside its own fc1 staging: not a GEMM launcher's launch
-  } else if (deep) {
-    if (m.seq == SEQ_GRU) fp32(9, 2048, 6144, 0);
-    else fp32(9, 2048, 1536, 0), fp32(9, 512, 2048, 1);
   } else if (m.seq == SEQ_CONFORMER) {
     for (int b = 0; b < CF_BLOCKS; ++b) cf(9, T3, CF_D, CF_D);   // r_net of every block
-    cf(9, M, 512, CF_D);                                         // input layer
+    cf(9, M, m.sw, CF_D);                                        // input layer (K 512, or 2048 on the 14-layer trunk)
     for (int b = 0; b < CF_BLOCKS; ++b) {
       cf(9, M, CF_D, CF_FF), cf(9, M, CF_FF, CF_D);              // ffn1
       cf(9, M, CF_D, 3 * CF_D), cf(9, M, CF_D, CF_D);            // mhsa: qkv_net, o_net
       cf(9, M, CF_D, 2 * CF_D), cf(9, M, CF_D, CF_D);            // conv module: the two pointwise convs
       cf(9, M, CF_D, CF_FF), cf(9, M, CF_FF, CF_D);              // ffn2
     }
+  } else if (deep) {
+    if (m.seq == SEQ_GRU) fp32(9, 2048, 6144, 0);
+    else fp32(9, 2048, 1536, 0), fp32(9, 512, 2048, 1);
   } else if (m.seq == SEQ_GRU) {
     linear(9, 1536, 0);
   } else if (m.seq == SEQ_MHA) {
@@ -447,8 +455,11 @@ const char* window_geometry(const Model& m, int64_t L_clip, const sedx_window_sp
       if (decision_pad_negative(m, g.g.T))
         return refuse("window %d has %lld frames, a multiple of 32: Cnn14_DecisionLevelAtt has no output for it", w,
                       (long long)g.g.T, 0);
-      if (seq_too_long(m, g.g.T3))
-        return refuse("window %d gives %lld sequence frames: the Conformer encoder holds %d", w, (long long)g.g.T3,
+      if (conformer14_too_long(m, g.g.Ts))
+        return refuse("window %d gives %lld sequence frames: more than %d leave no framewise output", w,
+                      (long long)g.g.Ts, CF14_FRAMES);
+      if (seq_too_long(m, g.g.Ts))
+        return refuse("window %d gives %lld sequence frames: the Conformer encoder holds %d", w, (long long)g.g.Ts,
                       CF_MAX_T);
       wg->groups.push_back(g);
     }

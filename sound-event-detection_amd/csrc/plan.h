@@ -46,7 +46,17 @@ struct Geometry {
 inline int64_t conv_T(const Model& m, int64_t L) { return L / m.cfg.hop_size + 1; }
 // the Conformer encoder's positional table has CF_MAX_T rows; the reference
 // fails on a longer sequence too (embedding.py:30: the add does not broadcast)
-inline bool seq_too_long(const Model& m, int64_t T3) { return m.seq == SEQ_CONFORMER && T3 > CF_MAX_T; }
+// (Ts: the sequence's frames, Geometry::Ts)
+inline bool seq_too_long(const Model& m, int64_t Ts) { return m.seq == SEQ_CONFORMER && Ts > CF_MAX_T; }
+// Cnn_14layers_Conformer_FrameAtt (models.py:1627-1801): the Conformer encoder on the 14-layer trunk's T / 32
+// sequence frames.  Every sequence frame is repeated 1000 // seq_len times (:1791-1792); unless that gives 1000
+// frames the last one is repeated up to the next multiple of 100 (:1793-1794).  Past 1000 sequence frames the
+// ratio is 0 and the reference returns an empty framewise tensor: refused by the forwards and the size queries.
+constexpr int CF14_FRAMES = 1000;
+inline bool conformer14(const Model& m) { return m.depth == 14 && m.seq == SEQ_CONFORMER; }
+inline bool conformer14_too_long(const Model& m, int64_t Ts) { return conformer14(m) && Ts > CF14_FRAMES; }
+constexpr const char* CF14_REFUSAL =   // fits ForwardPlan::reject
+    "%lld sequence frames: more than 1000 leave no framewise output";
 Geometry geometry_from_T(const Model& m, int64_t T);
 // Cnn14_DecisionLevelAtt pads 32 (T / 32) frames to T - 1 with (T % 32) - 1 copies of
 // the last one (models.py:2738, :2778): at T % 32 == 0 that count is -1 and
@@ -137,7 +147,7 @@ struct ForwardPlan {
   // (14-layer: G [M][6144] or QKV [M][1536], H [M][2048], O [M][512], no scratch) ...
   Region G, Hs, O, LG, gru;
   // ... or the Conformer encoder's x [M][144], LayerNorm(x), the hidden [M][576],
-  // the attention / depthwise output, r and r_k [3][T3][144] (and LG)
+  // the attention / depthwise output, r and r_k [3][Ts][144] (and LG)
   Region X, Xn, Hb, AV, Rr, RK;
   size_t total_bytes = 0;
   char reject[96] = {};            // plan_forward's reason

@@ -372,6 +372,12 @@ void launch_mha(const float* QKV, int B, int T, float* O, hipStream_t s);
 // ratio: frames per sequence frame, 8 or 32 (the 14-layer trunk's interpolate_ratio)
 void launch_att_head(const float* logits, int B, int T, int C, int ldl, int out_frames,
                      float* framewise, float* clipwise, float* emb_cla, hipStream_t s, int ratio = 8);
+// AttBlock finish for any frame repeat ratio (att_head_rep.hip; Cnn_14layers_Conformer_FrameAtt): every one of
+// the T <= 1000 sequence frames `ratio` >= 1 times, then the last frame up to out_frames (ratio T <= out_frames
+// <= 1000); clipwise sums over the T sequence frames.  No embedding output.  The file's header states the order
+// of every sum.
+void launch_att_head_rep(const float* logits, int B, int T, int C, int ldl, int out_frames, int ratio,
+                         float* framewise, float* clipwise, hipStream_t s);
 // fc head finish (models.py:284-288, :369-373): sigmoid of logits [B][T][ldl]
 // (columns 0..C-1), x8 frame repeat -> framewise [B][8T][C], clipwise [B][C] =
 // the max (max_pool) or the mean over the frames

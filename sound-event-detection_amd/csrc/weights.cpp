@@ -31,6 +31,7 @@ static bool model_parts(int32_t model_type, int* seq, int* head) {
     case SEDX_MODEL_VGGISH_FRAMEATT: *seq = SEQ_NONE, *head = HEAD_ATT; return true;
     case SEDX_MODEL_VGGISH_GRU_FRAMEATT: *seq = SEQ_GRU, *head = HEAD_ATT; return true;
     case SEDX_MODEL_VGGISH_FRAMEAVG: *seq = SEQ_NONE, *head = HEAD_FC_AVG; return true;
+    case SEDX_MODEL_CONFORMER14_FRAMEATT: *seq = SEQ_CONFORMER, *head = HEAD_ATT; return true;
     default: return false;
   }
 }
@@ -40,13 +41,15 @@ bool make_model(const sedx_config& cfg, Model* m) {
   m->cfg = cfg;
   m->decision = cfg.model_type == SEDX_MODEL_CNN14_DECISIONLEVELATT;
   m->depth = cfg.model_type == SEDX_MODEL_GRU14_FRAMEATT || cfg.model_type == SEDX_MODEL_TRANSFORMER14_FRAMEATT ||
-                     m->decision
+                     cfg.model_type == SEDX_MODEL_CONFORMER14_FRAMEATT || m->decision
                  ? 14
                  : 9;
   m->vgg = cfg.model_type == SEDX_MODEL_VGGISH_FRAMEATT || cfg.model_type == SEDX_MODEL_VGGISH_GRU_FRAMEATT ||
            cfg.model_type == SEDX_MODEL_VGGISH_FRAMEAVG;
   if (m->vgg) m->depth = VGG_LAYERS;
-  m->hw = m->depth == 14 ? 2048 : m->seq == SEQ_CONFORMER ? CF_D : 512;
+  // the trunk's output feeds the sequence layer; the Conformer encoder narrows it to 144 for the head
+  m->sw = m->depth == 14 ? 2048 : 512;
+  m->hw = m->seq == SEQ_CONFORMER ? CF_D : m->sw;
   m->nac = (((m->head == HEAD_ATT ? 2 : 1) * cfg.classes_num + 63) / 64) * 64;
   return true;
 }
@@ -56,6 +59,15 @@ bool ignored_key(const Model& m, const std::string& k) {
   if (m.vgg && m.seq != SEQ_GRU) return k.compare(0, 4, "gru.") == 0;
   if (m.seq != SEQ_CONFORMER) return false;
   return k == "classifier.weight" || k == "classifier.bias" || k == "linear_emb.weight" || k == "linear_emb.bias";
+}
+
+bool ignored_key_shape_ok(const Model& m, const std::string& k, const std::vector<int64_t>& shape) {
+  if (m.depth != 14 || m.seq != SEQ_CONFORMER) return true;
+  // classifier = Linear(144, classes_num) at the constructor's classes_num, which the handle does not know (its
+  // classes_num is the head's 25): any row count; linear_emb = Linear(1, 2048) (models.py:1727, :1735)
+  if (k == "classifier.weight") return shape.size() == 2 && shape[0] >= 1 && shape[1] == CF_D;
+  if (k == "classifier.bias") return shape.size() == 1 && shape[0] >= 1;
+  return shape == (k == "linear_emb.weight" ? std::vector<int64_t>{m.sw, 1} : std::vector<int64_t>{m.sw});
 }
 
 namespace {
@@ -177,6 +189,7 @@ std::map<std::string, std::vector<int64_t>> expected_params(const Model& m) {
     e["multihead.layer_norm.bias"] = {m.hw};
   } else if (m.seq == SEQ_CONFORMER) {
     for (const auto& t : CF_TOP) e[t.key] = t.shape;
+    e[CF_TOP[0].key] = {CF_D, m.sw};   // the input Linear reads the trunk's output: (144, 2048) on the 14-layer trunk
     for (int b = 0; b < CF_BLOCKS; ++b) {
       for (int f = 0; f < 2; ++f)
         for (const auto& t : CF_FFN) e[cf_ffn_key(b, f) + t.key] = t.shape;

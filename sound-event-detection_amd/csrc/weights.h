@@ -57,6 +57,7 @@ struct Model {
   int head = HEAD_ATT; // the head that reads its output
   int depth = 9;       // conv layers of the trunk: 9, or 14 (blocks 5-6 and five pools: T/32 sequence frames)
   int hw = 512;        // width of the head's input: 512, 144 after the Conformer encoder, 2048 on the 14-layer trunk
+  int sw = 512;        // width of the sequence layer's input (the trunk's output): 512, or 2048 on the 14-layer trunk
   int nac = 64;        // rows of the head projection: att|cla (2C) or fc (C), rounded up to 64
   // Cnn14_DecisionLevelAtt: between the trunk and the head, max + avg pooling over 3 sequence frames and
   // fc1 = Linear(2048, 2048) + ReLU (decision.hip); T - 1 framewise frames, no embedding output
@@ -76,6 +77,9 @@ bool make_model(const sedx_config& cfg, Model* m);
 // keys of modules the Conformer models build and never call at inference
 // (models.py:1290-1300, :1505-1515): accepted with any shape, not stored
 bool ignored_key(const Model& m, const std::string& k);
+// whether an ignored key may have `shape`: Cnn_14layers_Conformer_FrameAtt takes its ignored keys (models.py:1727,
+// :1735) at the reference's shapes only; the 9-layer Conformer and the VGGish models take theirs at any shape
+bool ignored_key_shape_ok(const Model& m, const std::string& k, const std::vector<int64_t>& shape);
 // every state_dict key the model reads, with its shape
 std::map<std::string, std::vector<int64_t>> expected_params(const Model& m);
 
@@ -148,7 +152,7 @@ struct DevWeights {
   float* wac = nullptr;    // [nac][hw]
   float* bac = nullptr;
   // Conformer encoder (fp32 in every mode)
-  float* cf_in_w = nullptr;      // [144][512]
+  float* cf_in_w = nullptr;      // [144][512]; on the 14-layer trunk [144][2048]
   float* cf_in_b = nullptr;
   float* cf_in_g = nullptr;      // input layer's LayerNorm
   float* cf_in_be = nullptr;

@@ -4,7 +4,9 @@ Public surface (mirrors the reference's hot-path API):
   sedx.models      the seven 9-layer models: Cnn_9layers_Gru_FrameAtt,
                    Cnn_9layers_Transformer_FrameAtt, Cnn_9layers_FrameMax,
                    Cnn_9layers_FrameAvg, Cnn_9layers_FrameAtt, Cnn_9layers_Gru_FrameAvg,
-                   Cnn_9layers_Transformer_FrameAvg (+ helpers)
+                   Cnn_9layers_Transformer_FrameAvg (+ helpers), the Conformer models
+                   Cnn_9layers_Conformer_FrameAtt / _FrameAvg and Cnn_14layers_Conformer_FrameAtt,
+                   the 14-layer, Cnn14 and VGGish models
   sedx.inference   predict_windows, inference_prob, gamma_features, events_from_framewise
   sedx.calibrate   optimize_sed_thresholds, segment_counts, segment_metrics, segment_targets
   sedx.evaluate    Evaluator, average_precision, sed_average_precision, ranked_counts,

@@ -16,7 +16,9 @@ encoder_type="Conformer", pooling="token", layer_init="pytorch")`` and
 ``forward(x, mixup_lambda=None, timeshift=False, spec_augment=True,
 mask=None)``), and the two models on the 14-layer trunk
 (``Cnn_14layers_Gru_FrameAtt``, ``Cnn_14layers_Transformer_FrameAtt``: eight
-constructor arguments, 25 classes), and ``Cnn14_DecisionLevelAtt`` (the PANNs
+constructor arguments, 25 classes; ``Cnn_14layers_Conformer_FrameAtt``: the
+Conformer constructor after ``feature_type``, 25 classes, 144-wide embedding,
+every sequence frame repeated ``1000 // seq_len`` times), and ``Cnn14_DecisionLevelAtt`` (the PANNs
 architecture: seven constructor arguments, up to 527 classes,
 ``forward(input, mixup_lambda=None)`` returning the reference's two keys, no
 ``'embedding'``), and the three transfer-learning models on the VGGish trunk
@@ -49,6 +51,7 @@ from .stft import Spectrogram, LogmelFilterBank
 
 __all__ = ['Cnn_9layers_Gru_FrameAtt', 'Cnn_9layers_Transformer_FrameAtt',
            'Cnn_14layers_Gru_FrameAtt', 'Cnn_14layers_Transformer_FrameAtt', 'Cnn14_DecisionLevelAtt',
+           'Cnn_14layers_Conformer_FrameAtt',
            'VGGish', 'VGGish_FrameAtt', 'VGGish_Gru_FrameAtt', 'VGGish_FrameAvg',
            'Cnn_9layers_FrameMax', 'Cnn_9layers_FrameAvg', 'Cnn_9layers_FrameAtt',
            'Cnn_9layers_Gru_FrameAvg', 'Cnn_9layers_Transformer_FrameAvg',
@@ -63,7 +66,8 @@ MODEL_IDS = {'Cnn_9layers_Gru_FrameAtt': 0, 'Cnn_9layers_Transformer_FrameAtt': 
              'Cnn_9layers_Conformer_FrameAtt': 7, 'Cnn_9layers_Conformer_FrameAvg': 8,
              'Cnn_14layers_Gru_FrameAtt': 10, 'Cnn_14layers_Transformer_FrameAtt': 11,   # 9 is not assigned
              'Cnn14_DecisionLevelAtt': 13,                                              # nor is 12
-             'VGGish_FrameAtt': 15, 'VGGish_Gru_FrameAtt': 16, 'VGGish_FrameAvg': 17}   # nor is 14
+             'VGGish_FrameAtt': 15, 'VGGish_Gru_FrameAtt': 16, 'VGGish_FrameAvg': 17,   # nor is 14
+             'Cnn_14layers_Conformer_FrameAtt': 19}                                     # nor is 18
 FEATURE_IDS = {'logmel': 0, 'gamma': 1}
 
 
@@ -304,13 +308,13 @@ class _ConformerBlock(nn.Module):
 class ConformerEncoder(nn.Module):
     """conformer/conformer_encoder.py:7-29 (weights only).  The native encoder
     implements the reference's one shape: (512, 144, 3 blocks, 576, 4 heads,
-    kernel 7)."""
+    kernel 7), with idim 2048 on the 14-layer trunk."""
 
     def __init__(self, idim, adim=144, dropout_rate=0.1, elayers=3, eunits=576, aheads=4, kernel_size=7):
         super().__init__()
-        if (idim, adim, elayers, eunits, aheads, kernel_size) != (512, 144, 3, 576, 4, 7):
+        if idim not in (512, 2048) or (adim, elayers, eunits, aheads, kernel_size) != (144, 3, 576, 4, 7):
             raise ValueError('the native Conformer encoder implements the reference shape '
-                             '(idim 512, adim 144, elayers 3, eunits 576, aheads 4, kernel_size 7)')
+                             '(idim 512 or 2048, adim 144, elayers 3, eunits 576, aheads 4, kernel_size 7)')
         self.input_layer = nn.Sequential(nn.Linear(idim, adim), nn.LayerNorm(adim), nn.Dropout(dropout_rate),
                                          nn.ReLU(), _PositionalEncoding(adim, dropout_rate))
         self.conformer_blocks = nn.Sequential(*[_ConformerBlock(adim, eunits, aheads, dropout_rate, kernel_size)
@@ -733,6 +737,7 @@ class _ConformerModel(_SedModel):
     sequence holds at most 5000 frames (the ``pe`` table)."""
     _embedding_width = 144
     _head_classes = None       # the handle's class count when it is not classes_num
+    _trunk_width = 512         # the encoder's input: 2048 on the 14-layer trunk (conv_block5, conv_block6)
 
     def __init__(self, sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num,
                  cnn_kwargs=None, encoder_kwargs=None, encoder_type='Conformer', pooling='token',
@@ -752,10 +757,13 @@ class _ConformerModel(_SedModel):
         self.pooling = pooling
         self.encoder_kwargs = {'adim': 144, 'aheads': 4, 'dropout_rate': 0.1, 'elayers': 3, 'eunits': 576,
                                'kernel_size': 7}
-        self.encoder = ConformerEncoder(512, **self.encoder_kwargs)
+        if self._trunk_width == 2048:
+            self.conv_block5 = ConvBlock(512, 1024)
+            self.conv_block6 = ConvBlock(1024, 2048)
+        self.encoder = ConformerEncoder(self._trunk_width, **self.encoder_kwargs)
         self._build_head(classes_num)
-        self.classifier = nn.Linear(144, classes_num)      # unused in forward (models.py:1290, :1505)
-        self.linear_emb = nn.Linear(1, 512)                # unused in forward (pooling == "token")
+        self.classifier = nn.Linear(144, classes_num)      # unused in forward (models.py:1290, :1505, :1727)
+        self.linear_emb = nn.Linear(1, self._trunk_width)  # unused in forward (pooling == "token")
 
     def forward(self, x, mixup_lambda=None, timeshift=False, spec_augment=True, mask=None):
         if mask is not None:
@@ -783,6 +791,34 @@ class Cnn_9layers_Conformer_FrameAvg(_ConformerModel):
 
     def _build_head(self, classes_num):
         self.fc = nn.Linear(144, classes_num, bias=True)
+
+
+class Cnn_14layers_Conformer_FrameAtt(_ConformerModel):
+    """pytorch/models.py:1627-1801: the 14-layer trunk (blocks 1-5 pooled 2x2,
+    block 6's frequency mean: ``data_length // hop // 32`` sequence frames of
+    2048 channels), ``ConformerEncoder(2048, 144, ...)``, ``AttBlock(144, 25)``
+    -- 25 classes whatever ``classes_num`` is (:1725).  ``feature_type`` is
+    accepted and ignored (always logmel).  Every sequence frame is repeated
+    ``1000 // seq_len`` times; unless that gives 1000 frames the last one is
+    repeated up to the next multiple of 100 (10 s: 31 x 32 = 992 -> 1000; a 5 s
+    window: 15 x 66 = 990 -> 1000).  Fewer than 32 input frames raise as in the
+    reference; more than 1000 sequence frames raise (the reference returns an
+    empty framewise tensor).  embedding = the encoder output (batch, 144,
+    seq).  Block 4's conv2, blocks 5-6, the encoder and the head run fp32 in
+    every precision mode."""
+    _model_name = 'Cnn_14layers_Conformer_FrameAtt'
+    _head_classes = 25
+    _trunk_width = 2048
+
+    def __init__(self, sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num, feature_type,
+                 cnn_kwargs=None, encoder_kwargs=None, encoder_type='Conformer', pooling='token',
+                 layer_init='pytorch'):
+        super().__init__(sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num,
+                         cnn_kwargs=cnn_kwargs, encoder_kwargs=encoder_kwargs, encoder_type=encoder_type,
+                         pooling=pooling, layer_init=layer_init)
+
+    def _build_head(self, classes_num):
+        self.att_block = AttBlock(n_in=144, n_out=25, activation='sigmoid')
 
 
 class _Deep14Model(_SedModel):
