@@ -39,7 +39,6 @@ struct sedx_handle : sedx::Model {
   bool finalized = false;
   void* blob = nullptr;      // single device allocation for all packed weights
   DevWeights w;
-  bool emb_cla = false;      // d_embedding is cla [B][C][T3] (models.py:683-686, :459), else the head's input transposed
   int g_nfft = 0, g_hop = 0;   // gammatone FFT size and hop (prepare_weights)
   void* ws = nullptr;        // cached workspace
   size_t ws_bytes = 0;
@@ -183,15 +182,10 @@ sedx_status preflight(sedx_handle* h) {
 // the geometry the size queries answer for: L_or_T = samples (logmel) or frames (gamma)
 sedx_status query_geometry(const sedx_handle* h, int64_t L_or_T, Geometry* g) {
   *g = geometry_from_T(*h, h->cfg.feature_type == SEDX_FEATURE_GAMMA ? L_or_T : conv_T(*h, L_or_T));
-  if (conformer14_too_long(*h, g->Ts)) return fail(h, SEDX_EINVAL, CF14_REFUSAL, (long long)g->Ts);
-  if (seq_too_long(*h, g->Ts))
-    return fail(h, SEDX_EINVAL, "%lld sequence frames: the Conformer encoder holds %d", (long long)g->Ts, CF_MAX_T);
-  // the 14-layer models have no output below 32 frames (the reference's fifth
-  // avg_pool2d raises): the queries reject what the forward rejects
-  if (h->depth == 14 && g->Ts < 1) return fail(h, SEDX_EINVAL, "input too short for the 5 pooling stages");
-  if (decision_pad_negative(*h, g->T)) return fail(h, SEDX_EINVAL, DECISION_PAD_REFUSAL, (long long)g->T);
-  char why[96];   // the VGGish models: what plan_forward refuses, the queries refuse
-  if (vgg_refusal(*h, g->T, why, sizeof(why))) return fail(h, SEDX_EINVAL, "%s", why);
+  char buf[96];
+  const char* why = shape_refusal(*h, g->T, buf, sizeof(buf));   // the queries reject what the forward rejects ...
+  // ... but one: on the 9-layer trunk the size of an input too short for any forward is still reported (frames 0)
+  if (why && !(h->depth == 9 && g->Ts < 1)) return fail(h, SEDX_EINVAL, "%s", why);
   return SEDX_OK;
 }
 
@@ -372,15 +366,23 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
   float* Hs = ws + p.Hs.off;
   float* O = ws + p.O.off;
   float* LG = ws + p.LG.off;
-  // GEMMs: x3 split-bf16 MFMA in x3 mode, fp32 MFMA in exact mode.  (Their
-  // order from here to the head finish is what plan_gemm_launches lists,
-  // plan.cpp: sedx_gemm_launch_plan's rows.)
-  auto linear = [&](const float* a, const float* wf, void* wx, int n, int bn, const float* bias, float* c,
-                    int act) {
-    if (x3)
-      launch_linear_x3(a, M, 512, wx, n, bn, bias, c, act, s);
-    else
-      launch_linear(a, M, 512, wf, n, bias, c, act, s);
+  // GEMMs: M, K, N and act of every launch from here to the head finish are the plan's next row (p.gemms, which
+  // sedx_gemm_launch_plan reports); a launch the plan does not list is not issued, and is SEDX_ESTATE below
+  int used = 0;
+  bool drift = false;
+  auto next_row = [&](bool cf) -> const GemmRow* {
+    const GemmRow* r = used < p.ngemms && (p.gemms[used].launcher == GEMM_BY_CF) == cf ? &p.gemms[used] : nullptr;
+    ++used, drift |= !r;
+    return r;
+  };
+  // x3 split-bf16 MFMA or fp32 MFMA, by the row (bn: the x3 kernel's tile width)
+  auto linear = [&](const float* a, const float* wf, void* wx, int bn, const float* bias, float* c) {
+    const GemmRow* r = next_row(false);
+    if (r && r->launcher == GEMM_BY_X3) launch_linear_x3(a, r->M, r->K, wx, r->N, bn, bias, c, r->act, s);
+    else if (r) launch_linear(a, r->M, r->K, wf, r->N, bias, c, r->act, s);
+  };
+  auto cf_gemm = [&](const float* a, const float* wgt, const float* bias, const float* res, float* c, int epi) {
+    if (const GemmRow* r = next_row(true)) launch_cf_gemm(a, r->M, r->K, wgt, r->N, bias, res, c, epi, s);
   };
   // the head's input [M][512]: the sequence layer's output, or (no sequence
   // layer: no projection, no recurrence / MHA launch) the stage-8 buffer itself
@@ -400,83 +402,75 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
     // r and r_k = r_net(r) of every block: on device, every forward
     launch_cf_relpos(w.cf_inv_freq, T3, CF_BLOCKS, Rr, s);
     for (int b = 0; b < CF_BLOCKS; ++b)
-      launch_cf_gemm(Rr + (size_t)b * T3 * CF_D, T3, CF_D, w.cf[b].rnet, CF_D, nullptr, nullptr,
-                     RK + (size_t)b * T3 * CF_D, CF_EPI_NONE, s);
-    // input layer (conformer_encoder.py:22-28): K = the trunk's width, 512 or (14-layer) 2048
-    launch_cf_gemm(S, M, h->sw, w.cf_in_w, CF_D, w.cf_in_b, nullptr, Xn, CF_EPI_NONE, s);
+      cf_gemm(Rr + (size_t)b * T3 * CF_D, w.cf[b].rnet, nullptr, nullptr, RK + (size_t)b * T3 * CF_D, CF_EPI_NONE);
+    // input layer (conformer_encoder.py:22-28): K = the trunk's width
+    cf_gemm(S, w.cf_in_w, w.cf_in_b, nullptr, Xn, CF_EPI_NONE);
     launch_cf_input_norm(Xn, iB, T3, w.cf_in_g, w.cf_in_be, w.cf_pe, X, s);
     capture(h, 20, X, nx, s);
     for (int b = 0; b < CF_BLOCKS; ++b) {
       const CfBlockWeights& c = w.cf[b];
       auto ffn = [&](int f) {              // x = 0.5 ffn(x) + x
         launch_cf_layernorm(X, M, c.ffn_g[f], c.ffn_be[f], Xn, s);
-        launch_cf_gemm(Xn, M, CF_D, c.ffn_w1[f], CF_FF, c.ffn_b1[f], nullptr, Hb, CF_EPI_SWISH, s);
-        launch_cf_gemm(Hb, M, CF_FF, c.ffn_w2[f], CF_D, c.ffn_b2[f], X, X, CF_EPI_HALF_RES, s);
+        cf_gemm(Xn, c.ffn_w1[f], c.ffn_b1[f], nullptr, Hb, CF_EPI_SWISH);
+        cf_gemm(Hb, c.ffn_w2[f], c.ffn_b2[f], X, X, CF_EPI_HALF_RES);
       };
       ffn(0);
       capture(h, 21 + 4 * b, X, nx, s);
       // mhsa: x = x + o_net(attention(qkv_net(LN(x))))
       launch_cf_layernorm(X, M, c.att_g, c.att_be, Xn, s);
-      launch_cf_gemm(Xn, M, CF_D, c.wqkv, 3 * CF_D, nullptr, nullptr, Hb, CF_EPI_NONE, s);
+      cf_gemm(Xn, c.wqkv, nullptr, nullptr, Hb, CF_EPI_NONE);
       launch_cf_relattn(Hb, iB, T3, RK + (size_t)b * T3 * CF_D, c.rwb, c.rrb, AV, s);
-      launch_cf_gemm(AV, M, CF_D, c.wo, CF_D, nullptr, X, X, CF_EPI_RES, s);
+      cf_gemm(AV, c.wo, nullptr, X, X, CF_EPI_RES);
       capture(h, 22 + 4 * b, X, nx, s);
       // conv module: x = conv(x) + x
       launch_cf_layernorm(X, M, c.cv_g, c.cv_be, Xn, s);
-      launch_cf_gemm(Xn, M, CF_D, c.pw1_w, 2 * CF_D, c.pw1_b, nullptr, Hb, CF_EPI_NONE, s);
+      cf_gemm(Xn, c.pw1_w, c.pw1_b, nullptr, Hb, CF_EPI_NONE);
       launch_cf_glu_dwconv(Hb, iB, T3, c.dw_wt, c.dw_b, AV, s);
-      launch_cf_gemm(AV, M, CF_D, c.pw2_w, CF_D, c.pw2_b, X, X, CF_EPI_RES, s);
+      cf_gemm(AV, c.pw2_w, c.pw2_b, X, X, CF_EPI_RES);
       capture(h, 23 + 4 * b, X, nx, s);
       ffn(1);
       launch_cf_layernorm(X, M, c.norm_g, c.norm_be, X, s);
       capture(h, 24 + 4 * b, X, nx, s);
     }
     HI = X;
-  } else if (h->depth == 14) {
-    // fp32 in every precision mode: the generic fp32 GEMM at the new widths
-    if (h->seq == SEQ_GRU) {
-      launch_linear(S, M, 2048, w.w_ih, 6144, w.b_ih, G, 0, s);
-      launch_gru1024(G, iB, T3, w.whh, w.bhh, Hs, s);
-    } else {
-      launch_linear(S, M, 2048, w.wqkv, 1536, w.bqkv, G, 0, s);
-      launch_mha(G, iB, T3, O, s);
-      launch_linear(O, M, 512, w.wfc, 2048, w.bfc, Hs, 1, s);
-    }
   } else if (h->seq == SEQ_GRU) {
-    linear(S, w.w_ih, w.w_ih_x3, 1536, 128, w.b_ih, G, 0);
-    if (p.gru_variant < 0)
+    linear(S, w.w_ih, w.w_ih_x3, 128, w.b_ih, G);
+    if (h->depth == 14)
+      launch_gru1024(G, iB, T3, w.whh, w.bhh, Hs, s);
+    else if (p.gru_variant < 0)
       launch_gru(G, iB, T3, w.whhT, w.bhh, Hs, s);
     else
       launch_gru_coop(G, iB, T3, w.whh, w.bhh, Hs, ws + p.gru.off, !x3, p.gru_fast, p.gru_variant, h->gru_err_dev,
                       (unsigned)t.gru_spin, s, p.gru_spread);
   } else if (h->seq == SEQ_MHA) {
-    linear(S, w.wqkv, w.wqkv_x3, 1536, 128, w.bqkv, G, 0);
+    linear(S, w.wqkv, w.wqkv_x3, 128, w.bqkv, G);
     launch_mha(G, iB, T3, O, s);
-    linear(O, w.wfc, w.wfc_x3, 512, 128, w.bfc, Hs, 1);
+    linear(O, w.wfc, w.wfc_x3, 128, w.bfc, Hs);
   }
   capture(h, 9, HI, (size_t)M * h->hw, s);
   mark(h, 10, s);
   // head projection (att|cla rows or fc rows, zero-padded to nac), then its finish
-  if (h->seq == SEQ_CONFORMER)
-    launch_cf_gemm(HI, M, CF_D, w.wac, h->nac, w.bac, nullptr, LG, CF_EPI_NONE, s);
-  else if (h->depth == 14)
-    launch_linear(HI, M, 2048, w.wac, h->nac, w.bac, LG, 0, s);
-  else
-    linear(HI, w.wac, w.wac_x3, h->nac, 64, w.bac, LG, 0);
-  if (conformer14(*h)) capture(h, 44, LG, (size_t)M * h->nac, s);
-  if (h->vgg && h->head == HEAD_ATT)   // x12, padded to 1000 frames
-    launch_vgg_att_head(LG, iB, T3, h->cfg.classes_num, h->nac, (int)g.out_frames, g.rep, d_fw, d_clip, d_emb, s);
-  else if (h->vgg)                     // x(1000 // seq_len), padded to 1000 frames, the mean over all of them
-    launch_vgg_fc_head(LG, iB, T3, h->cfg.classes_num, h->nac, (int)g.out_frames, g.rep, d_fw, d_clip, s);
-  else if (conformer14(*h))            // x(1000 // seq_len), padded to 1000 or the next multiple of 100
-    launch_att_head_rep(LG, iB, T3, h->cfg.classes_num, h->nac, (int)g.out_frames, g.rep, d_fw, d_clip, s);
-  else if (h->head == HEAD_ATT)
-    launch_att_head(LG, iB, T3, h->cfg.classes_num, h->nac, (int)g.out_frames, d_fw, d_clip,
-                    h->emb_cla && !h->decision ? d_emb : nullptr, s, g.rep);
-  else
-    launch_fc_head(LG, iB, T3, h->cfg.classes_num, h->nac, h->head == HEAD_FC_MAX, d_fw, d_clip, s,
-                   (int)g.out_frames);
-  if (!h->emb_cla && !h->decision && d_emb) launch_transpose_btd(HI, iB, T3, h->hw, d_emb, s);
+  if (h->seq == SEQ_CONFORMER) cf_gemm(HI, w.wac, w.bac, nullptr, LG, CF_EPI_NONE);
+  else linear(HI, w.wac, w.wac_x3, 64, w.bac, LG);
+  if (drift || used != p.ngemms)
+    return fail(h, SEDX_ESTATE, "the forward's GEMM launches (%d) are not the %d its plan lists", used, p.ngemms);
+  const int C = h->cfg.classes_num, frames = (int)g.out_frames;
+  float* emb_cla = h->emb == EMB_CLA ? d_emb : nullptr;
+  switch (h->head_launch) {
+    case HEAD_LAUNCH_VGG_ATT:   // x12, padded to 1000 frames
+      launch_vgg_att_head(LG, iB, T3, C, h->nac, frames, g.rep, d_fw, d_clip, emb_cla, s);
+      break;
+    case HEAD_LAUNCH_VGG_FC:    // x(1000 // seq_len), padded to 1000 frames, the mean over all of them
+      launch_vgg_fc_head(LG, iB, T3, C, h->nac, frames, g.rep, d_fw, d_clip, s);
+      break;
+    case HEAD_LAUNCH_ATT_REP:   // x(1000 // seq_len), padded to 1000 or the next multiple of 100
+      capture(h, 44, LG, (size_t)M * h->nac, s);
+      launch_att_head_rep(LG, iB, T3, C, h->nac, frames, g.rep, d_fw, d_clip, s);
+      break;
+    case HEAD_LAUNCH_ATT: launch_att_head(LG, iB, T3, C, h->nac, frames, d_fw, d_clip, emb_cla, s, g.rep); break;
+    default: launch_fc_head(LG, iB, T3, C, h->nac, h->head == HEAD_FC_MAX, d_fw, d_clip, s, frames);
+  }
+  if (h->emb == EMB_HEAD_INPUT && d_emb) launch_transpose_btd(HI, iB, T3, h->hw, d_emb, s);
   mark(h, 11, s);
   return launch_status(h);
 }
@@ -523,7 +517,7 @@ sedx_status sedx_set_capture(sedx_handle* h, int32_t stage, float* d_buf, size_t
   const bool cf_stage = h->seq == SEQ_CONFORMER && stage >= 20 && stage <= 20 + 4 * CF_BLOCKS;
   const bool deep_stage = h->depth == 14 && stage >= 40 && stage <= 43;   // blocks 5-6 of the 14-layer trunk
   const bool vgg_stage = h->vgg && stage >= 50 && stage <= 55;            // the VGGish trunk's launches
-  const bool lg_stage = conformer14(*h) && stage == 44;                   // Cnn_14layers_Conformer_FrameAtt's logits
+  const bool lg_stage = h->head_launch == HEAD_LAUNCH_ATT_REP && stage == 44;   // Cnn_14layers_Conformer_FrameAtt's logits
   if (h->vgg && stage >= 1 && stage <= 7) return fail(h, SEDX_EINVAL, "stage %d cannot be captured", (int)stage);
   if (stage == 1 || (stage > 9 && !cf_stage && !deep_stage && !vgg_stage && !lg_stage)) return fail(h, SEDX_EINVAL, "stage %d cannot be captured", (int)stage);
   h->cap_stage = stage;
@@ -564,18 +558,15 @@ sedx_status sedx_create(const sedx_config* cfg, int device, sedx_handle** out) {
   *out = nullptr;
   if (cfg->mel_bins != 64) return SEDX_EINVAL;
   if (cfg->window_size != 256 && cfg->window_size != 512 && cfg->window_size != 1024) return SEDX_EINVAL;
-  // 256 classes; AudioSet's 527 for Cnn14_DecisionLevelAtt alone (weights.h)
-  const int max_classes = cfg->model_type == SEDX_MODEL_CNN14_DECISIONLEVELATT ? DECISION_MAX_CLASSES : MAX_CLASSES;
-  if (cfg->hop_size <= 0 || cfg->sample_rate <= 0 || cfg->classes_num <= 0 || cfg->classes_num > max_classes)
+  if (cfg->hop_size <= 0 || cfg->sample_rate <= 0 || cfg->classes_num <= 0 || cfg->classes_num > DECISION_MAX_CLASSES)
     return SEDX_EINVAL;
   if (cfg->feature_type == SEDX_FEATURE_GAMMA && cfg->model_type != SEDX_MODEL_GRU_FRAMEATT)
     return SEDX_EINVAL;
   Model m;   // after the range checks: nac is computed from classes_num
-  if (!make_model(*cfg, &m)) return SEDX_EINVAL;
+  if (!make_model(*cfg, &m) || cfg->classes_num > m.max_classes) return SEDX_EINVAL;
   sedx_handle* h = new sedx_handle();
   static_cast<Model&>(*h) = m;
   h->device = device;
-  h->emb_cla = m.head == HEAD_ATT && m.seq != SEQ_MHA && m.seq != SEQ_CONFORMER;
   h->expected = expected_params(m);
   *out = h;
   return SEDX_OK;
@@ -788,7 +779,7 @@ sedx_status sedx_gemm_launch_plan(const sedx_handle* h, int64_t B, int64_t L_or_
     ncu = device_cus();
   }
   int n = 0;
-  for (const GemmRow& r : plan_gemm_launches(*h, h->tune, p, ncu)) {   // run_body's launch order
+  for (const GemmRow& r : plan_gemm_launches(p, ncu)) {   // run_body's launch order
     if (n < capacity) rows[n] = sedx_gemm_launch{r.stage, r.M, r.K, r.N, r.act, r.l.kernel, r.l.grid_x, r.l.grid_y};
     ++n;
   }

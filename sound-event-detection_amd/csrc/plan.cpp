@@ -10,6 +10,7 @@
 namespace sedx {
 
 Geometry geometry_from_T(const Model& m, int64_t T) {
+  const FrameRule& r = m.frames;
   Geometry g;
   g.T = T;
   g.T1 = T / 2;
@@ -17,45 +18,32 @@ Geometry geometry_from_T(const Model& m, int64_t T) {
   g.T3 = g.T2 / 2;
   g.T4 = g.T3 / 2;
   g.T5 = g.T4 / 2;
-  if (m.vgg) {
-    // four flooring max pools; x12 (models.py:2342, :2444) or x(1000 // seq_len) (:2578), then the last frame
-    // repeated up to exactly 1000 frames (:2376, :2478, :2580-2582).  Shapes no forward runs keep rep 1.
-    g.Ts = g.T4;
-    g.rep = m.head == HEAD_ATT ? VGG_ATT_REPEAT : g.Ts >= 1 && g.Ts <= VGG_OUT_FRAMES ? (int)(VGG_OUT_FRAMES / g.Ts) : 1;
-    g.fw_len = g.rep * g.Ts;
-    g.out_frames = VGG_OUT_FRAMES;
-    return g;
-  }
-  const bool deep = m.depth == 14;
-  g.Ts = deep ? g.T5 : g.T3;
-  g.rep = deep ? 32 : 8;   // interpolate_ratio (models.py:741, :1133)
-  // Cnn_14layers_Conformer_FrameAtt: 1000 // seq_len (models.py:1791).  Shapes no forward runs keep 32.
-  if (conformer14(m) && g.Ts >= 1 && g.Ts <= CF14_FRAMES) g.rep = (int)(CF14_FRAMES / g.Ts);
+  g.Ts = r.pools == 3 ? g.T3 : r.pools == 4 ? g.T4 : g.T5;
+  // a fixed repeat, or 1000 // seq_len; shapes no forward runs keep -rep
+  g.rep = r.rep > 0 ? r.rep : g.Ts >= 1 && g.Ts <= r.max_seq ? (int)(1000 / g.Ts) : -r.rep;
   g.fw_len = g.rep * g.Ts;
   g.out_frames = g.fw_len;
-  // pad_framewise_output(roundup) models.py:678-681: Cnn_9layers_Gru_FrameAtt
-  // (Cnn_9layers_Gru_FrameAvg returns the 8 T3 frames, :551) and the two
-  // Conformer models (:1359-1360, :1571-1572)
-  // and the 14-layer models (:783-784, :1176-1177, :1793-1794)
-  const bool pad100 = m.cfg.model_type == SEDX_MODEL_GRU_FRAMEATT || m.seq == SEQ_CONFORMER || deep;
-  if (m.decision) {
-    // Cnn14_DecisionLevelAtt: frames_num = T - 1 (models.py:2738, :2778), not a multiple of 100; where the
-    // model has no output (T < 32, T % 32 == 0: refused by every caller) the repeated frames stand
-    if (g.Ts >= 1 && T % 32 != 0) g.out_frames = T - 1;
-  } else if (pad100 && g.fw_len != 1000)
-    g.out_frames = (g.fw_len % 100 == 0) ? g.fw_len : g.fw_len + 100 - g.fw_len % 100;
+  if (r.pad == PAD_TO_1000) g.out_frames = 1000;
+  else if (r.pad == PAD_TO_100 && g.fw_len != 1000 && g.fw_len % 100 != 0) g.out_frames = g.fw_len + 100 - g.fw_len % 100;
+  // where the model has no output (too few frames, a multiple of 32: refused by every caller) the repeated frames stand
+  else if (r.pad == PAD_TO_T_LESS_1 && g.Ts >= 1 && T % 32 != 0) g.out_frames = T - 1;
   return g;
 }
 
-const char* vgg_refusal(const Model& m, int64_t T, char* buf, size_t n) {
-  if (!m.vgg) return nullptr;
-  const int64_t seq = T / 16;
-  if (seq < 1) snprintf(buf, n, "%lld frames: the VGGish trunk's 4 pooling stages need 16", (long long)T);
-  else if (m.head == HEAD_ATT && seq > VGG_ATT_MAX_SEQ)
-    snprintf(buf, n, "%lld sequence frames: x12 passes the 1000-frame output (at most %d)", (long long)seq, VGG_ATT_MAX_SEQ);
-  else if (seq > VGG_OUT_FRAMES)
-    snprintf(buf, n, "%lld sequence frames: VGGish_FrameAvg has 1000 output frames", (long long)seq);
-  else return nullptr;
+const char* shape_refusal(const Model& m, int64_t T, char* buf, size_t n) {
+  const FrameRule& r = m.frames;
+  const long long seq = geometry_from_T(m, T).Ts;
+  if (seq < 1 && m.vgg)
+    snprintf(buf, n, "%lld frames: the VGGish trunk's %d pooling stages need %d", (long long)T, r.pools, 1 << r.pools);
+  else if (seq < 1) snprintf(buf, n, "input too short for the %d pooling stages", r.pools);
+  else if (r.pad == PAD_TO_T_LESS_1 && T % 32 == 0)
+    snprintf(buf, n, "%lld frames: a multiple of 32 has no output (the reference pads by -1 frames)", (long long)T);
+  else if (seq <= r.max_seq) return nullptr;
+  else if (r.pad == PAD_TO_1000 && r.rep > 0)
+    snprintf(buf, n, "%lld sequence frames: x%d passes the 1000-frame output (at most %d)", seq, r.rep, r.max_seq);
+  else if (r.pad == PAD_TO_1000) snprintf(buf, n, "%lld sequence frames: VGGish_FrameAvg has 1000 output frames", seq);
+  else if (r.rep < 0) snprintf(buf, n, "%lld sequence frames: more than %d leave no framewise output", seq, r.max_seq);
+  else snprintf(buf, n, "%lld sequence frames: the Conformer encoder holds %d", seq, r.max_seq);
   return buf;
 }
 
@@ -146,7 +134,7 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
   size_t e_head = a0;
   // (Cnn14_DecisionLevelAtt: H [M][2048] and the logits only)
   // (Cnn_14layers_Conformer_FrameAtt: none of G / H / O; the encoder's regions below)
-  const bool cf14 = conformer14(m);
+  const bool cf14 = deep && m.seq == SEQ_CONFORMER;
   p->G = take(e_head, m.decision || cf14 ? 0 : M * (deep && m.seq == SEQ_GRU ? 6144 : 1536));
   p->Hs = take(e_head, cf14 ? 0 : M * (deep ? 2048 : 512));
   p->O = take(e_head, m.decision || cf14 ? 0 : M * 512);
@@ -177,17 +165,33 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
     p->layers[i].out = i % 2 ? p->A.off : p->P.off;
   }
   if (p->block1 == B1_F23_FUSED) p->layers[0].in = p->x0.off;
+  // ---- the sequence layer's and the head's GEMMs, in launch order ----
+  // fp32 (launch_linear) on the 14-layer trunk in every mode, split-bf16 elsewhere in x3 mode; the Conformer
+  // encoder and its head by launch_cf_gemm in every mode
+  p->ngemms = 0;
+  auto gemm = [&](int stage, int Mr, int K, int N, int act, int by) {
+    p->gemms[p->ngemms++] = GemmRow{stage, Mr, K, N, act, by, GemmLaunch{}};
+  };
+  const int by = x3 && !deep ? GEMM_BY_X3 : GEMM_BY_LINEAR, Mi = p->M;
+  if (m.seq == SEQ_CONFORMER) {
+    for (int b = 0; b < CF_BLOCKS; ++b) gemm(9, (int)g.Ts, CF_D, CF_D, 0, GEMM_BY_CF);   // r_net of every block
+    gemm(9, Mi, m.sw, CF_D, 0, GEMM_BY_CF);                                              // input layer
+    for (int b = 0; b < CF_BLOCKS; ++b) {
+      gemm(9, Mi, CF_D, CF_FF, 0, GEMM_BY_CF), gemm(9, Mi, CF_FF, CF_D, 0, GEMM_BY_CF);      // ffn1
+      gemm(9, Mi, CF_D, 3 * CF_D, 0, GEMM_BY_CF), gemm(9, Mi, CF_D, CF_D, 0, GEMM_BY_CF);    // mhsa: qkv_net, o_net
+      gemm(9, Mi, CF_D, 2 * CF_D, 0, GEMM_BY_CF), gemm(9, Mi, CF_D, CF_D, 0, GEMM_BY_CF);    // conv module: pointwise convs
+      gemm(9, Mi, CF_D, CF_FF, 0, GEMM_BY_CF), gemm(9, Mi, CF_FF, CF_D, 0, GEMM_BY_CF);      // ffn2
+    }
+  } else if (m.seq == SEQ_GRU) {
+    gemm(9, Mi, m.sw, 3 * m.sw, 0, by);                            // both directions' gates: 1536, or 6144
+  } else if (m.seq == SEQ_MHA) {
+    gemm(9, Mi, m.sw, 1536, 0, by), gemm(9, Mi, 512, m.sw, 1, by);   // q|k|v, then fc + ReLU
+  }   // (launch_decision pools inside its own fc1 staging: not a GEMM launcher's launch)
+  gemm(10, Mi, m.hw, m.nac, 0, m.seq == SEQ_CONFORMER ? GEMM_BY_CF : by);   // the head projection
   // ---- shapes no forward runs ----
   p->reject[0] = 0;
-  if (vgg_refusal(m, T, p->reject, sizeof(p->reject))) {
-  } else if (g.T3 < 1) snprintf(p->reject, sizeof(p->reject), "input too short for the 3 pooling stages");
-  else if (g.Ts < 1) snprintf(p->reject, sizeof(p->reject), "input too short for the 5 pooling stages");
-  else if (decision_pad_negative(m, T)) snprintf(p->reject, sizeof(p->reject), DECISION_PAD_REFUSAL, (long long)T);
-  else if (conformer14_too_long(m, g.Ts)) snprintf(p->reject, sizeof(p->reject), CF14_REFUSAL, (long long)g.Ts);
-  else if (seq_too_long(m, g.Ts))
-    snprintf(p->reject, sizeof(p->reject), "%lld sequence frames: the Conformer encoder holds %d", (long long)g.Ts,
-             CF_MAX_T);
-  else if (B * g.T > INT32_MAX / 64) snprintf(p->reject, sizeof(p->reject), "batch too large");   // 32-bit launch sizes
+  if (!shape_refusal(m, T, p->reject, sizeof(p->reject)) && B * g.T > INT32_MAX / 64)
+    snprintf(p->reject, sizeof(p->reject), "batch too large");   // 32-bit launch sizes
   return p->reject[0] ? p->reject : nullptr;
 }
 
@@ -379,44 +383,11 @@ GemmLaunch plan_linear_launch(int M, int K, int N, int act, int ncu) {
   return GemmLaunch{GEMM_TILED, tx, ty, 256};
 }
 
-std::vector<GemmRow> plan_gemm_launches(const Model& m, const Tuning& t, const ForwardPlan& p, int ncu) {
-  std::vector<GemmRow> rows;
-  const int M = p.M, T3 = (int)p.g.Ts;
-  const bool deep = m.depth == 14;
-  // launch_linear's rows are planned; the 9-layer families' GEMMs run launch_linear_x3 in x3 mode
-  auto fp32 = [&](int stage, int K, int N, int act) {
-    rows.push_back(GemmRow{stage, M, K, N, act, plan_linear_launch(M, K, N, act, ncu)});
-  };
-  auto linear = [&](int stage, int N, int act) {
-    if (t.precision == SEDX_PRECISION_X3) rows.push_back(GemmRow{stage, M, 512, N, act, GemmLaunch{GEMM_X3, 0, 0, 0}});
-    else fp32(stage, 512, N, act);
-  };
-  auto cf = [&](int stage, int Mr, int K, int N) {
-    rows.push_back(GemmRow{stage, Mr, K, N, 0, GemmLaunch{GEMM_CONFORMER, 0, 0, 0}});
-  };
-  if (m.decision) {
-    // launch_decision pools inside its own fc1 staging: not a GEMM launcher's launch
-  } else if (m.seq == SEQ_CONFORMER) {
-    for (int b = 0; b < CF_BLOCKS; ++b) cf(9, T3, CF_D, CF_D);   // r_net of every block
-    cf(9, M, m.sw, CF_D);                                        // input layer (K 512, or 2048 on the 14-layer trunk)
-    for (int b = 0; b < CF_BLOCKS; ++b) {
-      cf(9, M, CF_D, CF_FF), cf(9, M, CF_FF, CF_D);              // ffn1
-      cf(9, M, CF_D, 3 * CF_D), cf(9, M, CF_D, CF_D);            // mhsa: qkv_net, o_net
-      cf(9, M, CF_D, 2 * CF_D), cf(9, M, CF_D, CF_D);            // conv module: the two pointwise convs
-      cf(9, M, CF_D, CF_FF), cf(9, M, CF_FF, CF_D);              // ffn2
-    }
-  } else if (deep) {
-    if (m.seq == SEQ_GRU) fp32(9, 2048, 6144, 0);
-    else fp32(9, 2048, 1536, 0), fp32(9, 512, 2048, 1);
-  } else if (m.seq == SEQ_GRU) {
-    linear(9, 1536, 0);
-  } else if (m.seq == SEQ_MHA) {
-    linear(9, 1536, 0), linear(9, 512, 1);
-  }
-  // the head projection
-  if (m.seq == SEQ_CONFORMER) cf(10, M, CF_D, m.nac);
-  else if (deep) fp32(10, 2048, m.nac, 0);
-  else linear(10, m.nac, 0);
+std::vector<GemmRow> plan_gemm_launches(const ForwardPlan& p, int ncu) {
+  std::vector<GemmRow> rows(p.gemms, p.gemms + p.ngemms);
+  for (GemmRow& r : rows)   // launch_linear_x3 and launch_cf_gemm keep their own shape choice
+    r.l = r.launcher == GEMM_BY_LINEAR ? plan_linear_launch(r.M, r.K, r.N, r.act, ncu)
+                                       : GemmLaunch{r.launcher == GEMM_BY_X3 ? GEMM_X3 : GEMM_CONFORMER, 0, 0, 0};
   return rows;
 }
 
@@ -434,33 +405,25 @@ const char* window_geometry(const Model& m, int64_t L_clip, const sedx_window_sp
   wg->clip_len = spec->driver == SEDX_DRIVER_MAIN_STRONG ? std::min<int64_t>(L_clip, (int64_t)sr * 10) : L_clip;
   wg->groups.clear();
   std::vector<int64_t> frames(wg->n_win);
-  auto refuse = [&](const char* fmt, int w, long long n, int k) {
-    snprintf(wg->reject, sizeof(wg->reject), fmt, w, n, k);
-    return wg->reject;
-  };
   for (int w = 0; w < wg->n_win; ++w) {
     const int64_t len = wg->loop.len[w];
     // the model raises on these windows: STFT reflect padding needs more
-    // than n_fft/2 samples (stft.py:237), the third 2x2 pool one frame
-    // (models.py:139)
-    if (len <= m.cfg.window_size / 2)
-      return refuse("window %d has %lld samples: too short for the STFT's reflect padding", w, (long long)len, 0);
+    // than n_fft/2 samples (stft.py:237); then what every forward refuses
+    if (len <= m.cfg.window_size / 2) {
+      snprintf(wg->reject, sizeof(wg->reject), "window %d has %lld samples: too short for the STFT's reflect padding",
+               w, (long long)len);
+      return wg->reject;
+    }
     if (wg->groups.empty() || wg->groups.back().len != len) {
       WinGroup g;
       g.w0 = w;
       g.len = len;
       g.g = geometry_from_T(m, conv_T(m, len));
-      if (g.g.Ts < 1) return refuse("window %d too short for the CNN", w, 0, 0);
-      if (vgg_refusal(m, g.g.T, wg->reject, sizeof(wg->reject))) return wg->reject;
-      if (decision_pad_negative(m, g.g.T))
-        return refuse("window %d has %lld frames, a multiple of 32: Cnn14_DecisionLevelAtt has no output for it", w,
-                      (long long)g.g.T, 0);
-      if (conformer14_too_long(m, g.g.Ts))
-        return refuse("window %d gives %lld sequence frames: more than %d leave no framewise output", w,
-                      (long long)g.g.Ts, CF14_FRAMES);
-      if (seq_too_long(m, g.g.Ts))
-        return refuse("window %d gives %lld sequence frames: the Conformer encoder holds %d", w, (long long)g.g.Ts,
-                      CF_MAX_T);
+      char why[96];
+      if (shape_refusal(m, g.g.T, why, sizeof(why))) {
+        snprintf(wg->reject, sizeof(wg->reject), "window %d: %s", w, why);
+        return wg->reject;
+      }
       wg->groups.push_back(g);
     }
     ++wg->groups.back().nw;

@@ -44,33 +44,15 @@ struct Geometry {
   int rep = 8;
 };
 inline int64_t conv_T(const Model& m, int64_t L) { return L / m.cfg.hop_size + 1; }
-// the Conformer encoder's positional table has CF_MAX_T rows; the reference
-// fails on a longer sequence too (embedding.py:30: the add does not broadcast)
-// (Ts: the sequence's frames, Geometry::Ts)
-inline bool seq_too_long(const Model& m, int64_t Ts) { return m.seq == SEQ_CONFORMER && Ts > CF_MAX_T; }
-// Cnn_14layers_Conformer_FrameAtt (models.py:1627-1801): the Conformer encoder on the 14-layer trunk's T / 32
-// sequence frames.  Every sequence frame is repeated 1000 // seq_len times (:1791-1792); unless that gives 1000
-// frames the last one is repeated up to the next multiple of 100 (:1793-1794).  Past 1000 sequence frames the
-// ratio is 0 and the reference returns an empty framewise tensor: refused by the forwards and the size queries.
-constexpr int CF14_FRAMES = 1000;
-inline bool conformer14(const Model& m) { return m.depth == 14 && m.seq == SEQ_CONFORMER; }
-inline bool conformer14_too_long(const Model& m, int64_t Ts) { return conformer14(m) && Ts > CF14_FRAMES; }
-constexpr const char* CF14_REFUSAL =   // fits ForwardPlan::reject
-    "%lld sequence frames: more than 1000 leave no framewise output";
+// the model's frame rule (Model::frames, weights.h) applied to T frames; it answers for shapes no forward runs too
 Geometry geometry_from_T(const Model& m, int64_t T);
-// Cnn14_DecisionLevelAtt pads 32 (T / 32) frames to T - 1 with (T % 32) - 1 copies of
-// the last one (models.py:2738, :2778): at T % 32 == 0 that count is -1 and
-// the reference raises, so the forwards and the size queries refuse it alike
-inline bool decision_pad_negative(const Model& m, int64_t T) { return m.decision && T >= 32 && T % 32 == 0; }
-constexpr const char* DECISION_PAD_REFUSAL =   // fits ForwardPlan::reject
-    "%lld frames: a multiple of 32 has no output (the reference pads by -1 frames)";
-// The VGGish models (models.py:2284-2592): four flooring max pools, T / 16 sequence frames, always 1000 output
-// frames.  Fewer than 16 frames: the fourth pool has no output.  The two FrameAtt models repeat x12 and pad to
-// 1000: past 83 sequence frames the pad count is negative and the reference raises.  VGGish_FrameAvg repeats
-// x(1000 // seq_len): past 1000 sequence frames the reference returns an empty tensor and NaN, refused here.
-constexpr int VGG_OUT_FRAMES = 1000, VGG_ATT_REPEAT = 12, VGG_ATT_MAX_SEQ = VGG_OUT_FRAMES / VGG_ATT_REPEAT;
-// nullptr, or why no VGGish forward runs T frames (written into buf; fits ForwardPlan::reject)
-const char* vgg_refusal(const Model& m, int64_t T, char* buf, size_t n);
+// The one rule of which shapes a model refuses, by its frame rule: nullptr, or why no forward runs T frames
+// (written into buf; fits ForwardPlan::reject).  Too few frames for the trunk's pools (the reference's pool
+// raises); T - 1 frames at a multiple of 32 (the reference pads by -1 frames and raises); more sequence frames
+// than max_seq (the Conformer encoder's positional add does not broadcast, embedding.py:30; x12 passes the
+// 1000 output frames and the pad count is negative; 1000 // seq_len is 0 and the reference returns an empty
+// framewise tensor).  plan_forward, the size queries (api.cpp query_geometry) and window_geometry all ask it.
+const char* shape_refusal(const Model& m, int64_t T, char* buf, size_t n);
 
 // ---- what the handle's setters store ----------------------------------------
 struct Tuning {
@@ -116,6 +98,18 @@ struct ConvLayer {
   size_t in, out;   // float offsets in the workspace
   int order;        // a Winograd launch's round order: SEDX_TUNE_WINO_ORDER (0 for block 1's F(2x2) conv2)
 };
+// One GEMM launch of the sequence layer (stage 9) or the head projection (stage 10).  plan_forward lists them in
+// launch order; run_body (api.cpp) takes M, K, N and act of each launch from the next row and supplies the
+// pointers, and sedx_gemm_launch_plan reports the same rows.
+enum GemmLauncher { GEMM_BY_LINEAR, GEMM_BY_X3, GEMM_BY_CF };   // launch_linear, launch_linear_x3, launch_cf_gemm
+struct GemmLaunch {
+  int kernel = 0, grid_x = 0, grid_y = 0, threads = 0;   // kernel: GemmKernel (below)
+};
+struct GemmRow {
+  int stage, M, K, N, act, launcher;
+  GemmLaunch l;   // filled by plan_gemm_launches
+};
+constexpr int MAX_GEMM_ROWS = 32;   // the Conformer models: 3 r_net + input + 3 x 8 + head = 29
 struct ForwardPlan {
   Geometry g{};
   int64_t B = 0;
@@ -149,6 +143,8 @@ struct ForwardPlan {
   // ... or the Conformer encoder's x [M][144], LayerNorm(x), the hidden [M][576],
   // the attention / depthwise output, r and r_k [3][Ts][144] (and LG)
   Region X, Xn, Hb, AV, Rr, RK;
+  GemmRow gemms[MAX_GEMM_ROWS] = {};   // the sequence layer's and the head's GEMM launches, in launch order
+  int ngemms = 0;
   size_t total_bytes = 0;
   char reject[96] = {};            // plan_forward's reason
 };
@@ -198,17 +194,10 @@ enum GemmKernel {
   GEMM_X3 = SEDX_GEMM_X3,               // launch_linear_x3 and launch_cf_gemm keep their own shape choice:
   GEMM_CONFORMER = SEDX_GEMM_CONFORMER  // their rows carry the GEMM only
 };
-struct GemmLaunch {
-  int kernel = GEMM_TILED, grid_x = 0, grid_y = 0, threads = 0;
-};
 GemmLaunch plan_linear_launch(int M, int K, int N, int act, int ncu);
-// the GEMM launches of a forward plan's sequence layer (stage 9) and head
-// (stage 10) in run_body's launch order (api.cpp)
-struct GemmRow {
-  int stage, M, K, N, act;
-  GemmLaunch l;
-};
-std::vector<GemmRow> plan_gemm_launches(const Model& m, const Tuning& t, const ForwardPlan& p, int ncu);
+// sedx_gemm_launch_plan's rows: the plan's GEMM rows (ForwardPlan::gemms) with plan_linear_launch attached to
+// launch_linear's
+std::vector<GemmRow> plan_gemm_launches(const ForwardPlan& p, int ncu);
 
 // ---- windowed drivers (windows.cpp) ------------------------------------------
 // loop control of predict.py:297-338 / main_strong.py:786-832: the sample

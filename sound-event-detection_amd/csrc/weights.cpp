@@ -13,44 +13,58 @@
 namespace sedx {
 
 // ---- the model --------------------------------------------------------------
-// sedx_model -> (seq, head); false for an unknown model_type
-static bool model_parts(int32_t model_type, int* seq, int* head) {
-  switch (model_type) {
-    case SEDX_MODEL_GRU_FRAMEATT: *seq = SEQ_GRU, *head = HEAD_ATT; return true;
-    case SEDX_MODEL_TRANSFORMER_FRAMEATT: *seq = SEQ_MHA, *head = HEAD_ATT; return true;
-    case SEDX_MODEL_CNN_FRAMEMAX: *seq = SEQ_NONE, *head = HEAD_FC_MAX; return true;
-    case SEDX_MODEL_CNN_FRAMEAVG: *seq = SEQ_NONE, *head = HEAD_FC_AVG; return true;
-    case SEDX_MODEL_CNN_FRAMEATT: *seq = SEQ_NONE, *head = HEAD_ATT; return true;
-    case SEDX_MODEL_GRU_FRAMEAVG: *seq = SEQ_GRU, *head = HEAD_FC_AVG; return true;
-    case SEDX_MODEL_TRANSFORMER_FRAMEAVG: *seq = SEQ_MHA, *head = HEAD_FC_AVG; return true;
-    case SEDX_MODEL_CONFORMER_FRAMEATT: *seq = SEQ_CONFORMER, *head = HEAD_ATT; return true;
-    case SEDX_MODEL_CONFORMER_FRAMEAVG: *seq = SEQ_CONFORMER, *head = HEAD_FC_AVG; return true;
-    case SEDX_MODEL_GRU14_FRAMEATT: *seq = SEQ_GRU, *head = HEAD_ATT; return true;
-    case SEDX_MODEL_TRANSFORMER14_FRAMEATT: *seq = SEQ_MHA, *head = HEAD_ATT; return true;
-    case SEDX_MODEL_CNN14_DECISIONLEVELATT: *seq = SEQ_NONE, *head = HEAD_ATT; return true;
-    case SEDX_MODEL_VGGISH_FRAMEATT: *seq = SEQ_NONE, *head = HEAD_ATT; return true;
-    case SEDX_MODEL_VGGISH_GRU_FRAMEATT: *seq = SEQ_GRU, *head = HEAD_ATT; return true;
-    case SEDX_MODEL_VGGISH_FRAMEAVG: *seq = SEQ_NONE, *head = HEAD_FC_AVG; return true;
-    case SEDX_MODEL_CONFORMER14_FRAMEATT: *seq = SEQ_CONFORMER, *head = HEAD_ATT; return true;
-    default: return false;
-  }
-}
+// One row per model: everything the host code knows about a sedx_model follows from its row (make_model).
+// Frame rules (FrameRule, weights.h): the 9-layer trunk's three pools and x8 (interpolate_ratio, models.py:741),
+// the 14-layer trunk's five and x32 (:1133), the VGGish trunk's four and x12 (:2342, :2444) or x(1000 // seq_len)
+// (:2578; Cnn_14layers_Conformer_FrameAtt too, :1791).  max_seq: the Conformer encoder's positional table
+// (embedding.py:30 fails past it), the 1000 output frames that x12 / x(1000 // seq_len) must not pass.
+namespace {
+enum Stage { STAGE_NONE, STAGE_DECISION };   // between the trunk and the head
+struct ModelSpec {
+  int model_type, trunk, seq, head, stage;
+  FrameRule frames;
+};
+constexpr ModelSpec MODELS[] = {
+    {SEDX_MODEL_GRU_FRAMEATT, TRUNK_9, SEQ_GRU, HEAD_ATT, STAGE_NONE, {3, 8, PAD_TO_100, SEQ_ANY}},
+    {SEDX_MODEL_TRANSFORMER_FRAMEATT, TRUNK_9, SEQ_MHA, HEAD_ATT, STAGE_NONE, {3, 8, PAD_NONE, SEQ_ANY}},
+    {SEDX_MODEL_CNN_FRAMEMAX, TRUNK_9, SEQ_NONE, HEAD_FC_MAX, STAGE_NONE, {3, 8, PAD_NONE, SEQ_ANY}},
+    {SEDX_MODEL_CNN_FRAMEAVG, TRUNK_9, SEQ_NONE, HEAD_FC_AVG, STAGE_NONE, {3, 8, PAD_NONE, SEQ_ANY}},
+    {SEDX_MODEL_CNN_FRAMEATT, TRUNK_9, SEQ_NONE, HEAD_ATT, STAGE_NONE, {3, 8, PAD_NONE, SEQ_ANY}},
+    {SEDX_MODEL_GRU_FRAMEAVG, TRUNK_9, SEQ_GRU, HEAD_FC_AVG, STAGE_NONE, {3, 8, PAD_NONE, SEQ_ANY}},   // the 8 T3 frames (:551)
+    {SEDX_MODEL_TRANSFORMER_FRAMEAVG, TRUNK_9, SEQ_MHA, HEAD_FC_AVG, STAGE_NONE, {3, 8, PAD_NONE, SEQ_ANY}},
+    {SEDX_MODEL_CONFORMER_FRAMEATT, TRUNK_9, SEQ_CONFORMER, HEAD_ATT, STAGE_NONE, {3, 8, PAD_TO_100, CF_MAX_T}},
+    {SEDX_MODEL_CONFORMER_FRAMEAVG, TRUNK_9, SEQ_CONFORMER, HEAD_FC_AVG, STAGE_NONE, {3, 8, PAD_TO_100, CF_MAX_T}},
+    {SEDX_MODEL_GRU14_FRAMEATT, TRUNK_14, SEQ_GRU, HEAD_ATT, STAGE_NONE, {5, 32, PAD_TO_100, SEQ_ANY}},
+    {SEDX_MODEL_TRANSFORMER14_FRAMEATT, TRUNK_14, SEQ_MHA, HEAD_ATT, STAGE_NONE, {5, 32, PAD_TO_100, SEQ_ANY}},
+    {SEDX_MODEL_CNN14_DECISIONLEVELATT, TRUNK_14, SEQ_NONE, HEAD_ATT, STAGE_DECISION, {5, 32, PAD_TO_T_LESS_1, SEQ_ANY}},
+    {SEDX_MODEL_VGGISH_FRAMEATT, TRUNK_VGG, SEQ_NONE, HEAD_ATT, STAGE_NONE, {4, 12, PAD_TO_1000, 1000 / 12}},
+    {SEDX_MODEL_VGGISH_GRU_FRAMEATT, TRUNK_VGG, SEQ_GRU, HEAD_ATT, STAGE_NONE, {4, 12, PAD_TO_1000, 1000 / 12}},
+    {SEDX_MODEL_VGGISH_FRAMEAVG, TRUNK_VGG, SEQ_NONE, HEAD_FC_AVG, STAGE_NONE, {4, -1, PAD_TO_1000, 1000}},
+    {SEDX_MODEL_CONFORMER14_FRAMEATT, TRUNK_14, SEQ_CONFORMER, HEAD_ATT, STAGE_NONE, {5, -32, PAD_TO_100, 1000}},
+};
+static_assert(TRUNK_VGG == VGG_LAYERS, "Model::depth of the VGGish trunk");
+}  // namespace
 
 bool make_model(const sedx_config& cfg, Model* m) {
-  if (!model_parts(cfg.model_type, &m->seq, &m->head)) return false;
+  const ModelSpec* row = nullptr;
+  for (const ModelSpec& r : MODELS)
+    if (r.model_type == cfg.model_type) row = &r;   // the table's lookup
+  if (!row) return false;
   m->cfg = cfg;
-  m->decision = cfg.model_type == SEDX_MODEL_CNN14_DECISIONLEVELATT;
-  m->depth = cfg.model_type == SEDX_MODEL_GRU14_FRAMEATT || cfg.model_type == SEDX_MODEL_TRANSFORMER14_FRAMEATT ||
-                     cfg.model_type == SEDX_MODEL_CONFORMER14_FRAMEATT || m->decision
-                 ? 14
-                 : 9;
-  m->vgg = cfg.model_type == SEDX_MODEL_VGGISH_FRAMEATT || cfg.model_type == SEDX_MODEL_VGGISH_GRU_FRAMEATT ||
-           cfg.model_type == SEDX_MODEL_VGGISH_FRAMEAVG;
-  if (m->vgg) m->depth = VGG_LAYERS;
+  m->seq = row->seq, m->head = row->head, m->frames = row->frames;
+  m->depth = row->trunk;
+  m->vgg = row->trunk == TRUNK_VGG;
+  m->decision = row->stage == STAGE_DECISION;
   // the trunk's output feeds the sequence layer; the Conformer encoder narrows it to 144 for the head
-  m->sw = m->depth == 14 ? 2048 : 512;
+  m->sw = row->trunk == TRUNK_14 ? 2048 : 512;
   m->hw = m->seq == SEQ_CONFORMER ? CF_D : m->sw;
   m->nac = (((m->head == HEAD_ATT ? 2 : 1) * cfg.classes_num + 63) / 64) * 64;
+  // the heads that repeat by the frame rule have launchers of their own; the others repeat `rep` and pad
+  const bool att = m->head == HEAD_ATT;
+  m->head_launch = m->vgg ? (att ? HEAD_LAUNCH_VGG_ATT : HEAD_LAUNCH_VGG_FC)
+                   : row->frames.rep < 0 ? HEAD_LAUNCH_ATT_REP : att ? HEAD_LAUNCH_ATT : HEAD_LAUNCH_FC;
+  m->emb = m->decision ? EMB_NONE : att && m->seq != SEQ_MHA && m->seq != SEQ_CONFORMER ? EMB_CLA : EMB_HEAD_INPUT;
+  m->max_classes = m->decision ? DECISION_MAX_CLASSES : MAX_CLASSES;   // AudioSet's 527 for Cnn14_DecisionLevelAtt alone
   return true;
 }
 

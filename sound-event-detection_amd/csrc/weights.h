@@ -50,15 +50,38 @@ struct Tensor {
 };
 using Params = std::map<std::string, Tensor>;
 
-// what sedx_create derives from the config
+// How T input frames become output frames (geometry_from_T and shape_refusal, plan.cpp, read nothing else of
+// a model): `pools` flooring halvings give the sequence frames Ts; each is repeated `rep` times, or (rep < 0)
+// 1000 // Ts times, -rep where no forward runs; `pad` repeats the last frame; no forward runs Ts > max_seq.
+enum FramePad {
+  PAD_NONE,
+  PAD_TO_100,      // up to the next multiple of 100, unless the repeats give 1000 (pad_framewise_output, models.py:678-681)
+  PAD_TO_T_LESS_1, // to T - 1 frames: (T % 32) - 1 copies, so a multiple of 32 has no output (models.py:2738, :2778)
+  PAD_TO_1000      // always 1000 frames (models.py:2376, :2478, :2580-2582)
+};
+constexpr int SEQ_ANY = INT32_MAX;
+struct FrameRule {
+  int pools = 3, rep = 8, pad = PAD_NONE, max_seq = SEQ_ANY;
+};
+enum Trunk { TRUNK_9 = 9, TRUNK_14 = 14, TRUNK_VGG = 6 };   // the value: Model::depth
+// which launcher finishes the head projection's logits, and what d_embedding receives (api.cpp run_body)
+enum HeadLaunch { HEAD_LAUNCH_ATT, HEAD_LAUNCH_ATT_REP, HEAD_LAUNCH_FC, HEAD_LAUNCH_VGG_ATT, HEAD_LAUNCH_VGG_FC };
+enum EmbKind { EMB_NONE, EMB_CLA, EMB_HEAD_INPUT };   // nothing; cla [B][C][Ts] (models.py:683-686, :459); the head's input transposed
+
+// what sedx_create derives from the config: one row of the model table (weights.cpp), and what follows from it
 struct Model {
   sedx_config cfg{};
   int seq = SEQ_GRU;   // what follows the CNN trunk
   int head = HEAD_ATT; // the head that reads its output
+  FrameRule frames;
+  // ---- derived from the row ----
   int depth = 9;       // conv layers of the trunk: 9, or 14 (blocks 5-6 and five pools: T/32 sequence frames)
   int hw = 512;        // width of the head's input: 512, 144 after the Conformer encoder, 2048 on the 14-layer trunk
   int sw = 512;        // width of the sequence layer's input (the trunk's output): 512, or 2048 on the 14-layer trunk
   int nac = 64;        // rows of the head projection: att|cla (2C) or fc (C), rounded up to 64
+  int head_launch = HEAD_LAUNCH_ATT;
+  int emb = EMB_CLA;
+  int max_classes = 256;   // MAX_CLASSES, or DECISION_MAX_CLASSES
   // Cnn14_DecisionLevelAtt: between the trunk and the head, max + avg pooling over 3 sequence frames and
   // fc1 = Linear(2048, 2048) + ReLU (decision.hip); T - 1 framewise frames, no embedding output
   bool decision = false;
@@ -72,7 +95,7 @@ constexpr int VGG_LAYERS = 6;
 constexpr int VGG_SEQ_INDEX[VGG_LAYERS] = {0, 3, 6, 8, 11, 13};
 constexpr int VGG_CIN[VGG_LAYERS] = {1, 64, 128, 256, 256, 512};
 constexpr int VGG_COUT[VGG_LAYERS] = {64, 128, 256, 256, 512, 512};
-// cfg -> Model (seq, head, hw, nac); false for an unknown model_type
+// cfg -> Model: the model table's row and what follows from it; false for an unknown model_type
 bool make_model(const sedx_config& cfg, Model* m);
 // keys of modules the Conformer models build and never call at inference
 // (models.py:1290-1300, :1505-1515): accepted with any shape, not stored

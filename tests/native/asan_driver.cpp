@@ -23,8 +23,8 @@
 //  * the fp32 GEMM launch plan (plan_linear_launch): over the sequence and head
 //    GEMMs, row counts at every kernel switch and CU counts, the grid covering
 //    the output exactly in the chosen kernel's tiles.
-// Any memory error, undefined behaviour or failed check aborts the process
-// (non-zero exit).
+// Any memory error or undefined behaviour aborts the process; a failed check is
+// printed and counted (host_check.h): non-zero exit either way.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -35,8 +35,7 @@
 #include <vector>
 
 #include "../../include/sedx.h"
-#include "../../sound-event-detection_amd/csrc/plan.h"
-#include "../../sound-event-detection_amd/csrc/weights.h"
+#include "host_check.h"
 
 namespace {
 
@@ -107,15 +106,6 @@ int parse_all_prefixes(const std::vector<uint8_t>& img, int* ok) {
 }
 
 // ---- weight packing (csrc/weights.cpp) ---------------------------------------
-#define CHECK(cond, ...)                                    \
-  do {                                                      \
-    if (!(cond)) {                                          \
-      std::fprintf(stderr, "check failed: %s: ", #cond);    \
-      std::fprintf(stderr, __VA_ARGS__);                    \
-      std::fprintf(stderr, "\n");                           \
-      std::abort();                                         \
-    }                                                       \
-  } while (0)
 
 using namespace sedx;
 
@@ -382,22 +372,6 @@ std::vector<PtrWant> pointer_table(const Model& m, const DevWeights& W) {
 static_assert(sizeof(DevWeights) == sizeof(void*) * (39 + 5 * 8 + CF_BLOCKS * 29) + 14 * sizeof(int32_t),
               "pointer_table lists every DevWeights pointer");
 
-Model model_of(int model_type, int classes, int window, int feature) {
-  sedx_config cfg{};
-  cfg.model_type = model_type;
-  cfg.feature_type = feature;
-  cfg.sample_rate = 16000;
-  cfg.window_size = window;
-  cfg.hop_size = 160;
-  cfg.mel_bins = 64;
-  cfg.fmin = 50.f;
-  cfg.fmax = 7000.f;
-  cfg.classes_num = classes;
-  Model m;
-  CHECK(make_model(cfg, &m), "model %d", model_type);
-  return m;
-}
-
 // rows of the head projection against the state_dict: att row c at c, cla row
 // c at C + c (fc: row c at c), zeros after
 void check_head_rows(const Model& m, const Params& P, const float* wac, const float* bac) {
@@ -541,34 +515,73 @@ int check_weights() {
 }
 
 // ---- forward and window plans (csrc/plan.cpp) ---------------------------------
-struct Span {
-  const char* name;
-  size_t off, floats;   // float units
-};
-Span span(const char* name, const Region& r) { return Span{name, r.off, r.floats}; }
-// every span 256-byte aligned and inside [lo, hi) floats, no two overlapping
-void check_spans(const std::vector<Span>& v, size_t lo, size_t hi, const char* what) {
-  for (size_t i = 0; i < v.size(); ++i) {
-    CHECK(v[i].off * 4 % 256 == 0, "%s: %s at float %zu is not 256-byte aligned", what, v[i].name, v[i].off);
-    CHECK(v[i].off >= lo && v[i].off + v[i].floats <= hi, "%s: %s [%zu, +%zu) outside [%zu, %zu)", what, v[i].name,
-          v[i].off, v[i].floats, lo, hi);
-    for (size_t j = 0; j < i; ++j)
-      CHECK(v[i].off + v[i].floats <= v[j].off || v[j].off + v[j].floats <= v[i].off, "%s: %s overlaps %s", what,
-            v[i].name, v[j].name);
+// the conv launches after block 1's first, by trunk: the layer's T is T >> pools; its F, channels and epilogue
+struct LayerRow { int pools, F, cin, cout, epi; };
+const LayerRow ROWS9[7] = {{0, 64, 64, 64, EPI_POOL2},    {1, 32, 64, 128, EPI_STORE},  {1, 32, 128, 128, EPI_POOL2},
+                           {2, 16, 128, 256, EPI_STORE}, {2, 16, 256, 256, EPI_POOL2}, {3, 8, 256, 512, EPI_STORE},
+                           {3, 8, 512, 512, EPI_FMEAN}};
+const LayerRow ROWS14[11] = {{0, 64, 64, 64, EPI_POOL2},    {1, 32, 64, 128, EPI_STORE},   {1, 32, 128, 128, EPI_POOL2},
+                             {2, 16, 128, 256, EPI_STORE}, {2, 16, 256, 256, EPI_POOL2},  {3, 8, 256, 512, EPI_STORE},
+                             {3, 8, 512, 512, EPI_POOL2},  {4, 4, 512, 1024, EPI_STORE},  {4, 4, 1024, 1024, EPI_POOL2},
+                             {5, 2, 1024, 2048, EPI_STORE}, {5, 2, 2048, 2048, EPI_FMEAN}};
+const LayerRow ROWSVGG[5] = {{1, 32, 64, 128, EPI_MAXPOOL2},   {2, 16, 128, 256, EPI_STORE}, {2, 16, 256, 256, EPI_MAXPOOL2},
+                             {3, 8, 256, 512, EPI_STORE},     {3, 8, 512, 512, EPI_MAXPOOL2_FMEAN}};
+
+// one plan of any model against the launch contracts of sedx_internal.h: the extents below are what the kernels
+// write, restated here, not what plan.cpp reserved.  Top-level regions aligned, disjoint and inside the total; the
+// conv chain by the trunk's layer table, each launch reading what the previous one wrote, in the other buffer.
+// Returns plan_forward's reason.
+const char* check_plan_regions(const Model& m, const Tuning& t, int64_t B, int64_t T, ForwardPlan* plan) {
+  ForwardPlan& p = *plan;
+  const char* why = plan_forward(m, t, B, T, &p);
+  const bool deep = m.depth == 14;
+  const LayerRow* rows = m.vgg ? ROWSVGG : deep ? ROWS14 : ROWS9;
+  const int nlayers = m.vgg ? 5 : deep ? 11 : 7, pools = m.vgg ? 4 : deep ? 5 : 3;
+  const int64_t Ts = T >> pools;
+  CHECK(p.g.T == T && p.g.T1 == T / 2 && p.g.T2 == T / 4 && p.g.T3 == T / 8 && p.g.Ts == Ts && p.B == B && p.M == (int)(B * Ts),
+        "geometry of model %d at T %lld", m.cfg.model_type, (long long)T);
+  CHECK(p.nlayers == nlayers && p.first_deep == (m.vgg ? 5 : deep ? 6 : 7), "model %d: layer list", m.cfg.model_type);
+  const size_t total = p.total_bytes / 4, uB = (size_t)B;
+  CHECK(p.total_bytes % 256 == 0, "total");
+  check_spans({span("x0", p.x0), span("A", p.A), span("P", p.P), span("sched", p.sched)}, 0, total, "workspace");
+  CHECK(p.x0.floats >= uB * T * 64, "x0");                                   // launch_logmel / launch_features_bn0
+  CHECK(p.sched.floats >= 7 * 256, "sched");                                 // 7 launches x CONV_SCHED_INTS
+  for (int i = 0; i < nlayers; ++i) {
+    const ConvLayer& c = p.layers[i];
+    const LayerRow& r = rows[i];
+    const int64_t Tl = T >> r.pools;
+    CHECK(c.T == Tl && c.F == r.F && c.cin == r.cin && c.cout == r.cout && c.epi == r.epi, "model %d layer %d", m.cfg.model_type, i);
+    const Region& out = i % 2 ? p.A : p.P;
+    CHECK(c.out == out.off && c.in == (i % 2 ? p.P.off : i == 0 && p.block1 == B1_F23_FUSED ? p.x0.off : p.A.off),
+          "layer %d buffers", i);
+    const bool pool = r.epi == EPI_POOL2 || r.epi == EPI_MAXPOOL2, mean = r.epi == EPI_FMEAN || r.epi == EPI_MAXPOOL2_FMEAN;
+    const int64_t To = pool || r.epi == EPI_MAXPOOL2_FMEAN ? Tl / 2 : Tl, Fo = mean ? 1 : pool ? r.F / 2 : r.F;
+    CHECK(c.To == To && c.Fo == Fo, "layer %d output %d x %d", i, c.To, c.Fo);
+    const size_t ext = uB * To * Fo * r.cout;   // [B][To][Fo][Cout]; the frequency means: [B][To][Cout]
+    CHECK(ext <= out.floats, "layer %d writes %zu floats into %zu", i, ext, out.floats);
+    if (i > 0) {
+      const ConvLayer& q = p.layers[i - 1];
+      CHECK(c.in == q.out && c.T == q.To && c.F == q.Fo && c.cin == q.cout, "layer %d does not read layer %d", i, i - 1);
+      CHECK(uB * c.T * c.F * c.cin <= (i % 2 ? p.P : p.A).floats, "layer %d reads outside its buffer", i);
+    }
+    if (i >= p.first_deep) CHECK(c.cin % DEEP_CK == 0 && c.cout % DEEP_BN == 0, "deep layer %d", i);   // conv_deep.hip's tiles
   }
+  // the last launch writes the sequence input [B][Ts][sw] into P; the logits live in A
+  const ConvLayer& last = p.layers[nlayers - 1];
+  CHECK(last.To == Ts && last.Fo == 1 && last.cout == m.sw && last.out == p.P.off, "the sequence input is not P");
+  CHECK(inside(p.LG, p.A) && p.LG.floats >= uB * Ts * m.nac, "logits");
+  return why;
 }
 
-// one plan against the launch contracts of sedx_internal.h: the extents below
-// are what the kernels write, restated here, not what plan.cpp reserved
+// a 9-layer plan: the refusals, the kernel choices against literal tables and the head / encoder scratch
 void check_plan(const Model& m, const Tuning& t, int64_t B, int64_t T) {
   ForwardPlan p;
-  const char* why = plan_forward(m, t, B, T, &p);
-  const int64_t T1 = T / 2, T2 = T1 / 2, T3 = T2 / 2;
+  const char* why = check_plan_regions(m, t, B, T, &p);
+  const int64_t T3 = T / 8;
   const bool cf = m.seq == SEQ_CONFORMER;
   const char* want_why = T3 < 1 ? "input too short" : cf && T3 > 5000 ? "the Conformer encoder holds 5000" : B * T > INT32_MAX / 64 ? "batch too large" : nullptr;
   CHECK((why == nullptr) == (want_why == nullptr), "B %lld T %lld: %s", (long long)B, (long long)T, why ? why : "accepted");
-  if (why) CHECK(std::strstr(why, want_why) != nullptr, "B %lld T %lld: reason '%s'", (long long)B, (long long)T, why);
-  CHECK(p.g.T == T && p.g.T1 == T1 && p.g.T2 == T2 && p.g.T3 == T3 && p.B == B && p.M == (int)(B * T3), "geometry");
+  if (why && want_why) CHECK(std::strstr(why, want_why) != nullptr, "B %lld T %lld: reason '%s'", (long long)B, (long long)T, why);
   // the block-1 form, the layout flag and the family for (precision, SEDX_TUNE_WINO_BLOCK1, SEDX_TUNE_WINO_F43)
   static const Block1Form wino_form[3][3] = {{B1_PAD_EXACT, B1_PAD_EXACT, B1_PAD_EXACT},
                                             {B1_CONV1_F23, B1_CONV1_F23, B1_CONV1_F43},
@@ -581,31 +594,9 @@ void check_plan(const Model& m, const Tuning& t, int64_t B, int64_t T) {
   CHECK(p.block1 == form && p.c4 == (wino && wino_c4[t.wino_block1][t.wino_f43]) && p.family == family,
         "precision %d block1 %d f43 %d: form %d c4 %d family %d", t.precision, t.wino_block1, t.wino_f43, p.block1, p.c4, p.family);
   CHECK(p.claims == (x3 || (family == CONV_WINO43 && B >= 8)), "claims at B %lld", (long long)B);
-  // top level: disjoint, aligned, inside the byte count
-  const size_t total = p.total_bytes / 4;
-  CHECK(p.total_bytes % 256 == 0, "total");
-  check_spans({span("x0", p.x0), span("A", p.A), span("P", p.P), span("sched", p.sched)}, 0, total, "workspace");
-  // what the launches write
-  const size_t uB = (size_t)B, M = uB * T3, nac = (size_t)m.nac;
-  CHECK(p.x0.floats >= uB * T * 64, "x0");                                   // launch_logmel / launch_features_bn0
-  CHECK(p.sched.floats >= 7 * 256, "sched");                                 // 7 launches x CONV_SCHED_INTS
+  const size_t uB = (size_t)B, M = uB * T3;
   const size_t first = form == B1_F23_FUSED ? 0 : form == B1_PAD_EXACT || form == B1_PAD_X3 ? uB * (T + 2) * 66 : uB * T * 64 * 64;
   CHECK(first <= p.A.floats, "block 1's first launch: %zu floats into A of %zu", first, p.A.floats);
-  struct Row { int64_t T; int F, cin, cout, epi; };
-  const Row rows[7] = {{T, 64, 64, 64, EPI_POOL2},    {T1, 32, 64, 128, EPI_STORE},  {T1, 32, 128, 128, EPI_POOL2},
-                       {T2, 16, 128, 256, EPI_STORE}, {T2, 16, 256, 256, EPI_POOL2}, {T3, 8, 256, 512, EPI_STORE},
-                       {T3, 8, 512, 512, EPI_FMEAN}};
-  for (int i = 0; i < 7; ++i) {
-    const ConvLayer& c = p.layers[i];
-    const Row& r = rows[i];
-    CHECK(c.T == r.T && c.F == r.F && c.cin == r.cin && c.cout == r.cout && c.epi == r.epi, "layer %d", i);
-    const Region& out = i % 2 ? p.A : p.P;
-    CHECK(c.out == out.off && c.in == (i % 2 ? p.P.off : i == 0 && form == B1_F23_FUSED ? p.x0.off : p.A.off), "layer %d buffers", i);
-    const int64_t To = r.epi == EPI_POOL2 ? r.T / 2 : r.T, Fo = r.epi == EPI_POOL2 ? r.F / 2 : r.epi == EPI_FMEAN ? 1 : r.F;
-    CHECK(c.To == To && c.Fo == Fo, "layer %d output %d x %d", i, c.To, c.Fo);
-    const size_t ext = uB * To * Fo * r.cout;   // [B][To][Fo][Cout]; EPI_FMEAN: [B][T][Cout]
-    CHECK(ext <= out.floats, "layer %d writes %zu floats into %zu", i, ext, out.floats);
-  }
   // after the conv stack, inside A (P still holds the stage-8 output)
   const size_t a0 = p.A.off, a1 = p.A.off + p.A.floats;
   if (cf) {
@@ -620,7 +611,6 @@ void check_plan(const Model& m, const Tuning& t, int64_t B, int64_t T) {
     // gru.hip: the sync block rounded up to 256 B (10,056 -> 10,240), then 8 x 2 x 32 x 256 floats
     CHECK(p.gru.floats * 4 >= 10240 + (size_t)8 * 2 * 32 * 256 * 4, "recurrence scratch");
   }
-  CHECK(p.LG.floats >= M * nac, "logits");
   // launch_gru_coop's arguments
   static const int variant[8] = {2, -1, 0, 1, 3, 3, 4, 5};   // COOP, SIMPLE, TAG16, TAG8, COOP16, AUTO, KSPLIT, PAIR
   static const bool fast[4] = {true, false, false, true};    // AUTO, GLOBAL, SPREAD, LOCAL
@@ -672,7 +662,7 @@ bool check_window_plan(const Model& m, const Tuning& t, int driver, bool overlap
 
 int check_plans() {
   int n = 0;
-  for (int model_type = 0; model_type <= 8; ++model_type) {
+  for (int model_type : {0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 11, 13, 15, 16, 17, 19}) {   // every sedx_model_type
     const Model m = model_of(model_type, 25, 512, SEDX_FEATURE_LOGMEL);
     Tuning t;
     for (t.precision = 0; t.precision < 3; ++t.precision)
@@ -682,9 +672,24 @@ int check_plans() {
             for (int64_t B : {1, 7, 8, 32, 530})
               for (int64_t T : {8, 9, 34, 64, 734, 1001, 6131}) {
                 t.pipelined = pipe != 0;
-                check_plan(m, t, B, T), ++n;
+                ForwardPlan p;   // the other trunks: the generic checks; their drivers hold what is theirs alone
+                if (m.depth == 9) check_plan(m, t, B, T);
+                else check_plan_regions(m, t, B, T, &p);
+                ++n;
               }
   }
+  // every model at the shapes the family drivers plan: both sides of each trunk's and each frame rule's limits
+  const int64_t shapes[21][2] = {{1, 16},   {3, 17},    {2, 31},    {1, 32},    {1, 33},     {3, 63},     {33, 64},
+                                 {5, 66},   {3, 112},   {33, 161},  {3, 200},   {5, 501},    {32, 1001},  {1, 1001},
+                                 {3, 1343}, {1, 4127},  {2, 16015}, {2, 16032}, {1, 32000},  {1, 32031},  {1, 32032}};
+  for (int model_type : {0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 11, 13, 15, 16, 17, 19})
+    for (int precision = 0; precision < 3; ++precision)
+      for (const auto& sh : shapes) {
+        Tuning t;
+        t.precision = precision;
+        ForwardPlan p;
+        check_plan_regions(model_of(model_type), t, sh[0], sh[1], &p), ++n;
+      }
   const Model gru = model_of(SEDX_MODEL_GRU_FRAMEATT, 25, 512, SEDX_FEATURE_LOGMEL);
   for (int kernel = 0; kernel < 8; ++kernel)
     for (int handoff = 0; handoff < 4; ++handoff)
@@ -862,7 +867,7 @@ int main() {
   const int launch_checks = check_launch_plans();
   const int gemm_checks = check_gemm_plans();
   std::printf("asan_driver: %d wav_parse cases (%d accepted), %d vad cases, %d weight-pack checks, %d plan checks, "
-              "%d conv launch plans, %d GEMM launch plans: clean\n", cases, ok, vad_cases, weight_checks, plan_checks,
+              "%d conv launch plans, %d GEMM launch plans\n", cases, ok, vad_cases, weight_checks, plan_checks,
               launch_checks, gemm_checks);
-  return 0;
+  return host_check::finish("asan_driver");
 }

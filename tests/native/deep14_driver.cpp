@@ -1,47 +1,17 @@
 // Host side of the 14-layer models under AddressSanitizer + UBSan (make
-// asan-deep14): the forward plan (regions inside the workspace, disjoint where
-// they are live together), expected_params of both key sets and the deep conv
-// weight pack read back by a direct index computation.  No GPU, no preload.
+// asan-deep14): the geometry and the head regions of the forward plan (its
+// top-level regions and conv chain: asan_driver's check_plans, over every
+// model), expected_params of both key sets and the deep conv weight pack read
+// back by a direct index computation.  No GPU, no preload.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
 #include <vector>
 
-#include "../../sound-event-detection_amd/csrc/plan.h"
-#include "../../sound-event-detection_amd/csrc/weights.h"
+#include "host_check.h"
 
 using namespace sedx;
-
-static int failures = 0;
-#define CHECK(cond, ...)                      \
-  do {                                        \
-    if (!(cond)) {                            \
-      ++failures;                             \
-      std::printf("FAIL %s:%d: ", __FILE__, __LINE__); \
-      std::printf(__VA_ARGS__);               \
-      std::printf("\n");                      \
-    }                                         \
-  } while (0)
-
-static Model model_of(int type) {
-  sedx_config cfg{};
-  cfg.model_type = type;
-  cfg.feature_type = SEDX_FEATURE_LOGMEL;
-  cfg.sample_rate = 16000, cfg.window_size = 512, cfg.hop_size = 160, cfg.mel_bins = 64;
-  cfg.fmin = 25, cfg.fmax = 7000, cfg.classes_num = 25;
-  Model m;
-  if (!make_model(cfg, &m)) {
-    std::printf("FAIL make_model(%d)\n", type);
-    std::exit(1);
-  }
-  return m;
-}
-
-static bool disjoint(const Region& a, const Region& b) {
-  return a.floats == 0 || b.floats == 0 || a.off + a.floats <= b.off || b.off + b.floats <= a.off;
-}
-static bool inside(const Region& a, const Region& outer) { return a.off >= outer.off && a.off + a.floats <= outer.off + outer.floats; }
 
 static void check_params(int type, bool gru) {
   const Model m = model_of(type);
@@ -87,13 +57,6 @@ static void check_plan(int type, int precision, int64_t B, int64_t T) {
   const int64_t n = 32 * T5, padded = n == 1000 || n % 100 == 0 ? n : n + 100 - n % 100;
   CHECK(p.g.out_frames == padded, "out_frames %lld of T %lld", (long long)p.g.out_frames, (long long)T);
   if (why) return;
-  CHECK(p.nlayers == 11 && p.first_deep == 6 && p.M == B * T5, "layer list");
-  const Region all{0, p.total_bytes / 4};
-  const Region* top[4] = {&p.x0, &p.A, &p.P, &p.sched};
-  for (int i = 0; i < 4; ++i) {
-    CHECK(inside(*top[i], all), "region %d outside the workspace", i);
-    for (int j = i + 1; j < 4; ++j) CHECK(disjoint(*top[i], *top[j]), "regions %d and %d overlap", i, j);
-  }
   const Region* head[4] = {&p.G, &p.Hs, &p.O, &p.LG};
   for (int i = 0; i < 4; ++i) {
     CHECK(inside(*head[i], p.A), "head region %d outside A", i);
@@ -103,26 +66,6 @@ static void check_plan(int type, int precision, int64_t B, int64_t T) {
   CHECK(p.G.floats >= (size_t)p.M * (gru ? 6144 : 1536) && p.Hs.floats >= (size_t)p.M * 2048 &&
             p.O.floats >= (size_t)p.M * 512 && p.LG.floats >= (size_t)p.M * 64,
         "head region sizes");
-  // the conv chain: each launch reads what the previous one wrote, in the other buffer, inside it
-  static const int cin[11] = {64, 64, 128, 128, 256, 256, 512, 512, 1024, 1024, 2048};
-  static const int cout[11] = {64, 128, 128, 256, 256, 512, 512, 1024, 1024, 2048, 2048};
-  for (int i = 0; i < p.nlayers; ++i) {
-    const ConvLayer& c = p.layers[i];
-    CHECK(c.cin == cin[i] && c.cout == cout[i], "layer %d channels %d -> %d", i, c.cin, c.cout);
-    const Region& dst = i % 2 ? p.A : p.P;
-    const Region out{c.out, (size_t)B * c.To * c.Fo * c.cout};
-    CHECK(inside(out, dst), "layer %d output outside its buffer", i);
-    if (i > 0) {
-      const ConvLayer& q = p.layers[i - 1];
-      CHECK(c.in == q.out && c.T == q.To && c.F == q.Fo && c.cin == q.cout, "layer %d does not read layer %d", i, i - 1);
-    }
-    if (i >= 6) {
-      const int F = i == 6 ? 8 : i < 9 ? 4 : 2;
-      const int epi = i == 10 ? EPI_FMEAN : i % 2 == 0 ? EPI_POOL2 : EPI_STORE;
-      CHECK(c.F == F && c.epi == epi && c.cin % DEEP_CK == 0 && c.cout % DEEP_BN == 0, "deep layer %d", i);
-    }
-  }
-  CHECK(p.layers[10].To == T5 && p.layers[10].Fo == 1 && p.layers[10].out == p.P.off, "the sequence input is not P");
 }
 
 static void check_pack(int Cin, int Cout) {
@@ -163,10 +106,5 @@ int main() {
   check_pack(16, 128);
   check_pack(48, 256);
   check_pack(512, 1024);
-  if (failures) {
-    std::printf("deep14_driver: %d failures\n", failures);
-    return 1;
-  }
-  std::printf("deep14_driver: clean\n");
-  return 0;
+  return host_check::finish("deep14_driver");
 }

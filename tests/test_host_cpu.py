@@ -205,37 +205,83 @@ def _create_handle(L, model_type):
 def test_workspace_sizes_against_the_recorded_grid(golden_dir):
     """sedx_workspace_size, sedx_output_geometry and sedx_window_workspace_size
     (no GPU) over the grid tools/make_golden_workspace.py recorded from the
-    library before the forward plan: 9 models x 3 precisions x
+    library before the model table: 16 models x 3 precisions x
     SEDX_TUNE_WINO_BLOCK1 x SEDX_TUNE_WINO_F43 x 5 (clips, samples), and one
-    window spec per model.  The geometry is equal.  A size may not grow, and
-    may be smaller only by the hand-counted slack the plan's carve removed
-    (at most (4 * 64 + 64) * 4 = 1,280 B of head scratch or 8 * 64 * 4 =
-    2,048 B of Conformer scratch): it lies in [recorded - 4096, recorded]."""
+    window spec per model.  Sizes and geometry are equal; where a model refuses
+    a pair, both queries' statuses are."""
     import ctypes
     from sedx import _lib
     g = json.load(open(os.path.join(golden_dir, 'workspace_sizes.json')))
-    assert len(g['rows']) == 9 * 3 * 3 * 3 * 5 and len(g['window_bytes']) == 9
+    assert len(g['models']) == 16 and len(g['rows']) == 16 * 3 * 3 * 3 * 5 and len(g['window_bytes']) == 16
     L = _lib.lib()
     handles = {}
-    for mt, prec, b1, f43, B, n, want, frames, seq in g['rows']:
+    for mt, prec, b1, f43, B, n, *want in g['rows']:
         h = handles.get(mt) or handles.setdefault(mt, _create_handle(L, mt))
         assert L.sedx_set_precision(h, prec) == 0
         assert L.sedx_set_tuning(h, _lib.TUNE_WINO_BLOCK1, b1) == 0 and L.sedx_set_tuning(h, _lib.TUNE_WINO_F43, f43) == 0
         wsz, fr, sl = ctypes.c_size_t(), ctypes.c_int64(), ctypes.c_int64()
-        assert L.sedx_workspace_size(h, B, n, ctypes.byref(wsz)) == 0
-        assert L.sedx_output_geometry(h, n, ctypes.byref(fr), ctypes.byref(sl)) == 0
-        assert (fr.value, sl.value) == (frames, seq), (mt, n)
-        assert want - 4096 <= wsz.value <= want, (mt, prec, b1, f43, B, n, wsz.value, want)
+        st = [L.sedx_workspace_size(h, B, n, ctypes.byref(wsz)), L.sedx_output_geometry(h, n, ctypes.byref(fr), ctypes.byref(sl))]
+        got = [wsz.value, fr.value, sl.value] if st == [0, 0] else ['refused'] + st
+        assert got == want, (mt, prec, b1, f43, B, n, got, want)
+    assert sorted(handles) == g['models']
     w = g['window']
     spec = _lib.window_spec(w['sample_duration'], w['overlap_value'])
-    for mt, want in enumerate(g['window_bytes']):
+    for mt, want in zip(g['models'], g['window_bytes']):
         h = _create_handle(L, mt)                     # default tuning, as recorded
         wsz = ctypes.c_size_t()
         assert L.sedx_window_workspace_size(h, w['n_clips'], w['samples'], ctypes.byref(spec), ctypes.byref(wsz)) == 0
-        assert want - 4096 <= wsz.value <= want, (mt, wsz.value, want)
+        assert wsz.value == want, (mt, wsz.value, want)
         L.sedx_destroy(h)
     for h in handles.values():
         L.sedx_destroy(h)
+
+
+def test_model_shapes_against_the_recorded_answers(golden_dir):
+    """What every model type answers about shapes (no GPU), against what
+    tools/make_golden_model_shapes.py recorded from the library before the
+    model table: for every T of 1 .. 1400 and both sides of each large limit,
+    the status and (frames, seq) of sedx_output_geometry, the status of
+    sedx_workspace_size, the status and row count of sedx_gemm_launch_plan and
+    the sedx_last_error text of every refusal, all equal; the GEMM rows
+    themselves at two shapes in two precision modes, equal; and
+    sedx_window_geometry for four window specs: status and answers equal, the
+    message compared by the substrings other tests assert on it (the one
+    reason is now worded once: "window N: <the forward's reason>")."""
+    import importlib.util
+    from sedx import _lib
+    spec = importlib.util.spec_from_file_location('make_golden_model_shapes',
+                                                  os.path.join(REPO, 'tools', 'make_golden_model_shapes.py'))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    g = json.load(open(os.path.join(golden_dir, 'model_shapes.json')))
+    assert (g['t_range'], g['large'], g['gemm_points'], g['ncu']) == (tool.T_RANGE, [list(p) for p in tool.LARGE],
+                                                                    [list(p) for p in tool.GEMM_POINTS], tool.NCU)
+    assert g['windows'] == [list(w) for w in tool.WINDOWS] and sorted(map(int, g['models'])) == tool.MODELS
+    assert os.path.getsize(os.path.join(golden_dir, 'model_shapes.json')) < os.path.getsize(
+        os.path.join(golden_dir, 'vad_kat.json'))
+    L = _lib.lib()
+    pts = tool.points()
+    refusing_window = 0
+    for mt in tool.MODELS:
+        want = g['models'][str(mt)]
+        h = tool.create(L, mt)
+        cols = {name: tool.unrle(runs) for name, runs in want['columns'].items()}
+        assert all(len(c) == len(pts) for c in cols.values()) and sorted(cols) == sorted(tool.COLUMNS)
+        for i, (B, T) in enumerate(pts):
+            got = tool.point(L, h, B, T)
+            assert got == [cols[name][i] for name in tool.COLUMNS], (mt, B, T, got)
+        assert tool.gemm_section(L, h) == want['gemm'], mt
+        for w, rec in zip(tool.WINDOWS, want['windows']):
+            got = tool.window(L, h, *w)
+            assert got[0] == rec[0] and got[2:] == rec[2:], (mt, w, got, rec)
+            assert (got[1] == '') == (rec[1] == '')
+            for key in ('multiple of 32', 'x12', '1000', '5000', 'reflect padding'):
+                assert (key in got[1]) == (key in rec[1]), (mt, w, key, got[1], rec[1])
+            # too few frames for the trunk's pools: "too short", or the VGGish trunk's wording of it
+            assert ('too short' in rec[1]) == ('too short' in got[1] or 'pooling stages need 16' in got[1]), (mt, w, got[1])
+            refusing_window += rec[0] != 0
+        L.sedx_destroy(h)
+    assert refusing_window >= len(tool.MODELS)          # every model has a window spec it refuses
 
 
 def test_conv_launch_plan_against_the_recorded_launches(golden_dir):

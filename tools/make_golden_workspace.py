@@ -18,6 +18,7 @@ from sedx import _lib  # noqa: E402
 PAIRS = [(1, 1280), (1, 5280), (5, 5280), (3, 117280), (32, 160000)]   # (clips, samples)
 WINDOW = dict(sample_duration=5, overlap_value=1.0, n_clips=2, samples=160000)
 TUNE_WINO_BLOCK1, TUNE_WINO_F43 = 2, 7
+MODELS = [0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 11, 13, 15, 16, 17, 19]   # every sedx_model_type (include/sedx.h)
 
 
 def create(L, model_type):
@@ -28,11 +29,12 @@ def create(L, model_type):
 
 
 def sizes(L, h, B, samples):
-    """(workspace bytes, output frames, sequence frames) of B clips of ``samples`` samples."""
+    """[workspace bytes, output frames, sequence frames] of B clips of ``samples`` samples; where the model
+    refuses the pair, the two queries' statuses instead: ['refused', size status, geometry status]."""
     wsz, fr, sl = ctypes.c_size_t(), ctypes.c_int64(), ctypes.c_int64()
-    assert L.sedx_workspace_size(h, B, samples, ctypes.byref(wsz)) == 0
-    assert L.sedx_output_geometry(h, samples, ctypes.byref(fr), ctypes.byref(sl)) == 0
-    return wsz.value, fr.value, sl.value
+    st = [L.sedx_workspace_size(h, B, samples, ctypes.byref(wsz)),
+          L.sedx_output_geometry(h, samples, ctypes.byref(fr), ctypes.byref(sl))]
+    return [wsz.value, fr.value, sl.value] if st == [0, 0] else ['refused'] + st
 
 
 def window_size(L, h):
@@ -45,9 +47,9 @@ def window_size(L, h):
 
 def walk(L):
     """rows [model, precision, wino_block1, wino_f43, clips, samples, bytes, frames, seq] and
-    the window workspace bytes per model (default tuning)."""
+    the window workspace bytes per model of MODELS (default tuning)."""
     rows, windows = [], []
-    for model_type in range(9):
+    for model_type in MODELS:
         h = create(L, model_type)
         windows.append(window_size(L, h))
         for precision in range(3):
@@ -57,7 +59,7 @@ def walk(L):
                 for f43 in range(3):
                     assert L.sedx_set_tuning(h, TUNE_WINO_F43, f43) == 0
                     for B, n in PAIRS:
-                        rows.append([model_type, precision, b1, f43, B, n] + list(sizes(L, h, B, n)))
+                        rows.append([model_type, precision, b1, f43, B, n] + sizes(L, h, B, n))
         L.sedx_destroy(h)
     return rows, windows
 
@@ -68,7 +70,8 @@ if __name__ == '__main__':
     rows, windows = walk(_lib.lib())
     out = os.path.join(REPO, 'tests', 'golden', 'workspace_sizes.json')
     with open(out, 'w') as f:
-        f.write('{"window": %s,\n "window_bytes": %s,\n "rows": [\n  ' % (json.dumps(WINDOW), json.dumps(windows)))
+        f.write('{"models": %s,\n "window": %s,\n "window_bytes": %s,\n "rows": [\n  '
+                % (json.dumps(MODELS), json.dumps(WINDOW), json.dumps(windows)))
         f.write(',\n  '.join(json.dumps(r) for r in rows))
         f.write('\n ]}\n')
     print('%d rows, %d window sizes -> %s' % (len(rows), len(windows), out))
