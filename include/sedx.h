@@ -166,7 +166,46 @@ typedef enum {
    * T/32 (the same tensor as 32); 44 is the head's logits [M][64]: columns
    * 0..C-1 att, C..2C-1 cla, zeros beyond.  Timed stage 8 as the 14-layer
    * models, 9 the encoder, 10 the head. */
-  SEDX_MODEL_CONFORMER14_FRAMEATT = 19
+  SEDX_MODEL_CONFORMER14_FRAMEATT = 19,
+  /* 20 is not assigned (probed as the first unknown id after 19) */
+  /* Cnn_9layers_Conformer  :2019-2214, the DCASE-2020-style token model: the 9-layer
+   * trunk with all 8 frequency bins of block 4 kept (conv_block4 is not pooled
+   * and there is no frequency mean), every (frame, bin) pixel a 512-wide token
+   * in (t, f) order behind one learned tag token linear_emb(ones) (:2159-2164),
+   * the Conformer encoder of ids 7 and 8 on those tokens, and classifier =
+   * Linear(144, classes_num) on every token: token 0 is the clipwise output, the
+   * others the framewise output (:2177-2179).  Both outputs are LOGITS: no
+   * sigmoid, no frame repeat, no padding.  feature_type must be LOGMEL;
+   * classes_num is the classifier's width, 1..256.  The encoder and the
+   * classifier are fp32 in every precision mode.
+   *   geometry   T = L / hop + 1 frames; T3 = T / 8; seq_len = 8 T3 + 1 tokens;
+   *              out_frames = 8 T3 (10 s at hop 160 / 16 kHz: 1001 tokens, 1000
+   *              frames; 10400 samples: 64 frames; 7777: 48; 81760: 512)
+   *   refusals   T < 8 (the third pool has no output) and seq_len > 5000 (the
+   *              encoder's positional table): SEDX_EINVAL from the forwards,
+   *              sedx_output_geometry, sedx_workspace_size, the launch plans and
+   *              the windowed drivers, before any launch
+   *   keys       the 9-layer trunk's (frontend buffers, bn0, conv_block1-4),
+   *              encoder.* as ids 7 and 8, classifier.{weight [C][144], bias [C]}
+   *              and linear_emb.{weight [512][1], bias [512]}: all four are read
+   *              and a missing one is SEDX_EKEY; no att_block.*, no fc.*
+   *   outputs    d_framewise [B][8 T3][C] and d_clipwise [B][C]; the reference
+   *              returns no 'embedding': d_embedding is ignored and may be NULL
+   * Captures (sedx_set_capture): 0 and 2..7 as the 9-layer models; 8 is the token
+   * buffer [items][seq_len][512], tag row included; 20 and 21 + 4b + j as ids 7
+   * and 8, here [items][seq_len][144]; 9 is the encoder's output (the same tensor
+   * as 32); 44 is the classifier's logits [M][nac], M = items x seq_len, nac =
+   * classes_num rounded up to 64 (zeros beyond C): the outputs are its rows, bit
+   * for bit.  Timed stage 8 is block 4's conv2 plus the token kernel, 9 the
+   * encoder, 10 the classifier and the split. */
+  SEDX_MODEL_CONFORMER_TOKEN = 21,
+  /* Cnn_9layers_Gru_Reg  :2788-2889: Cnn_9layers_Gru_FrameAtt (id 0) without
+   * pad_framewise_output (:2880-2882): the same constructor, state_dict keys,
+   * AttBlock(512, 25), LOGMEL or GAMMA features, captures and timed stages;
+   * out_frames = 8 (T / 8), never padded to a multiple of 100; d_embedding = cla
+   * [B, C, seq_len].  Its framewise output is the first out_frames frames of id
+   * 0's, bit for bit, and so are the clipwise output and the embedding. */
+  SEDX_MODEL_GRU_REG = 22
 } sedx_model;
 
 typedef enum { SEDX_FEATURE_LOGMEL = 0, SEDX_FEATURE_GAMMA = 1 } sedx_feature;
@@ -192,7 +231,8 @@ typedef struct sedx_handle sedx_handle;
  * and the constructors of the other sedx_model values).  feature_type GAMMA is
  * Cnn_9layers_Gru_FrameAtt's alone (Cnn_9layers_Gru_FrameAvg takes the argument
  * and ignores it, :512-518); any other model_type with it is SEDX_EINVAL
- * (the 14-layer and the VGGish models included, SEDX_MODEL_CONFORMER14_FRAMEATT too).  classes_num: 1..256, and up to 527 for
+ * (the 14-layer and the VGGish models included, SEDX_MODEL_CONFORMER14_FRAMEATT and SEDX_MODEL_CONFORMER_TOKEN too;
+ * SEDX_MODEL_GRU_REG takes it as id 0 does).  classes_num: 1..256, and up to 527 for
  * SEDX_MODEL_CNN14_DECISIONLEVELATT. */
 sedx_status sedx_create(const sedx_config* cfg, int device, sedx_handle** out);
 void sedx_destroy(sedx_handle* h);
@@ -572,6 +612,18 @@ sedx_status sedx_set_precision(sedx_handle* h, int32_t mode);
  *                         rounding (both fp32 throughout; F(4,3)'s error vs a
  *                         float64 conv is ~6x the direct conv's, still ~1e-5
  *                         of the 1e-3 bar), so not bit-identical to each other.
+ *  SEDX_TUNE_CF_ATTN      (the four Conformer models) the encoder's relative
+ *                         attention core.  0: four lanes per query on the vector
+ *                         ALUs, exact two-pass softmax (cf_relattn_kernel,
+ *                         csrc/conformer.hip); 1: the fp32 matrix pipe
+ *                         (v_mfma_f32_16x16x4_f32), 64 queries x 64 keys per
+ *                         step, online softmax with rescaling
+ *                         (csrc/conformer_attn.hip); 2 (default): per model --
+ *                         ids 7, 8 and 19 run 0, so their output bits are those
+ *                         of every earlier release; id 21 runs 1 (7.6-8.0 ms
+ *                         against 1.56-1.57 ms for the three launches of a
+ *                         forward at 32 x 1001 tokens).  Both are fp32
+ *                         throughout and differ in summation order only.
  *
  * Co-residency: the cooperative GRU kernels need all workgroups of a
  * (32-clip group, direction) resident at once — 8 CUs (COOP) or 16 (COOP16)
@@ -587,7 +639,8 @@ typedef enum {
   SEDX_TUNE_GRU_SPIN = 4,
   SEDX_TUNE_WINO_ORDER = 5,
   SEDX_TUNE_GAMMA_SPEC = 6,
-  SEDX_TUNE_WINO_F43 = 7
+  SEDX_TUNE_WINO_F43 = 7,
+  SEDX_TUNE_CF_ATTN = 8
 } sedx_tuning_knob;
 enum {
   SEDX_GRU_KERNEL_COOP = 0,

@@ -185,7 +185,8 @@ sedx_status query_geometry(const sedx_handle* h, int64_t L_or_T, Geometry* g) {
   char buf[96];
   const char* why = shape_refusal(*h, g->T, buf, sizeof(buf));   // the queries reject what the forward rejects ...
   // ... but one: on the 9-layer trunk the size of an input too short for any forward is still reported (frames 0)
-  if (why && !(h->depth == 9 && g->Ts < 1)) return fail(h, SEDX_EINVAL, "%s", why);
+  // (Cnn_9layers_Conformer refuses it here as everywhere)
+  if (why && !(h->depth == 9 && g->Ts < 1 && !h->token)) return fail(h, SEDX_EINVAL, "%s", why);
   return SEDX_OK;
 }
 
@@ -350,7 +351,11 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
       launch_conv3x3_x3(in, iB, c.T, c.F, c.cin, c.cout, w.wx3[k], w.cb[k], out, c.epi, claim, s);
     else
       launch_conv3x3(in, iB, c.T, c.F, c.cin, c.cout, w.wp[k], w.cb[k], out, c.epi, w.zero, s);
-    if (p.c4 && c.epi != EPI_FMEAN)
+    if (h->token && i == 6) {
+      // Cnn_9layers_Conformer: the tag token, then block 4's pixels in (frame, bin) order (inside stage 8; capture 8)
+      launch_tokens(out, iB, c.To, p.c4, w.bfc, ws + p.Tok.off, s);   // bfc: the tag token (weights.h)
+      capture(h, 8, ws + p.Tok.off, (size_t)M * h->sw, s);
+    } else if (p.c4 && c.epi != EPI_FMEAN)
       capture_c4(h, 2 + i, out, B, c.To, c.Fo, c.cout, s);
     else
       capture(h, 2 + i, out, (size_t)B * c.To * c.Fo * c.cout, s);
@@ -361,7 +366,7 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
     h->conv_done_recorded = true;
   }
   const bool x3 = t.precision == SEDX_PRECISION_X3;
-  float* S = ws + p.P.off;                        // [B][T3][512] (14-layer: [B][T5][2048])
+  float* S = ws + (h->token ? p.Tok.off : p.P.off);   // [B][T3][512] (14-layer: [B][T5][2048]; tokens: [B][8 T3 + 1][512])
   float* G = ws + p.G.off;
   float* Hs = ws + p.Hs.off;
   float* O = ws + p.O.off;
@@ -419,7 +424,7 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
       // mhsa: x = x + o_net(attention(qkv_net(LN(x))))
       launch_cf_layernorm(X, M, c.att_g, c.att_be, Xn, s);
       cf_gemm(Xn, c.wqkv, nullptr, nullptr, Hb, CF_EPI_NONE);
-      launch_cf_relattn(Hb, iB, T3, RK + (size_t)b * T3 * CF_D, c.rwb, c.rrb, AV, s);
+      (p.attn_mx ? launch_cf_relattn_mx : launch_cf_relattn)(Hb, iB, T3, RK + (size_t)b * T3 * CF_D, c.rwb, c.rrb, AV, s);
       cf_gemm(AV, c.wo, nullptr, X, X, CF_EPI_RES);
       capture(h, 22 + 4 * b, X, nx, s);
       // conv module: x = conv(x) + x
@@ -466,6 +471,10 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
     case HEAD_LAUNCH_ATT_REP:   // x(1000 // seq_len), padded to 1000 or the next multiple of 100
       capture(h, 44, LG, (size_t)M * h->nac, s);
       launch_att_head_rep(LG, iB, T3, C, h->nac, frames, g.rep, d_fw, d_clip, s);
+      break;
+    case HEAD_LAUNCH_TOKEN:     // logits as they stand: token 0 clipwise, tokens 1.. framewise
+      capture(h, 44, LG, (size_t)M * h->nac, s);
+      launch_token_head(LG, iB, T3, C, h->nac, d_fw, d_clip, s);
       break;
     case HEAD_LAUNCH_ATT: launch_att_head(LG, iB, T3, C, h->nac, frames, d_fw, d_clip, emb_cla, s, g.rep); break;
     default: launch_fc_head(LG, iB, T3, C, h->nac, h->head == HEAD_FC_MAX, d_fw, d_clip, s, frames);
@@ -517,7 +526,8 @@ sedx_status sedx_set_capture(sedx_handle* h, int32_t stage, float* d_buf, size_t
   const bool cf_stage = h->seq == SEQ_CONFORMER && stage >= 20 && stage <= 20 + 4 * CF_BLOCKS;
   const bool deep_stage = h->depth == 14 && stage >= 40 && stage <= 43;   // blocks 5-6 of the 14-layer trunk
   const bool vgg_stage = h->vgg && stage >= 50 && stage <= 55;            // the VGGish trunk's launches
-  const bool lg_stage = h->head_launch == HEAD_LAUNCH_ATT_REP && stage == 44;   // Cnn_14layers_Conformer_FrameAtt's logits
+  // Cnn_14layers_Conformer_FrameAtt's and Cnn_9layers_Conformer's logits
+  const bool lg_stage = (h->head_launch == HEAD_LAUNCH_ATT_REP || h->head_launch == HEAD_LAUNCH_TOKEN) && stage == 44;
   if (h->vgg && stage >= 1 && stage <= 7) return fail(h, SEDX_EINVAL, "stage %d cannot be captured", (int)stage);
   if (stage == 1 || (stage > 9 && !cf_stage && !deep_stage && !vgg_stage && !lg_stage)) return fail(h, SEDX_EINVAL, "stage %d cannot be captured", (int)stage);
   h->cap_stage = stage;
@@ -538,7 +548,8 @@ sedx_status sedx_set_tuning(sedx_handle* h, int32_t knob, int32_t value) {
                {SEDX_TUNE_GRU_SPIN, 0, INT32_MAX, &Tuning::gru_spin},
                {SEDX_TUNE_WINO_ORDER, 0, 3, &Tuning::wino_order},
                {SEDX_TUNE_GAMMA_SPEC, 0, 1, &Tuning::gamma_spec},
-               {SEDX_TUNE_WINO_F43, 0, 2, &Tuning::wino_f43}};
+               {SEDX_TUNE_WINO_F43, 0, 2, &Tuning::wino_f43},
+               {SEDX_TUNE_CF_ATTN, 0, 2, &Tuning::cf_attn}};
   for (const auto& k : knobs) {
     if (k.knob != knob) continue;
     if (value < k.lo || value > k.hi) return fail(h, SEDX_EINVAL, "bad value %d for tuning knob %d", (int)value, (int)knob);
@@ -560,7 +571,8 @@ sedx_status sedx_create(const sedx_config* cfg, int device, sedx_handle** out) {
   if (cfg->window_size != 256 && cfg->window_size != 512 && cfg->window_size != 1024) return SEDX_EINVAL;
   if (cfg->hop_size <= 0 || cfg->sample_rate <= 0 || cfg->classes_num <= 0 || cfg->classes_num > DECISION_MAX_CLASSES)
     return SEDX_EINVAL;
-  if (cfg->feature_type == SEDX_FEATURE_GAMMA && cfg->model_type != SEDX_MODEL_GRU_FRAMEATT)
+  if (cfg->feature_type == SEDX_FEATURE_GAMMA && cfg->model_type != SEDX_MODEL_GRU_FRAMEATT &&
+      cfg->model_type != SEDX_MODEL_GRU_REG)   // the same forward before the head (models.py:2846-2850)
     return SEDX_EINVAL;
   Model m;   // after the range checks: nac is computed from classes_num
   if (!make_model(*cfg, &m) || cfg->classes_num > m.max_classes) return SEDX_EINVAL;

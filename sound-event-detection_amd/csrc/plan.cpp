@@ -22,6 +22,8 @@ Geometry geometry_from_T(const Model& m, int64_t T) {
   // a fixed repeat, or 1000 // seq_len; shapes no forward runs keep -rep
   g.rep = r.rep > 0 ? r.rep : g.Ts >= 1 && g.Ts <= r.max_seq ? (int)(1000 / g.Ts) : -r.rep;
   g.fw_len = g.rep * g.Ts;
+  // the tag token and every (frame, bin) pixel of block 4: one output frame per pixel token
+  if (r.tokens) g.Ts = g.T3 >= 1 ? r.tokens * g.T3 + 1 : 0, g.fw_len = r.tokens * g.T3;
   g.out_frames = g.fw_len;
   if (r.pad == PAD_TO_1000) g.out_frames = 1000;
   else if (r.pad == PAD_TO_100 && g.fw_len != 1000 && g.fw_len % 100 != 0) g.out_frames = g.fw_len + 100 - g.fw_len % 100;
@@ -90,6 +92,10 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
   // XCD cost that XCD a quarter of its CUs and the whole launch waits for it
   // (b1c2 0.61 vs 0.51 ms in the timed region, profiles/r05t_*)
   p->gru_spread = t.gru_handoff == SEDX_GRU_HANDOFF_SPREAD || (t.gru_handoff == SEDX_GRU_HANDOFF_AUTO && t.pipelined);
+  // SEDX_TUNE_CF_ATTN 2: cf_relattn_kernel on ids 7, 8 and 19 (they keep their output bits), the matrix-pipe
+  // kernel on Cnn_9layers_Conformer: at 32 x 1001 tokens its three launches take 1.56-1.57 ms against 7.58-7.97 ms
+  // ("Token model")
+  p->attn_mx = m.seq == SEQ_CONFORMER && (t.cf_attn == 1 || (t.cf_attn == 2 && m.token));
   // ---- where ----
   size_t end = 0;
   p->x0 = take(end, (size_t)B * T * 64);
@@ -123,9 +129,10 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
   }
   for (int i = 0; !m.vgg && i < (deep ? 6 : 7); ++i) {
     const int blk = (i + 1) / 2, cout = 64 << blk, Tl = (int)Ts[blk], F = 64 >> blk, pool = i % 2 == 0 && i < 6;
+    const bool fmean = i == 6 && !m.token;   // Cnn_9layers_Conformer keeps block 4's 8 bins (tokens.hip reads them)
     p->layers[i] = ConvLayer{Tl, F, i == 0 ? 64 : i % 2 ? cout / 2 : cout, cout,
-                             i == 6 ? EPI_FMEAN : pool ? EPI_POOL2 : EPI_STORE,
-                             pool ? Tl / 2 : Tl, i == 6 ? 1 : pool ? F / 2 : F, 0, 0,
+                             fmean ? EPI_FMEAN : pool ? EPI_POOL2 : EPI_STORE,
+                             pool ? Tl / 2 : Tl, fmean ? 1 : pool ? F / 2 : F, 0, 0,
                              i == 0 && p->block1 == B1_CONV1_F23 ? 0 : wino_order};
     size_t& ext = i % 2 ? a_conv : p_conv;
     ext = std::max(ext, (size_t)B * p->layers[i].To * p->layers[i].Fo * cout);
@@ -134,7 +141,8 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
   size_t e_head = a0;
   // (Cnn14_DecisionLevelAtt: H [M][2048] and the logits only)
   // (Cnn_14layers_Conformer_FrameAtt: none of G / H / O; the encoder's regions below)
-  const bool cf14 = deep && m.seq == SEQ_CONFORMER;
+  // (Cnn_9layers_Conformer: as the line above, at M = B (8 T3 + 1) rows)
+  const bool cf14 = (deep || m.token) && m.seq == SEQ_CONFORMER;
   p->G = take(e_head, m.decision || cf14 ? 0 : M * (deep && m.seq == SEQ_GRU ? 6144 : 1536));
   p->Hs = take(e_head, cf14 ? 0 : M * (deep ? 2048 : 512));
   p->O = take(e_head, m.decision || cf14 ? 0 : M * 512);
@@ -146,6 +154,8 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
     // block 6) wrote the sequence input into P, so on the 14-layer trunk these follow the deep stack's regions
     // in time and share none of P
     size_t e_cf = a0;
+    // Cnn_9layers_Conformer: the encoder's input [M][512], written by tokens.hip from block 4's pixels in P
+    p->Tok = take(e_cf, m.token ? M * m.sw : 0);
     p->X = take(e_cf, M * CF_D);
     p->Xn = take(e_cf, M * CF_D);
     p->Hb = take(e_cf, M * CF_FF);

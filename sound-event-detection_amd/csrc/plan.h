@@ -66,6 +66,7 @@ struct Tuning {
   int mel_mfma = 0;                          // SEDX_TUNE_MEL_MFMA (measured slower: opt-in)
   int gamma_spec = 0;                        // SEDX_TUNE_GAMMA_SPEC
   int gru_spin = 1 << 24;                    // SEDX_TUNE_GRU_SPIN: bound of every GRU hand-off spin (polls)
+  int cf_attn = 2;                           // SEDX_TUNE_CF_ATTN (2: per model, plan_forward)
   // sedx_set_pipelined: conv stacks of successive forwards run in issue order
   // (each waits for the previous one's conv-done event), whatever streams
   // they are issued on, so the sequence + head of batch i overlap the conv
@@ -143,6 +144,8 @@ struct ForwardPlan {
   // ... or the Conformer encoder's x [M][144], LayerNorm(x), the hidden [M][576],
   // the attention / depthwise output, r and r_k [3][Ts][144] (and LG)
   Region X, Xn, Hb, AV, Rr, RK;
+  Region Tok;                      // Cnn_9layers_Conformer: the token buffer [M][512] (capture 8), ahead of X
+  bool attn_mx = false;            // the encoder's attention: launch_cf_relattn_mx (SEDX_TUNE_CF_ATTN)
   GemmRow gemms[MAX_GEMM_ROWS] = {};   // the sequence layer's and the head's GEMM launches, in launch order
   int ngemms = 0;
   size_t total_bytes = 0;

@@ -409,9 +409,23 @@ void launch_cf_relpos(const float* inv_freq, int T, int nblk, float* r, hipStrea
 // rwb / rrb [4][36] -> O [B][T][144]
 void launch_cf_relattn(const float* QKV, int B, int T, const float* rk, const float* rwb, const float* rrb,
                        float* O, hipStream_t s);
+// the same contract on the fp32 matrix pipe (conformer_attn.hip; SEDX_TUNE_CF_ATTN 1): 1 <= T <= CF_MAX_T, the
+// softmax exact, a clip's result independent of B and of the clip's position; the file's header states the
+// summation order
+void launch_cf_relattn_mx(const float* QKV, int B, int T, const float* rk, const float* rwb, const float* rrb,
+                          float* O, hipStream_t s);
 // GLU + depthwise 7-tap conv over time + folded BN + Swish: Y [B][T][288],
 // wt [7][144] (BN scale folded in), bf [144] -> Z [B][T][144]
 void launch_cf_glu_dwconv(const float* Y, int B, int T, const float* wt, const float* bf, float* Z, hipStream_t s);
+
+// ---- Cnn_9layers_Conformer's tokens (tokens.hip) -----------------------------
+// The encoder's input S [B][8 T3 + 1][512]: row 0 of every clip = tag [512], row 1 + 8 t + f = pixel (t, f) of
+// block 4's conv2 output `in`: [B][128][T3][8][4] (c4: the chunk-of-4 layout) or [B][T3][8][512].  Copies only.
+void launch_tokens(const float* in, int B, int T3, bool c4, const float* tag, float* S, hipStream_t s);
+// The token head's finish: logits [B][Ts][ldl] -> clipwise [B][C] = row 0's columns 0..C-1, framewise
+// [B][Ts - 1][C] = rows 1..  Copies only: the outputs are the logits' bits.
+void launch_token_head(const float* logits, int B, int Ts, int C, int ldl, float* framewise, float* clipwise,
+                       hipStream_t s);
 
 // ---- windowed drivers (windows.cpp) ---------------------------------------
 // the loop and the merge plan: WindowLoop, MergePlan, window_loop, build_merge_plan (plan.h)

@@ -41,6 +41,9 @@ constexpr ModelSpec MODELS[] = {
     {SEDX_MODEL_VGGISH_GRU_FRAMEATT, TRUNK_VGG, SEQ_GRU, HEAD_ATT, STAGE_NONE, {4, 12, PAD_TO_1000, 1000 / 12}},
     {SEDX_MODEL_VGGISH_FRAMEAVG, TRUNK_VGG, SEQ_NONE, HEAD_FC_AVG, STAGE_NONE, {4, -1, PAD_TO_1000, 1000}},
     {SEDX_MODEL_CONFORMER14_FRAMEATT, TRUNK_14, SEQ_CONFORMER, HEAD_ATT, STAGE_NONE, {5, -32, PAD_TO_100, 1000}},
+    // a tag token + 8 T3 pixel tokens, one output frame per pixel token (:2159-2189); pe holds CF_MAX_T tokens
+    {SEDX_MODEL_CONFORMER_TOKEN, TRUNK_9, SEQ_CONFORMER, HEAD_TOKEN, STAGE_NONE, {3, 1, PAD_NONE, CF_MAX_T, 8}},
+    {SEDX_MODEL_GRU_REG, TRUNK_9, SEQ_GRU, HEAD_ATT, STAGE_NONE, {3, 8, PAD_NONE, SEQ_ANY}},   // id 0 without the pad (:2880-2882)
 };
 static_assert(TRUNK_VGG == VGG_LAYERS, "Model::depth of the VGGish trunk");
 }  // namespace
@@ -55,6 +58,7 @@ bool make_model(const sedx_config& cfg, Model* m) {
   m->depth = row->trunk;
   m->vgg = row->trunk == TRUNK_VGG;
   m->decision = row->stage == STAGE_DECISION;
+  m->token = row->head == HEAD_TOKEN;
   // the trunk's output feeds the sequence layer; the Conformer encoder narrows it to 144 for the head
   m->sw = row->trunk == TRUNK_14 ? 2048 : 512;
   m->hw = m->seq == SEQ_CONFORMER ? CF_D : m->sw;
@@ -62,8 +66,9 @@ bool make_model(const sedx_config& cfg, Model* m) {
   // the heads that repeat by the frame rule have launchers of their own; the others repeat `rep` and pad
   const bool att = m->head == HEAD_ATT;
   m->head_launch = m->vgg ? (att ? HEAD_LAUNCH_VGG_ATT : HEAD_LAUNCH_VGG_FC)
+                   : m->token ? HEAD_LAUNCH_TOKEN
                    : row->frames.rep < 0 ? HEAD_LAUNCH_ATT_REP : att ? HEAD_LAUNCH_ATT : HEAD_LAUNCH_FC;
-  m->emb = m->decision ? EMB_NONE : att && m->seq != SEQ_MHA && m->seq != SEQ_CONFORMER ? EMB_CLA : EMB_HEAD_INPUT;
+  m->emb = m->decision || m->token ? EMB_NONE : att && m->seq != SEQ_MHA && m->seq != SEQ_CONFORMER ? EMB_CLA : EMB_HEAD_INPUT;
   m->max_classes = m->decision ? DECISION_MAX_CLASSES : MAX_CLASSES;   // AudioSet's 527 for Cnn14_DecisionLevelAtt alone
   return true;
 }
@@ -71,7 +76,7 @@ bool make_model(const sedx_config& cfg, Model* m) {
 bool ignored_key(const Model& m, const std::string& k) {
   // every VGGish class builds nn.GRU(512, 256) (models.py:2318, :2521); only VGGish_Gru_FrameAtt calls it
   if (m.vgg && m.seq != SEQ_GRU) return k.compare(0, 4, "gru.") == 0;
-  if (m.seq != SEQ_CONFORMER) return false;
+  if (m.seq != SEQ_CONFORMER || m.token) return false;   // Cnn_9layers_Conformer reads all four
   return k == "classifier.weight" || k == "classifier.bias" || k == "linear_emb.weight" || k == "linear_emb.bias";
 }
 
@@ -174,6 +179,11 @@ std::map<std::string, std::vector<int64_t>> expected_params(const Model& m) {
     e["att_block.cla.weight"] = {C, m.hw, 1};
     e["att_block.cla.bias"] = {C};
     add_bn(e, "att_block.bn_att", C);   // unused in forward (models.py:161-169)
+  } else if (m.head == HEAD_TOKEN) {
+    e["classifier.weight"] = {C, m.hw};    // nn.Linear(144, classes_num) (models.py:2115)
+    e["classifier.bias"] = {C};
+    e["linear_emb.weight"] = {m.sw, 1};    // nn.Linear(1, 512) (:2123)
+    e["linear_emb.bias"] = {m.sw};
   } else {
     e["fc.weight"] = {C, m.hw};         // nn.Linear(512, classes_num) (models.py:247, :332, :503, :921; 144: :1500)
     e["fc.bias"] = {C};
@@ -442,14 +452,14 @@ void pack_conv_deep(const double* wf, int Cin, int Cout, float* out) {
 }
 
 // head projection [nac][hw] and its bias [nac], rows zero-padded to nac:
-// att | cla (row c, row C + c), or fc
+// att | cla (row c, row C + c), or fc, or (HEAD_TOKEN) classifier
 void pack_head(const Model& m, const Params& P, std::vector<float>* wac, std::vector<float>* bac) {
   const size_t C = m.cfg.classes_num, hw = m.hw;
   wac->assign((size_t)m.nac * hw, 0.f);
   bac->assign(m.nac, 0.f);
   if (m.head != HEAD_ATT) {
-    const auto& wf = P.at("fc.weight").data;
-    const auto& bf = P.at("fc.bias").data;
+    const auto& wf = P.at(m.head == HEAD_TOKEN ? "classifier.weight" : "fc.weight").data;
+    const auto& bf = P.at(m.head == HEAD_TOKEN ? "classifier.bias" : "fc.bias").data;
     std::copy(wf.begin(), wf.end(), wac->begin());
     std::copy(bf.begin(), bf.end(), bac->begin());
   } else {
@@ -462,6 +472,14 @@ void pack_head(const Model& m, const Params& P, std::vector<float>* wac, std::ve
     std::copy(ba.begin(), ba.end(), bac->begin());
     std::copy(bc.begin(), bc.end(), bac->begin() + C);
   }
+}
+
+std::vector<float> pack_tag_token(const Params& P) {
+  const auto& w = P.at("linear_emb.weight").data;   // [512][1]
+  const auto& b = P.at("linear_emb.bias").data;
+  std::vector<float> tag(b.size());
+  for (size_t c = 0; c < tag.size(); ++c) tag[c] = w[c] + b[c];
+  return tag;
 }
 
 // ---- everything ---------------------------------------------------------------
@@ -680,6 +698,10 @@ sedx_status prepare_weights(const Model& m, const Params& P, DevWeights* Wp, Wei
   pack_head(m, P, &wac, &bac);
   blob->add(&W.wac, wac.data(), wac.size());
   blob->add(&W.bac, bac.data(), bac.size());
+  if (m.token) {
+    const std::vector<float> tag = pack_tag_token(P);
+    blob->add(&W.bfc, tag.data(), tag.size());   // the MultiHead fc bias's slot (weights.h)
+  }
 
   // ---- x3 packs of the linear layers ----
   auto add_x3 = [&](void** dst, const float* w, int N, int BN) {

@@ -42,7 +42,8 @@ constexpr size_t deep_b_off(int l) { return l == 0 ? 0 : deep_b_off(l - 1) + DEE
 // ---- the model ------------------------------------------------------------
 // a model = the CNN trunk, then a sequence layer, then a head
 enum SeqKind { SEQ_NONE = 0, SEQ_GRU = 1, SEQ_MHA = 2, SEQ_CONFORMER = 3 };
-enum HeadKind { HEAD_ATT = 0, HEAD_FC_AVG = 1, HEAD_FC_MAX = 2 };
+// HEAD_TOKEN: Cnn_9layers_Conformer's classifier = Linear(144, C) on every token; no sigmoid (models.py:2177-2179)
+enum HeadKind { HEAD_ATT = 0, HEAD_FC_AVG = 1, HEAD_FC_MAX = 2, HEAD_TOKEN = 3 };
 
 struct Tensor {
   std::vector<int64_t> shape;
@@ -53,6 +54,9 @@ using Params = std::map<std::string, Tensor>;
 // How T input frames become output frames (geometry_from_T and shape_refusal, plan.cpp, read nothing else of
 // a model): `pools` flooring halvings give the sequence frames Ts; each is repeated `rep` times, or (rep < 0)
 // 1000 // Ts times, -rep where no forward runs; `pad` repeats the last frame; no forward runs Ts > max_seq.
+// `tokens` > 0 (Cnn_9layers_Conformer, models.py:2159-2164): the sequence is a learned tag token, then every
+// (pooled frame, frequency bin) pixel of the trunk's `tokens` bins: Ts = tokens * T3 + 1, and the framewise
+// output is one frame per pixel token, tokens * T3 of them, no repeat and no pad.
 enum FramePad {
   PAD_NONE,
   PAD_TO_100,      // up to the next multiple of 100, unless the repeats give 1000 (pad_framewise_output, models.py:678-681)
@@ -61,11 +65,11 @@ enum FramePad {
 };
 constexpr int SEQ_ANY = INT32_MAX;
 struct FrameRule {
-  int pools = 3, rep = 8, pad = PAD_NONE, max_seq = SEQ_ANY;
+  int pools = 3, rep = 8, pad = PAD_NONE, max_seq = SEQ_ANY, tokens = 0;
 };
 enum Trunk { TRUNK_9 = 9, TRUNK_14 = 14, TRUNK_VGG = 6 };   // the value: Model::depth
 // which launcher finishes the head projection's logits, and what d_embedding receives (api.cpp run_body)
-enum HeadLaunch { HEAD_LAUNCH_ATT, HEAD_LAUNCH_ATT_REP, HEAD_LAUNCH_FC, HEAD_LAUNCH_VGG_ATT, HEAD_LAUNCH_VGG_FC };
+enum HeadLaunch { HEAD_LAUNCH_ATT, HEAD_LAUNCH_ATT_REP, HEAD_LAUNCH_FC, HEAD_LAUNCH_VGG_ATT, HEAD_LAUNCH_VGG_FC, HEAD_LAUNCH_TOKEN };
 enum EmbKind { EMB_NONE, EMB_CLA, EMB_HEAD_INPUT };   // nothing; cla [B][C][Ts] (models.py:683-686, :459); the head's input transposed
 
 // what sedx_create derives from the config: one row of the model table (weights.cpp), and what follows from it
@@ -89,6 +93,9 @@ struct Model {
   // with bias and ReLU, no BatchNorm (bn0 is never applied either), max pools after convs 1, 2, 4 and 6
   // (conv_vgg.hip, conv.hip's max-pool epilogues); T / 16 sequence frames, always 1000 output frames
   bool vgg = false;
+  // Cnn_9layers_Conformer (models.py:2019-2189): block 4's conv2 keeps its 8 frequency bins, tokens.hip turns
+  // them into the encoder's input (frames.tokens), the head is HEAD_TOKEN; no embedding output
+  bool token = false;
 };
 // the VGGish trunk: vggish.0.<VGG_SEQ_INDEX[l]>.{weight, bias} is conv l (nn.Sequential indices of VGGish.features)
 constexpr int VGG_LAYERS = 6;
@@ -98,7 +105,8 @@ constexpr int VGG_COUT[VGG_LAYERS] = {64, 128, 256, 256, 512, 512};
 // cfg -> Model: the model table's row and what follows from it; false for an unknown model_type
 bool make_model(const sedx_config& cfg, Model* m);
 // keys of modules the Conformer models build and never call at inference
-// (models.py:1290-1300, :1505-1515): accepted with any shape, not stored
+// (models.py:1290-1300, :1505-1515): accepted with any shape, not stored.  Cnn_9layers_Conformer calls both
+// (classifier, linear_emb): there they are expected_params' keys and none is ignored
 bool ignored_key(const Model& m, const std::string& k);
 // whether an ignored key may have `shape`: Cnn_14layers_Conformer_FrameAtt takes its ignored keys (models.py:1727,
 // :1735) at the reference's shapes only; the 9-layer Conformer and the VGGish models take theirs at any shape
@@ -171,7 +179,8 @@ struct DevWeights {
   float* wqkv = nullptr;   // [1536][512]; 14-layer: [1536][2048]
   float* bqkv = nullptr;
   float* wfc = nullptr;    // [512][512]; 14-layer: [2048][512]; Cnn14_DecisionLevelAtt (no MultiHead): fc1.weight
-  float* bfc = nullptr;    //   as it stands [2048][2048] and fc1.bias [2048]
+  float* bfc = nullptr;    //   as it stands [2048][2048] and fc1.bias [2048]; Cnn_9layers_Conformer (no MultiHead either):
+                           //   bfc = the tag token [512], fl(linear_emb.weight[c][0] + linear_emb.bias[c]) (pack_tag_token)
   float* wac = nullptr;    // [nac][hw]
   float* bac = nullptr;
   // Conformer encoder (fp32 in every mode)
@@ -232,6 +241,8 @@ inline size_t deep_pack_index(int Cin, int o, int i, int tap) {
 std::vector<uint16_t> pack_x3(const float* w, int N, int K, int taps, int BN);
 
 void pack_head(const Model& m, const Params& P, std::vector<float>* wac, std::vector<float>* bac);   // [nac][hw], [nac]
+// Cnn_9layers_Conformer's tag token [512]: linear_emb on a tensor of ones, w[c][0] * 1 + b[c] in fp32 (one rounding)
+std::vector<float> pack_tag_token(const Params& P);
 
 // gammatone tables (gamma_weights.cpp); gamma_kp: bins nfft / 2 + 1 padded to a multiple of 32
 inline int gamma_kp(int nfft) { return ((nfft / 2 + 1) + 31) / 32 * 32; }

@@ -31,6 +31,7 @@ EXPORTS = ['sedx_create', 'sedx_destroy', 'sedx_last_error', 'sedx_version', 'se
 TUNE_GRU_KERNEL, TUNE_GRU_HANDOFF, TUNE_WINO_BLOCK1, TUNE_MEL_MFMA, TUNE_GRU_SPIN, TUNE_WINO_ORDER = 0, 1, 2, 3, 4, 5
 TUNE_GAMMA_SPEC = 6
 TUNE_WINO_F43 = 7
+TUNE_CF_ATTN = 8   # 0: four lanes per query, 1: the fp32 matrix pipe, 2 (default): per model (1 on Cnn_9layers_Conformer, 0 elsewhere)
 PRECISION = {'exact': 0, 'x3': 1, 'winograd': 2}
 STAGES = ['frontend', 'b1c1', 'b1c2', 'b2c1', 'b2c2', 'b3c1', 'b3c2', 'b4c1', 'b4c2', 'seq', 'head', 'pipeline_wait']
 

@@ -18,7 +18,11 @@ mask=None)``), and the two models on the 14-layer trunk
 (``Cnn_14layers_Gru_FrameAtt``, ``Cnn_14layers_Transformer_FrameAtt``: eight
 constructor arguments, 25 classes; ``Cnn_14layers_Conformer_FrameAtt``: the
 Conformer constructor after ``feature_type``, 25 classes, 144-wide embedding,
-every sequence frame repeated ``1000 // seq_len`` times), and ``Cnn14_DecisionLevelAtt`` (the PANNs
+every sequence frame repeated ``1000 // seq_len`` times; ``Cnn_9layers_Conformer``: the Conformer
+constructor, every (frame, frequency bin) pixel of block 4 a token behind a learned tag token,
+``forward(x, mixup_lambda=None, timeshift=False, mask=None)`` returning LOGITS under the reference's
+two keys; ``Cnn_9layers_Gru_Reg``: ``Cnn_9layers_Gru_FrameAtt`` without the framewise padding, 25
+classes), and ``Cnn14_DecisionLevelAtt`` (the PANNs
 architecture: seven constructor arguments, up to 527 classes,
 ``forward(input, mixup_lambda=None)`` returning the reference's two keys, no
 ``'embedding'``), and the three transfer-learning models on the VGGish trunk
@@ -51,7 +55,7 @@ from .stft import Spectrogram, LogmelFilterBank
 
 __all__ = ['Cnn_9layers_Gru_FrameAtt', 'Cnn_9layers_Transformer_FrameAtt',
            'Cnn_14layers_Gru_FrameAtt', 'Cnn_14layers_Transformer_FrameAtt', 'Cnn14_DecisionLevelAtt',
-           'Cnn_14layers_Conformer_FrameAtt',
+           'Cnn_14layers_Conformer_FrameAtt', 'Cnn_9layers_Conformer', 'Cnn_9layers_Gru_Reg',
            'VGGish', 'VGGish_FrameAtt', 'VGGish_Gru_FrameAtt', 'VGGish_FrameAvg',
            'Cnn_9layers_FrameMax', 'Cnn_9layers_FrameAvg', 'Cnn_9layers_FrameAtt',
            'Cnn_9layers_Gru_FrameAvg', 'Cnn_9layers_Transformer_FrameAvg',
@@ -67,7 +71,8 @@ MODEL_IDS = {'Cnn_9layers_Gru_FrameAtt': 0, 'Cnn_9layers_Transformer_FrameAtt': 
              'Cnn_14layers_Gru_FrameAtt': 10, 'Cnn_14layers_Transformer_FrameAtt': 11,   # 9 is not assigned
              'Cnn14_DecisionLevelAtt': 13,                                              # nor is 12
              'VGGish_FrameAtt': 15, 'VGGish_Gru_FrameAtt': 16, 'VGGish_FrameAvg': 17,   # nor is 14
-             'Cnn_14layers_Conformer_FrameAtt': 19}                                     # nor is 18
+             'Cnn_14layers_Conformer_FrameAtt': 19,                                     # nor is 18
+             'Cnn_9layers_Conformer': 21, 'Cnn_9layers_Gru_Reg': 22}                    # nor is 20
 FEATURE_IDS = {'logmel': 0, 'gamma': 1}
 
 
@@ -632,6 +637,29 @@ class Cnn_9layers_Gru_FrameAtt(_SedModel):
         init_gru(self.gru)
 
 
+class Cnn_9layers_Gru_Reg(_SedModel):
+    """pytorch/models.py:2788-2889: ``Cnn_9layers_Gru_FrameAtt`` with
+    ``AttBlock(512, 25)`` -- 25 classes whatever ``classes_num`` is (:2827) --
+    and without ``pad_framewise_output`` (:2882): the framewise output is the
+    ``8 * (T // 8)`` interpolated frames (7777 samples: 48, where
+    ``Cnn_9layers_Gru_FrameAtt`` pads to 100).  ``forward(input,
+    mixup_lambda=None, timeshift=False)``; embedding = cla (batch, 25, seq)."""
+    _model_name = 'Cnn_9layers_Gru_Reg'
+    _embedding_cla = True
+
+    def __init__(self, sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num,
+                 feature_type):
+        super().__init__(sample_rate, window_size, hop_size, mel_bins, fmin, fmax, 25, feature_type)
+        self.gru = nn.GRU(input_size=512, hidden_size=256, num_layers=1, bias=True,
+                          batch_first=True, bidirectional=True)
+        self.att_block = AttBlock(n_in=512, n_out=25, activation='sigmoid')
+        init_bn(self.bn0)
+        init_gru(self.gru)
+
+    def forward(self, input, mixup_lambda=None, timeshift=False):
+        return super().forward(input, mixup_lambda=mixup_lambda, timeshift=timeshift)
+
+
 class Cnn_9layers_Transformer_FrameAtt(_SedModel):
     """pytorch/models.py:981-1077 (always logmel: the reference has no
     feature-type branch)."""
@@ -762,8 +790,10 @@ class _ConformerModel(_SedModel):
             self.conv_block6 = ConvBlock(1024, 2048)
         self.encoder = ConformerEncoder(self._trunk_width, **self.encoder_kwargs)
         self._build_head(classes_num)
-        self.classifier = nn.Linear(144, classes_num)      # unused in forward (models.py:1290, :1505, :1727)
-        self.linear_emb = nn.Linear(1, self._trunk_width)  # unused in forward (pooling == "token")
+        # unused in the forward of the FrameAtt / FrameAvg classes (models.py:1290, :1505, :1727); the head and
+        # the tag token of Cnn_9layers_Conformer (:2115, :2123)
+        self.classifier = nn.Linear(144, classes_num)
+        self.linear_emb = nn.Linear(1, self._trunk_width)
 
     def forward(self, x, mixup_lambda=None, timeshift=False, spec_augment=True, mask=None):
         if mask is not None:
@@ -791,6 +821,44 @@ class Cnn_9layers_Conformer_FrameAvg(_ConformerModel):
 
     def _build_head(self, classes_num):
         self.fc = nn.Linear(144, classes_num, bias=True)
+
+
+class Cnn_9layers_Conformer(_ConformerModel):
+    """pytorch/models.py:2019-2214, the DCASE-2020-style token model.  Block 4 is
+    not pooled and its 8 frequency bins are kept: every (frame, bin) pixel is a
+    512-wide token, in (t, f) order, behind the tag token ``linear_emb(ones)``;
+    the Conformer encoder runs on those ``8 * (T // 8) + 1`` tokens (1001 for a
+    10 s clip) and ``classifier = Linear(144, classes_num)`` reads both outputs off
+    them: ``clipwise_output`` (batch, classes) is token 0, ``framewise_output``
+    (batch, 8 * (T // 8), classes) the others.  Both are LOGITS (no sigmoid, no
+    interpolation, no padding) and there is no ``'embedding'``, as in the
+    reference.  ``cnn_kwargs`` and ``encoder_kwargs`` are accepted and ignored
+    (the reference overwrites both).  ``forward(x, mixup_lambda=None,
+    timeshift=False, mask=None)``: no ``spec_augment`` argument, ``mask`` must be
+    ``None``.  Fewer than 8 input frames and more than 5000 tokens raise.  The
+    encoder and the classifier run fp32 in every precision mode."""
+    _model_name = 'Cnn_9layers_Conformer'
+    _has_embedding = False
+
+    def __init__(self, sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num,
+                 cnn_kwargs=None, encoder_kwargs=None, encoder_type='Conformer', pooling='token',
+                 layer_init='pytorch'):
+        if encoder_type != 'Conformer':
+            raise ValueError('encoder_type=%r: only encoder_type="Conformer" is implemented natively' % (encoder_type,))
+        if pooling != 'token':
+            raise ValueError('pooling=%r: only pooling="token" (the tag token and the token head) is implemented '
+                             'natively' % (pooling,))
+        if str(layer_init).lower() != 'pytorch':
+            raise ValueError('layer_init=%r: only layer_init="pytorch" is supported; load a state_dict instead '
+                             '(inference-only model)' % (layer_init,))
+        super().__init__(sample_rate, window_size, hop_size, mel_bins, fmin, fmax, classes_num,
+                         cnn_kwargs=cnn_kwargs, encoder_kwargs=encoder_kwargs)
+
+    def _build_head(self, classes_num):
+        pass   # classifier, built by the base class at the constructor's class count
+
+    def forward(self, x, mixup_lambda=None, timeshift=False, mask=None):
+        return super().forward(x, mixup_lambda=mixup_lambda, timeshift=timeshift, mask=mask)
 
 
 class Cnn_14layers_Conformer_FrameAtt(_ConformerModel):

@@ -52,6 +52,8 @@ MODEL_PARTS = {
     'Cnn_14layers_Transformer_FrameAtt': ('mha', 'att'),
     'Cnn14_DecisionLevelAtt': ('fc1', 'att'),
     'Cnn_14layers_Conformer_FrameAtt': ('conformer', 'att'),
+    'Cnn_9layers_Conformer': ('conformer', 'token'),
+    'Cnn_9layers_Gru_Reg': ('gru', 'att'),
 }
 # the weight seed of every model's golden fixtures (tests/golden/)
 GOLDEN_SEEDS = {
@@ -104,6 +106,16 @@ VGGISH_GOLDEN_SEEDS = {
 # with seed 27 the first waveform clears 1.9e-4 (seeds 30, 31, 32, 35 and 37 clear 1e-4 too)
 CONFORMER14_GOLDEN_SEEDS = {
     'Cnn_14layers_Conformer_FrameAtt': 27,
+}
+# Cnn_9layers_Conformer's and Cnn_9layers_Gru_Reg's (tests/golden/token_*): ``pytorch/models.py:2019-2214``,
+# ``:2788-2889``.  tools/make_golden_token.py walks the waveform seed until the reference's windowed output keeps
+# every event-deciding value at least 1e-4 from its threshold, and records seed and margin in token_meta.json.
+# The margin is a property of the weight seed here too: with seed 42 Cnn_9layers_Gru_Reg stayed within 3e-5 of a
+# threshold on each of 280 waveforms, with seed 47 the first waveform clears 1.3e-4.  Cnn_9layers_Conformer's
+# outputs are logits spread around the thresholds: no waveform of 160 cleared 2e-5, the tool keeps the best
+TOKEN_GOLDEN_SEEDS = {
+    'Cnn_9layers_Conformer': 41,
+    'Cnn_9layers_Gru_Reg': 47,
 }
 VGGISH_HEADS = {'VGGish_FrameAtt': 'att', 'VGGish_Gru_FrameAtt': 'att', 'VGGish_FrameAvg': 'fc'}
 # VGGish.features' convs: nn.Sequential index, (cin, cout) (models.py:2230-2250)
@@ -196,7 +208,7 @@ def _vggish_state_dict(model_type, seed):
 
 def make_state_dict(model_type, classes_num=25, seed=0):
     """Return {key: np.ndarray} for the non-frontend parameters of one of the
-    nine 9-layer models, the three 14-layer ones or ``Cnn14_DecisionLevelAtt`` (``MODEL_PARTS``).  Draw order: the trunk, the
+    eleven 9-layer models, the three 14-layer ones or ``Cnn14_DecisionLevelAtt`` (``MODEL_PARTS``).  Draw order: the trunk, the
     sequence layer's tensors, the head's (so two models with one seed share
     every tensor up to the first that differs).  ``Cnn_9layers_FrameAtt``'s
     AttBlock has 25 classes whatever ``classes_num`` is (models.py:416), and so
@@ -215,7 +227,8 @@ def make_state_dict(model_type, classes_num=25, seed=0):
     fixed25 = model_type in DEEP14_GOLDEN_SEEDS or model_type in CONFORMER14_GOLDEN_SEEDS
     # the 14-layer trunk; Cnn14_DecisionLevelAtt's AttBlock has the caller's class count (:2723)
     deep = fixed25 or model_type in CNN14_GOLDEN_SEEDS
-    if model_type in ('Cnn_9layers_FrameAtt', 'Cnn_9layers_Conformer_FrameAtt') or fixed25:
+    # Cnn_9layers_Gru_Reg: AttBlock(512, 25) (:2827)
+    if model_type in ('Cnn_9layers_FrameAtt', 'Cnn_9layers_Conformer_FrameAtt', 'Cnn_9layers_Gru_Reg') or fixed25:
         classes_num = 25
     trunk = 2048 if deep else 512                 # the trunk's output: the sequence layer's input
     width = CONFORMER_DIM if seq == 'conformer' else trunk
@@ -263,6 +276,8 @@ def make_state_dict(model_type, classes_num=25, seed=0):
         # (models.py:247, :253); a negative bias like cla's below
         sd['fc.weight'] = _xavier_uniform(rng, (classes_num, width), width, classes_num)
         sd['fc.bias'] = rng.uniform(-0.5, 0.0, classes_num).astype(np.float32)
+    elif head == 'token':
+        pass   # Cnn_9layers_Conformer: classifier and linear_emb below are its head and its tag token (:2115, :2123)
     else:
         sd['att_block.att.weight'] = _xavier_uniform(rng, (classes_num, width, 1), width, classes_num)
         sd['att_block.att.bias'] = rng.uniform(-0.1, 0.1, classes_num).astype(np.float32)
@@ -270,7 +285,8 @@ def make_state_dict(model_type, classes_num=25, seed=0):
         sd['att_block.cla.bias'] = rng.uniform(-0.5, 0.0, classes_num).astype(np.float32)
         sd.update(_bn(rng, 'att_block.bn_att', classes_num))
     if seq == 'conformer':
-        # built and never called at inference (models.py:1290-1300, :1505-1515, :1727-1735)
+        # built and never called at inference (models.py:1290-1300, :1505-1515, :1727-1735); called by
+        # Cnn_9layers_Conformer (:2163, :2177)
         sd.update(_linear(rng, 'classifier', ctor_classes, CONFORMER_DIM))
         sd.update(_linear(rng, 'linear_emb', trunk, 1))
     return sd
