@@ -479,6 +479,52 @@ sedx_status sedx_forward_windows_vote(sedx_handle* h, const float* d_audio, int6
                                       const sedx_window_spec* spec, const double* bin_thres, float* d_votes,
                                       void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* Ragged form of the `predict` driver: recordings of DIFFERENT lengths in one
+ * call (pytorch/predict.py:264-407 walks a directory of them).  Every clip
+ * follows exactly the rules of sedx_window_geometry for its own length and
+ * duration; the windows of all clips then form one item list that runs
+ * through the model in forwards of at most items_per_forward items (<= 0:
+ * all at once), and each clip is merged and averaged on its own.  A clip's
+ * output does not depend on the batch it runs in, so it is the output of
+ * sedx_forward_windows on that clip alone, bit for bit.
+ *   spec              driver SEDX_DRIVER_PREDICT and vote 0 only (main_strong
+ *                     pads every clip to 10 s: it has no ragged form);
+ *                     spec->audio_duration must be <= 0:
+ *   h_audio_duration  NULL, or [n_clips] loop bounds in seconds (an entry
+ *                     <= 0, like NULL: that clip's length / sample_rate)
+ *   h_clip_len        [n_clips] samples per clip
+ *   h_n_windows       [n_clips] windows per clip (may be NULL)
+ *   h_frame_off       [n_clips + 1] prefix sum of the clips' merged frame
+ *                     counts (may be NULL)
+ * A clip sedx_window_geometry refuses (an empty clip, a window of <= n_fft/2
+ * samples, the model's frame limits, a zero merge step), and, here only, a
+ * clip without one complete window (fewer than sample_duration * sample_rate
+ * samples; alone it runs as one zero-padded window), makes the whole call
+ * SEDX_EINVAL before any launch; sedx_last_error names its index.
+ *   d_audio           the clips back to back, fp32; clip c holds samples
+ *                     h_clip_off[c] .. h_clip_off[c + 1]) (any offsets, odd
+ *                     ones included; non-decreasing).  Samples a window needs
+ *                     past its clip's end read as zero (pad_truncate), never
+ *                     as the next clip's audio, and nothing past
+ *                     h_clip_off[n_clips] is read.
+ *   d_merged          [h_frame_off[n_clips]][classes_num]; clip c's rows
+ *                     start at h_frame_off[c]
+ * The workspace holds the model's for ONE forward of items_per_forward items,
+ * plus every window's framewise output (out_frames x classes_num floats) and
+ * the tables (one upload).  Asynchronous on `stream` like the other drivers;
+ * a GRU hand-off time-out surfaces through sedx_check_error. */
+sedx_status sedx_ragged_window_geometry(const sedx_handle* h, const int64_t* h_clip_len, int64_t n_clips,
+                                        const sedx_window_spec* spec, const double* h_audio_duration,
+                                        int64_t* h_n_windows, int64_t* h_frame_off, int64_t* window_samples,
+                                        int64_t* total_windows);
+sedx_status sedx_ragged_window_workspace_size(const sedx_handle* h, const int64_t* h_clip_len, int64_t n_clips,
+                                              const sedx_window_spec* spec, const double* h_audio_duration,
+                                              int64_t items_per_forward, size_t* bytes);
+sedx_status sedx_forward_windows_ragged(sedx_handle* h, const float* d_audio, const int64_t* h_clip_off,
+                                        int64_t n_clips, const sedx_window_spec* spec,
+                                        const double* h_audio_duration, int64_t items_per_forward, float* d_merged,
+                                        void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* Arithmetic of the GEMM-shaped work: the 9-layer conv stack (96.8 % of the
  * FLOPs), the GRU input projection and recurrence, the MHA projections and
  * the AttBlock projection.
@@ -772,6 +818,19 @@ sedx_status sedx_events_device(const float* d_x, int64_t n_clips, int64_t T, int
                                int32_t mode, double overlap_value, int32_t sample_duration,
                                int32_t* d_events, int64_t capacity, int64_t* d_info,
                                void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* Mode 0 of the above over clips of different lengths, as
+ * sedx_forward_windows_ragged leaves them: d_x [h_frame_off[n_clips]][C], clip
+ * c's rows at h_frame_off[c] (host, [n_clips + 1], non-decreasing).  One
+ * wavefront per (clip, class) series; events are (clip, class, bgn, fin) with
+ * frames relative to the clip, in (clip, class, time) order; d_info as above.
+ * Every clip holds at most 655,360 frames. */
+sedx_status sedx_events_ragged_workspace_size(const int64_t* h_frame_off, int64_t n_clips, int64_t C, size_t* bytes);
+sedx_status sedx_events_device_ragged(const float* d_x, const int64_t* h_frame_off, int64_t n_clips, int64_t C,
+                                      const double* high_thres, const double* low_thres, int32_t use_low_thres,
+                                      const int64_t* n_smooth, const int64_t* n_salt, int32_t* d_events,
+                                      int64_t capacity, int64_t* d_info, void* d_workspace, size_t workspace_bytes,
+                                      void* stream);
 
 /* Threshold calibration (utils/optimize_thresholds.py optimize_sed_thresholds):
  * segment-based true / false positive and false negative counts of

@@ -54,6 +54,14 @@ struct sedx_handle : sedx::Model {
   // forward / sedx_stage_times turns it into SEDX_EHIP
   unsigned* gru_err_host = nullptr;
   unsigned* gru_err_dev = nullptr;
+  // the last ragged window plan and what it was asked for (ragged_geometry_of)
+  struct RaggedMemo {
+    bool valid = false, has_dur = false;
+    std::vector<int64_t> len;
+    std::vector<double> dur;
+    sedx_window_spec spec{};
+    RaggedGeom rg;
+  } ragged_memo;
   // optional per-stage timing (sedx_set_profiling): mark() records into
   // ev_cur, which is ev_last in mode 1.  Mode 2 (accumulate): every forward
   // takes its own set from the pool, so forwards in flight on different
@@ -221,12 +229,14 @@ sedx_status get_ws(sedx_handle* h, size_t need, void* user, size_t user_bytes, f
 }
 
 // the log-mel frontend of plan p's items into its X0: n_win windows of
-// sig_len samples per clip at win_start (device; nullptr: one, at 0)
+// sig_len samples per clip at win_start (device; nullptr: one, at 0); or, with
+// item_tab (device, one row per item), every item's source from its row
 void run_logmel(sedx_handle* h, const ForwardPlan& p, float* ws, const float* audio, const int16_t* audio_i16,
                 int64_t clip_stride, int64_t n_clips, int n_win, const int64_t* win_start, int64_t clip_len,
-                int64_t sig_len, hipStream_t s) {
+                int64_t sig_len, hipStream_t s, const ItemRow* item_tab = nullptr) {
   const DevWeights& w = h->w;
   FrontendParams f{};
+  f.item_tab = item_tab;
   f.audio = audio;
   f.audio_i16 = audio_i16;
   f.clip_stride = clip_stride;
@@ -1073,7 +1083,190 @@ sedx_status sedx_forward_windows_vote(sedx_handle* h, const float* d_audio, int6
                                 stream);
   })
 }
+// ---- the ragged form of the predict driver: clips of different lengths in one call ----
+// One inference asks for the same plan three times (geometry, workspace size, forward), and a clip's merge plan
+// costs about a millisecond of host time to build: the handle keeps the last accepted plan with its question.
+static const char* ragged_geometry_of(const sedx_handle* hc, const int64_t* len, int64_t n,
+                                      const sedx_window_spec* spec, const double* dur, const RaggedGeom** out) {
+  sedx_handle::RaggedMemo& m = const_cast<sedx_handle*>(hc)->ragged_memo;
+  if (m.valid && spec && len && n > 0 && (size_t)n == m.len.size() && std::equal(len, len + n, m.len.begin()) &&
+      m.has_dur == (dur != nullptr) && (!dur || std::equal(dur, dur + n, m.dur.begin())) &&
+      spec->driver == m.spec.driver && spec->overlap == m.spec.overlap && spec->vote == m.spec.vote &&
+      spec->sample_duration == m.spec.sample_duration && spec->overlap_value == m.spec.overlap_value &&
+      spec->audio_duration == m.spec.audio_duration) {
+    *out = &m.rg;
+    return nullptr;
+  }
+  m.valid = false;
+  if (const char* why = ragged_geometry(*hc, len, n, spec, dur, &m.rg)) return why;   // (why points into m.rg)
+  m.len.assign(len, len + n);
+  m.has_dur = dur != nullptr;
+  if (dur) m.dur.assign(dur, dur + n);
+  m.spec = *spec;
+  m.valid = true;
+  *out = &m.rg;
+  return nullptr;
+}
+
+sedx_status sedx_ragged_window_geometry(const sedx_handle* h, const int64_t* h_clip_len, int64_t n_clips,
+                                        const sedx_window_spec* spec, const double* h_audio_duration,
+                                        int64_t* h_n_windows, int64_t* h_frame_off, int64_t* window_samples,
+                                        int64_t* total_windows) {
+  if (!h) return SEDX_EINVAL;
+  SEDX_HOST_TRY(h, {
+    const RaggedGeom* prg = nullptr;
+    if (const char* why = ragged_geometry_of(h, h_clip_len, n_clips, spec, h_audio_duration, &prg))
+      return fail(h, SEDX_EINVAL, "%s", why);
+    const RaggedGeom& rg = *prg;
+    if (h_n_windows) std::copy(rg.n_win.begin(), rg.n_win.end(), h_n_windows);
+    if (h_frame_off) std::copy(rg.frame_off.begin(), rg.frame_off.end(), h_frame_off);
+    if (window_samples) *window_samples = rg.full_len;
+    if (total_windows) *total_windows = rg.item_off.back();
+    return SEDX_OK;
+  })
+}
+
+sedx_status sedx_ragged_window_workspace_size(const sedx_handle* h, const int64_t* h_clip_len, int64_t n_clips,
+                                              const sedx_window_spec* spec, const double* h_audio_duration,
+                                              int64_t items_per_forward, size_t* bytes) {
+  if (!h) return SEDX_EINVAL;
+  if (!bytes) return fail(h, SEDX_EINVAL, "null size pointer");
+  SEDX_HOST_TRY(h, {
+    const RaggedGeom* prg = nullptr;
+    if (const char* why = ragged_geometry_of(h, h_clip_len, n_clips, spec, h_audio_duration, &prg))
+      return fail(h, SEDX_EINVAL, "%s", why);
+    const RaggedGeom& rg = *prg;
+    *bytes = ragged_layout(*h, h->tune, rg, items_per_forward).total_bytes;
+    return SEDX_OK;
+  })
+}
+
+// every window of every clip as one item list through the model, in forwards
+// of at most items_per_forward items, then every clip's own merge
+static sedx_status forward_windows_ragged_impl(sedx_handle* h, const float* d_audio, const int64_t* h_clip_off,
+                                               int64_t n_clips, const sedx_window_spec* spec,
+                                               const double* h_audio_duration, int64_t items_per_forward,
+                                               float* d_merged, void* d_workspace, size_t workspace_bytes,
+                                               void* stream) {
+  if (sedx_status e = preflight(h)) return e;
+  if (h->cfg.feature_type != SEDX_FEATURE_LOGMEL)
+    return fail(h, SEDX_EINVAL, "windowed inference needs a logmel model");
+  if (!d_audio || !d_merged || !h_clip_off || n_clips <= 0)
+    return fail(h, SEDX_EINVAL, "null pointer or empty batch");
+  std::vector<int64_t> len((size_t)n_clips);
+  for (int64_t c = 0; c < n_clips; ++c) {
+    len[c] = h_clip_off[c + 1] - h_clip_off[c];
+    if (h_clip_off[c] < 0 || len[c] < 0)
+      return fail(h, SEDX_EINVAL, "clip %lld: the clip offsets must be non-negative and non-decreasing", (long long)c);
+  }
+  const RaggedGeom* prg = nullptr;
+  if (const char* why = ragged_geometry_of(h, len.data(), n_clips, spec, h_audio_duration, &prg))
+    return fail(h, SEDX_EINVAL, "%s", why);
+  const RaggedGeom& rg = *prg;
+  const RaggedLayout rl = ragged_layout(*h, h->tune, rg, items_per_forward);
+  // the frontend and conv launches index items with 32-bit sizes (as forward_wave)
+  if (rl.chunk > INT32_MAX || rl.chunk * rg.g.T > INT32_MAX / 64)
+    return fail(h, SEDX_EINVAL, "forward too large: %lld windows (lower items_per_forward)", (long long)rl.chunk);
+  DeviceGuard dg(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  float* ws = nullptr;
+  if (sedx_status st = get_ws(h, rl.total_bytes, d_workspace, workspace_bytes, &ws)) return st;
+  const int C = h->cfg.classes_num;
+  // tables: built on the host, one copy (consumed by the call, as in forward_windows_impl)
+  std::vector<char> blob;
+  ragged_tables(rg, rl, h_clip_off, &blob);
+  char* d_tables = reinterpret_cast<char*>(ws + rl.tables);
+  HIP_TRY(h, hipMemcpyAsync(d_tables, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
+  const ItemRow* d_item = reinterpret_cast<const ItemRow*>(d_tables + rl.t_item);
+  const int64_t item_floats = rg.g.out_frames * C;
+  mark(h, 0, s);
+  for (int64_t i0 = 0; i0 < rl.items; i0 += rl.chunk) {
+    const int64_t n = std::min(rl.chunk, rl.items - i0);
+    ForwardPlan p;
+    if (const char* why = plan_forward(*h, h->tune, n, rg.g.T, &p)) return fail(h, SEDX_EINVAL, "%s", why);
+    // n items of one window each, their sources from the item table at i0
+    run_logmel(h, p, ws, d_audio, nullptr, 0, n, 1, nullptr, rg.full_len, rg.full_len, s, d_item + i0);
+    if (sedx_status st = run_body(h, p, ws, ws + rl.fw + i0 * item_floats, ws + rl.clipwise, nullptr, s)) return st;
+  }
+  RaggedMergeArgs a{};
+  a.fw = ws + rl.fw;
+  a.item_floats = item_floats;
+  a.crow = reinterpret_cast<const RaggedClipRow*>(d_tables + rl.t_clip);
+  a.off = reinterpret_cast<const int32_t*>(d_tables + rl.t_off);
+  a.src = reinterpret_cast<const int2*>(d_tables + rl.t_src);
+  a.div = reinterpret_cast<const int32_t*>(d_tables + rl.t_div);
+  a.n_clips = (int32_t)n_clips;
+  a.rows = (int32_t)rg.frame_off.back();
+  a.C = C;
+  a.merged = d_merged;
+  launch_merge_ragged(a, s);
+  return launch_status(h);
+}
+
+sedx_status sedx_forward_windows_ragged(sedx_handle* h, const float* d_audio, const int64_t* h_clip_off,
+                                        int64_t n_clips, const sedx_window_spec* spec,
+                                        const double* h_audio_duration, int64_t items_per_forward, float* d_merged,
+                                        void* d_workspace, size_t workspace_bytes, void* stream) {
+  if (!h) return SEDX_EINVAL;
+  SEDX_HOST_TRY(h, {
+    return forward_windows_ragged_impl(h, d_audio, h_clip_off, n_clips, spec, h_audio_duration, items_per_forward,
+                                       d_merged, d_workspace, workspace_bytes, stream);
+  })
+}
 #undef SEDX_HOST_TRY
+
+sedx_status sedx_events_ragged_workspace_size(const int64_t* h_frame_off, int64_t n_clips, int64_t C, size_t* bytes) {
+  if (!bytes || !h_frame_off || n_clips < 0 || C <= 0) return SEDX_EINVAL;
+  int64_t tmax = 0;
+  for (int64_t c = 0; c < n_clips; ++c) {
+    if (h_frame_off[c + 1] < h_frame_off[c]) return SEDX_EINVAL;
+    tmax = std::max(tmax, h_frame_off[c + 1] - h_frame_off[c]);
+  }
+  *bytes = events_workspace_bytes(n_clips * C, tmax, C) + align256((size_t)(n_clips + 1) * 8);
+  return SEDX_OK;
+}
+
+sedx_status sedx_events_device_ragged(const float* d_x, const int64_t* h_frame_off, int64_t n_clips, int64_t C,
+                                      const double* high_thres, const double* low_thres, int32_t use_low_thres,
+                                      const int64_t* n_smooth, const int64_t* n_salt, int32_t* d_events,
+                                      int64_t capacity, int64_t* d_info, void* d_workspace, size_t workspace_bytes,
+                                      void* stream) {
+  if (n_clips < 0 || C <= 0 || !h_frame_off || !d_info || !n_smooth || !n_salt || !high_thres ||
+      (capacity > 0 && !d_events) || capacity < 0 || (use_low_thres && !low_thres))
+    return SEDX_EINVAL;
+  size_t need = 0;
+  if (sedx_events_ragged_workspace_size(h_frame_off, n_clips, C, &need) != SEDX_OK) return SEDX_EINVAL;
+  int64_t tmax = 0;
+  for (int64_t c = 0; c < n_clips; ++c) tmax = std::max(tmax, h_frame_off[c + 1] - h_frame_off[c]);
+  if (n_clips > 0 && h_frame_off[n_clips] > h_frame_off[0] && !d_x) return SEDX_EINVAL;
+  if (tmax > events_max_frames()) return SEDX_EINVAL;   // a series' two bitmaps live in LDS
+  if (!d_workspace || workspace_bytes < need) return SEDX_EINVAL;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // counts, slots, then one packed block: the per-class parameters (as sedx_events_device) and the frame offsets
+  char* p = static_cast<char*>(d_workspace);
+  int64_t* counts = reinterpret_cast<int64_t*>(p);
+  p += align256(n_clips * C * 8);
+  int64_t* slots = reinterpret_cast<int64_t*>(p);
+  p += align256(n_clips * C * events_slot_cap(tmax) * 8);
+  const size_t o_hi = 0, o_lo = align256(C * 4), o_ns = o_lo + align256(C * 8), o_salt = o_ns + align256(C * 8);
+  const size_t o_foff = o_salt + align256(C * 8);
+  std::vector<char> blob(o_foff + (size_t)(n_clips + 1) * 8, 0);
+  for (int64_t k = 0; k < C; ++k) {
+    reinterpret_cast<float*>(blob.data() + o_hi)[k] = (float)high_thres[k];
+    reinterpret_cast<double*>(blob.data() + o_lo)[k] = use_low_thres ? low_thres[k] : 0.0;
+    reinterpret_cast<int64_t*>(blob.data() + o_ns)[k] = n_smooth[k];
+    reinterpret_cast<int64_t*>(blob.data() + o_salt)[k] = n_salt[k];
+  }
+  std::memcpy(blob.data() + o_foff, h_frame_off, (size_t)(n_clips + 1) * 8);
+  if (hipMemcpyAsync(p, blob.data(), blob.size(), hipMemcpyHostToDevice, s) != hipSuccess) return SEDX_EHIP;
+  EventArgs a{d_x, n_clips, tmax, C, reinterpret_cast<const float*>(p + o_hi),
+              reinterpret_cast<const double*>(p + o_lo), reinterpret_cast<const int64_t*>(p + o_ns),
+              reinterpret_cast<const int64_t*>(p + o_salt), use_low_thres, 0, 0, counts, slots,
+              events_slot_cap(tmax), d_info, d_events, capacity};
+  launch_events_ragged(a, reinterpret_cast<const int64_t*>(p + o_foff), s);
+  if (take_launch_error() != hipSuccess) return SEDX_EHIP;
+  return hipGetLastError() == hipSuccess ? SEDX_OK : SEDX_EHIP;
+}
 
 sedx_status sedx_events_workspace_size(int64_t n_clips, int64_t T, int64_t C, size_t* bytes) {
   if (!bytes || n_clips < 0 || T < 0 || C <= 0) return SEDX_EINVAL;

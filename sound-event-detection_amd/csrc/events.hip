@@ -52,17 +52,23 @@ constexpr int64_t EV_LDS_BYTES = 160 * 1024;
 constexpr int64_t EV_MAX_WORDS = EV_LDS_BYTES / 16;   // bitmap words per series (T <= 655,360)
 
 // dynamic LDS: [wpb][2][W] words (on, below); wpb series per workgroup
-template <int MODE>
-__global__ __launch_bounds__(64 * EV_WAVES) void events_series_kernel(EventArgs a, int64_t W, int wpb) {
+// RAGGED (mode 0): clip n's series has frame_off[n + 1] - frame_off[n] frames, its rows at frame_off[n]; a.T,
+// the longest clip's frames, sized W and the slots.  The walk below runs on the clip's own T and word count.
+template <int MODE, bool RAGGED>
+__global__ __launch_bounds__(64 * EV_WAVES) void events_series_kernel(EventArgs a, const int64_t* frame_off,
+                                                                      int64_t Wmax, int wpb) {
   extern __shared__ uint64_t ev_lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t C = a.C, T = a.T;
+  const int64_t C = a.C;
   const int64_t sid = (int64_t)blockIdx.x * wpb + wave;
   if (wave >= wpb || sid >= a.N * C) return;        // wave-uniform
   const int64_t n = sid / C, k = sid - n * C;
-  uint64_t* om = ev_lds + (int64_t)wave * 2 * W;
-  uint64_t* lm = om + W;
-  const float* xs = a.x + n * T * C + k;
+  const int64_t row0 = RAGGED ? frame_off[n] : n * a.T;
+  const int64_t T = RAGGED ? frame_off[n + 1] - row0 : a.T;
+  const int64_t W = RAGGED ? (T + 63) / 64 : Wmax;
+  uint64_t* om = ev_lds + (int64_t)wave * 2 * Wmax;
+  uint64_t* lm = om + Wmax;
+  const float* xs = a.x + row0 * C + k;
   const float hi = a.hi[k];
   const double lo = a.lo[k];
   const float lo_f = (float)lo;
@@ -178,13 +184,28 @@ void launch_events(const EventArgs& a, int mode, hipStream_t s) {
   const unsigned blocks = (unsigned)((n + wpb - 1) / wpb);
   const size_t lds = (size_t)wpb * 2 * W * 8;
   // > 64 KB of dynamic LDS must be opted into (per device: launch_info)
-  if (!launch_info(reinterpret_cast<const void*>(events_series_kernel<0>), 64, EV_LDS_BYTES).ok ||
-      !launch_info(reinterpret_cast<const void*>(events_series_kernel<1>), 64, EV_LDS_BYTES).ok)
+  if (!launch_info(reinterpret_cast<const void*>(events_series_kernel<0, false>), 64, EV_LDS_BYTES).ok ||
+      !launch_info(reinterpret_cast<const void*>(events_series_kernel<1, false>), 64, EV_LDS_BYTES).ok)
     return;
+  const int64_t* none = nullptr;
   if (mode == 0)
-    hipLaunchKernelGGL(events_series_kernel<0>, dim3(blocks), dim3(64 * wpb), lds, s, a, W, wpb);
+    hipLaunchKernelGGL((events_series_kernel<0, false>), dim3(blocks), dim3(64 * wpb), lds, s, a, none, W, wpb);
   else
-    hipLaunchKernelGGL(events_series_kernel<1>, dim3(blocks), dim3(64 * wpb), lds, s, a, W, wpb);
+    hipLaunchKernelGGL((events_series_kernel<1, false>), dim3(blocks), dim3(64 * wpb), lds, s, a, none, W, wpb);
+  hipLaunchKernelGGL(events_compact_kernel, dim3(1), dim3(1024), 0, s, a);
+}
+
+// a.T: the longest clip's frames (<= events_max_frames(): api.cpp checks); LDS is sized for it
+void launch_events_ragged(const EventArgs& a, const int64_t* frame_off, hipStream_t s) {
+  (void)hipMemsetAsync(a.info, 0, 2 * sizeof(int64_t), s);
+  const int64_t n = a.N * a.C;
+  if (n == 0) return;
+  const int64_t W = (a.T + 63) / 64;
+  int wpb = (int)std::min<int64_t>(EV_WAVES, std::max<int64_t>(1, EV_LDS_BYTES / (16 * std::max<int64_t>(W, 1))));
+  const unsigned blocks = (unsigned)((n + wpb - 1) / wpb);
+  const size_t lds = (size_t)wpb * 2 * W * 8;
+  if (!launch_info(reinterpret_cast<const void*>(events_series_kernel<0, true>), 64, EV_LDS_BYTES).ok) return;
+  hipLaunchKernelGGL((events_series_kernel<0, true>), dim3(blocks), dim3(64 * wpb), lds, s, a, frame_off, W, wpb);
   hipLaunchKernelGGL(events_compact_kernel, dim3(1), dim3(1024), 0, s, a);
 }
 

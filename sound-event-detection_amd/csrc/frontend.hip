@@ -119,7 +119,7 @@ __device__ __forceinline__ float2 real_bin(const float2* Z, const float2* tw, in
 // "packed FP32").
 constexpr int FE_WAVES = 16;
 
-template <int NFFT, bool I16>
+template <int NFFT, bool I16, bool TAB>
 __global__ __launch_bounds__(64 * FE_WAVES) void logmel_kernel(FrontendParams p) {
   constexpr int N2 = NFFT / 2;
   constexpr int NS = NFFT / 64;          // samples per lane per frame
@@ -152,11 +152,18 @@ __global__ __launch_bounds__(64 * FE_WAVES) void logmel_kernel(FrontendParams p)
   auto load = [&](int fr, float* v) {
     const unsigned item = (unsigned)fr / (unsigned)p.T;
     const int t = fr - (int)item * p.T;
-    const unsigned clip = item / (unsigned)p.n_win;
-    const int w = (int)(item - clip * (unsigned)p.n_win);
-    const int64_t wstart = p.win_start ? p.win_start[w] : 0;
-    const int64_t src_off = (int64_t)clip * p.clip_stride + wstart;
-    const int64_t av64 = p.clip_len - wstart;        // samples of this item backed by audio
+    int64_t src_off, av64;                           // the item's source, samples of it backed by audio
+    if constexpr (TAB) {
+      const ItemRow row = p.item_tab[item];          // the ragged driver's item table, L2-resident
+      src_off = row.src;
+      av64 = row.avail;
+    } else {
+      const unsigned clip = item / (unsigned)p.n_win;
+      const int w = (int)(item - clip * (unsigned)p.n_win);
+      const int64_t wstart = p.win_start ? p.win_start[w] : 0;
+      src_off = (int64_t)clip * p.clip_stride + wstart;
+      av64 = p.clip_len - wstart;
+    }
     const int avail = av64 > L ? L : (int)av64;       // (j < L always)
     const int pos0 = t * p.hop - N2;                  // start in un-padded coordinates
     if (!I16 && pos0 >= 0 && pos0 + NFFT <= avail && ((src_off + pos0) & 1) == 0) {
@@ -323,7 +330,7 @@ typedef float fe_f32x4 __attribute__((ext_vector_type(4)));
 // fma chain over its four k; zero weights leave the chain unchanged for the
 // finite, non-negative powers), i.e. the band-sum path's bits, with ~1/4 of
 // its instructions per frame.
-template <bool I16, bool MT>
+template <bool I16, bool MT, bool TAB>
 __global__ __launch_bounds__(64 * FE16_WAVES) void logmel512_kernel(FrontendParams p) {
   constexpr int NFFT = 512, N2 = 256;
   constexpr int FE16_FRAME = fe16_frame<MT>();
@@ -404,11 +411,18 @@ __global__ __launch_bounds__(64 * FE16_WAVES) void logmel512_kernel(FrontendPara
     }
     const unsigned item = (unsigned)fr / (unsigned)p.T;
     const int t = fr - (int)item * p.T;
-    const unsigned clip = item / (unsigned)p.n_win;
-    const int w = (int)(item - clip * (unsigned)p.n_win);
-    const int64_t wstart = p.win_start ? p.win_start[w] : 0;   // window table (any length), L2-resident
-    const int64_t src_off = (int64_t)clip * p.clip_stride + wstart;
-    const int64_t av64 = p.clip_len - wstart;
+    int64_t src_off, av64;
+    if constexpr (TAB) {
+      const ItemRow row = p.item_tab[item];                      // the ragged driver's item table, L2-resident
+      src_off = row.src;
+      av64 = row.avail;
+    } else {
+      const unsigned clip = item / (unsigned)p.n_win;
+      const int w = (int)(item - clip * (unsigned)p.n_win);
+      const int64_t wstart = p.win_start ? p.win_start[w] : 0;   // window table (any length), L2-resident
+      src_off = (int64_t)clip * p.clip_stride + wstart;
+      av64 = p.clip_len - wstart;
+    }
     const int avail = av64 > L ? L : (int)av64;
     const int pos0 = t * p.hop - N2;
     if (!I16 && pos0 >= 0 && pos0 + NFFT <= avail && ((src_off + pos0) & 1) == 0) {
@@ -586,10 +600,10 @@ constexpr size_t fe_static_lds() {
   return (size_t)NFFT * 8 + NFFT * 4 + (size_t)FE_WAVES * 2 * fe_buf_len<NFFT / 2>() * 8;
 }
 
-template <int NFFT, bool I16>
+template <int NFFT, bool I16, bool TAB>
 static void launch_logmel_t(const FrontendParams& p0, int64_t total, hipStream_t s) {
   const LaunchInfo li =
-      launch_info(reinterpret_cast<const void*>(logmel_kernel<NFFT, I16>), 64 * FE_WAVES, fe_mel_lds<NFFT>());
+      launch_info(reinterpret_cast<const void*>(logmel_kernel<NFFT, I16, TAB>), 64 * FE_WAVES, fe_mel_lds<NFFT>());
   if (!li.ok) return;
   FrontendParams p = p0;
   p.mel_lds_floats = (int32_t)(li.dyn / 4);
@@ -602,15 +616,15 @@ static void launch_logmel_t(const FrontendParams& p0, int64_t total, hipStream_t
   int64_t blocks = (total + FE_WAVES - 1) / FE_WAVES;
   blocks = std::min<int64_t>(blocks, (int64_t)li.ncu * per_cu);
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL((logmel_kernel<NFFT, I16>), dim3((unsigned)blocks), dim3(64 * FE_WAVES), li.dyn, s, p);
+  hipLaunchKernelGGL((logmel_kernel<NFFT, I16, TAB>), dim3((unsigned)blocks), dim3(64 * FE_WAVES), li.dyn, s, p);
 }
 
 // one wave per four frames; every wave walks several groups so the register
 // prefetch of the next group overlaps the current one
-template <bool I16, bool MT>
+template <bool I16, bool MT, bool TAB>
 static void launch_logmel512(const FrontendParams& p0, int64_t total, hipStream_t s) {
   const size_t dyn = MT ? ((size_t)p0.mt_floats * 4 + 255) / 256 * 256 : fe_mel_lds<512>();
-  const LaunchInfo li = launch_info(reinterpret_cast<const void*>(logmel512_kernel<I16, MT>), 64 * FE16_WAVES,
+  const LaunchInfo li = launch_info(reinterpret_cast<const void*>(logmel512_kernel<I16, MT, TAB>), 64 * FE16_WAVES,
                                     MT ? FE_MT_MAX_FLOATS * 4 : fe_mel_lds<512>());
   if (!li.ok) return;
   FrontendParams p = p0;
@@ -622,34 +636,40 @@ static void launch_logmel512(const FrontendParams& p0, int64_t total, hipStream_
   // and would say one)
   blocks = std::min<int64_t>(blocks, (int64_t)li.ncu * 2);
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL((logmel512_kernel<I16, MT>), dim3((unsigned)blocks), dim3(64 * FE16_WAVES), MT ? dyn : li.dyn,
+  hipLaunchKernelGGL((logmel512_kernel<I16, MT, TAB>), dim3((unsigned)blocks), dim3(64 * FE16_WAVES), MT ? dyn : li.dyn,
                      s, p);
+}
+
+// TAB: the items' sources come from p.item_tab (the ragged windowed driver); the launches without a table
+// instantiate the kernels as they were
+template <bool I16, bool TAB>
+static void launch_logmel_src(const FrontendParams& p, int n_fft, int64_t total, hipStream_t s) {
+  switch (n_fft) {
+    case 256:
+      launch_logmel_t<256, I16, TAB>(p, total, s);
+      break;
+    case 512:
+      // the MFMA mel path when the host built its table (melW bands fit)
+      if (p.mel_mt && p.mt_floats <= FE_MT_MAX_FLOATS) launch_logmel512<I16, true, TAB>(p, total, s);
+      else launch_logmel512<I16, false, TAB>(p, total, s);
+      break;
+    case 1024:
+      launch_logmel_t<1024, I16, TAB>(p, total, s);
+      break;
+    default: break;
+  }
 }
 
 void launch_logmel(const FrontendParams& p, int n_fft, hipStream_t s) {
   const int64_t total = (int64_t)p.n_clips * p.n_win * p.T;
   if (total >= ((int64_t)1 << 31) - 4 ||p.sig_len >= (int64_t)1 << 31) return note_launch_error(hipErrorInvalidValue);
   const bool i16 = p.audio_i16 != nullptr;
-  switch (n_fft) {
-    case 256:
-      if (i16) launch_logmel_t<256, true>(p, total, s);
-      else launch_logmel_t<256, false>(p, total, s);
-      break;
-    case 512:
-      // the MFMA mel path when the host built its table (melW bands fit)
-      if (p.mel_mt && p.mt_floats <= FE_MT_MAX_FLOATS) {
-        if (i16) launch_logmel512<true, true>(p, total, s);
-        else launch_logmel512<false, true>(p, total, s);
-      } else {
-        if (i16) launch_logmel512<true, false>(p, total, s);
-        else launch_logmel512<false, false>(p, total, s);
-      }
-      break;
-    case 1024:
-      if (i16) launch_logmel_t<1024, true>(p, total, s);
-      else launch_logmel_t<1024, false>(p, total, s);
-      break;
-    default: break;
+  if (p.item_tab) {
+    if (i16) launch_logmel_src<true, true>(p, n_fft, total, s);
+    else launch_logmel_src<false, true>(p, n_fft, total, s);
+  } else {
+    if (i16) launch_logmel_src<true, false>(p, n_fft, total, s);
+    else launch_logmel_src<false, false>(p, n_fft, total, s);
   }
 }
 

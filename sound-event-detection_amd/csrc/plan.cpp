@@ -467,4 +467,140 @@ WinLayout win_layout(const Model& m, const Tuning& t, int64_t n_clips, const Win
   return l;
 }
 
+// ---- ragged windowed driver -----------------------------------------------------
+const char* ragged_geometry(const Model& m, const int64_t* clip_len, int64_t n_clips, const sedx_window_spec* spec,
+                            const double* dur, RaggedGeom* rg) {
+  if (!spec) return "null window spec";
+  if (!clip_len || n_clips <= 0) return "null clip lengths or no clips";
+  if (spec->driver != SEDX_DRIVER_PREDICT)
+    return "the ragged driver is predict.py's: main_strong pads every clip to 10 s and has no ragged form";
+  if (spec->vote != 0) return "the ragged driver has no vote merge (sedx_window_spec.vote must be 0)";
+  if (spec->audio_duration > 0) return "sedx_window_spec.audio_duration must be <= 0: the durations come per clip";
+  if (n_clips >= INT32_MAX) return "too many clips";
+  *rg = RaggedGeom{};
+  rg->clip_len.assign(clip_len, clip_len + n_clips);
+  rg->n_win.resize((size_t)n_clips);
+  rg->plan_of.resize((size_t)n_clips);
+  rg->item_off.assign((size_t)n_clips + 1, 0);
+  rg->frame_off.assign((size_t)n_clips + 1, 0);
+  std::vector<int32_t> plan_nw;   // the window count plans[i] was built for
+  WindowLoop wl;
+  WinGeom wg;
+  for (int64_t c = 0; c < n_clips; ++c) {
+    sedx_window_spec sp = *spec;
+    sp.audio_duration = dur && dur[c] > 0 ? dur[c] : 0.0;
+    const char* why = window_loop(m.cfg.sample_rate, clip_len[c], sp, &wl);
+    const int32_t nw = (int32_t)wl.start.size();
+    // the ragged driver's own rule: a clip holds at least one complete window.  (Alone, such a clip runs as one
+    // zero-padded window, as in the reference; a directory's stray short file is refused by index instead, and
+    // predict_files lists it as skipped.)
+    if (!why && clip_len[c] < (int64_t)sp.sample_duration * m.cfg.sample_rate)
+      why = "no complete window: the clip is shorter than sample_duration";
+    size_t pi = plan_nw.size();
+    if (!why) {
+      // window_geometry's remaining rules (the window's samples, the model's frame limits, the merge) see a
+      // clip only through its window count: one run, and one merge plan, per distinct count
+      pi = (size_t)(std::find(plan_nw.begin(), plan_nw.end(), nw) - plan_nw.begin());
+      if (pi == plan_nw.size()) {
+        why = window_geometry(m, clip_len[c], &sp, true, &wg);
+        if (!why) {
+          if (wg.groups.size() != 1) why = "windows of more than one length";   // (not the predict driver's)
+          else {
+            rg->full_len = wg.full_len;
+            rg->g = wg.groups[0].g;
+            plan_nw.push_back(nw);
+            rg->plans.push_back(std::move(wg.plan));
+          }
+        }
+      }
+    }
+    if (why) {
+      char buf[160];
+      snprintf(buf, sizeof(buf), "%s", why);   // (why may point into wg.reject)
+      snprintf(rg->reject, sizeof(rg->reject), "clip %lld: %s", (long long)c, buf);
+      return rg->reject;
+    }
+    rg->n_win[c] = nw;
+    rg->plan_of[c] = (int32_t)pi;
+    rg->item_off[c + 1] = rg->item_off[c] + nw;
+    rg->frame_off[c + 1] = rg->frame_off[c] + rg->plans[pi].N;
+    rg->win_start.insert(rg->win_start.end(), wl.start.begin(), wl.start.end());
+    // the tables index items and merged rows with 32 bits
+    if (rg->item_off[c + 1] > INT32_MAX / 2 || rg->frame_off[c + 1] > INT32_MAX / std::max(1, m.cfg.classes_num))
+      return "too many windows or merged frames for one ragged call";
+  }
+  return nullptr;
+}
+
+RaggedLayout ragged_layout(const Model& m, const Tuning& t, const RaggedGeom& rg, int64_t items_per_forward) {
+  RaggedLayout l;
+  const size_t C = m.cfg.classes_num;
+  l.items = rg.item_off.back();
+  l.chunk = items_per_forward > 0 ? std::min(items_per_forward, l.items) : l.items;
+  // the forwards: full chunks, then the rest (a smaller batch may plan other kernels)
+  ForwardPlan fp;
+  plan_forward(m, t, l.chunk, rg.g.T, &fp);
+  l.model_bytes = fp.total_bytes;
+  if (l.chunk > 0 && l.items % l.chunk) {
+    plan_forward(m, t, l.items % l.chunk, rg.g.T, &fp);
+    l.model_bytes = std::max(l.model_bytes, fp.total_bytes);
+  }
+  size_t end = l.model_bytes;
+  l.fw = take(end, (size_t)l.items * rg.g.out_frames * C).off;
+  l.clipwise = take(end, (size_t)l.chunk * C).off;
+  l.tables = end / 4;
+  for (const MergePlan& p : rg.plans) {
+    l.n_off += (size_t)p.N + 1;
+    l.n_src += p.src.size();
+  }
+  size_t b = 0;
+  l.t_item = carve(b, sizeof(ItemRow) * (size_t)l.items);
+  l.t_clip = carve(b, sizeof(RaggedClipRow) * (rg.n_win.size() + 1));
+  l.t_off = carve(b, 4 * l.n_off);
+  l.t_src = carve(b, 8 * l.n_src);
+  l.t_div = carve(b, 4 * l.n_off);
+  l.table_bytes = b;
+  l.total_bytes = end + b;
+  return l;
+}
+
+void ragged_tables(const RaggedGeom& rg, const RaggedLayout& l, const int64_t* clip_off, std::vector<char>* blob) {
+  blob->assign(l.table_bytes, 0);
+  ItemRow* item = reinterpret_cast<ItemRow*>(blob->data() + l.t_item);
+  RaggedClipRow* crow = reinterpret_cast<RaggedClipRow*>(blob->data() + l.t_clip);
+  int32_t* off = reinterpret_cast<int32_t*>(blob->data() + l.t_off);
+  int32_t* src = reinterpret_cast<int32_t*>(blob->data() + l.t_src);   // (window, frame) pairs
+  int32_t* div = reinterpret_cast<int32_t*>(blob->data() + l.t_div);
+  // the plans' tables back to back; off stays relative to its own plan's src entries
+  std::vector<int32_t> off0(rg.plans.size()), src0(rg.plans.size());
+  size_t no = 0, ns = 0;
+  for (size_t pi = 0; pi < rg.plans.size(); ++pi) {
+    const MergePlan& p = rg.plans[pi];
+    off0[pi] = (int32_t)no;
+    src0[pi] = (int32_t)ns;
+    std::copy(p.off.begin(), p.off.end(), off + no);
+    std::copy(p.div.begin(), p.div.end(), div + no);   // N entries of the N + 1 (the last stays 0)
+    for (size_t j = 0; j < p.src.size(); ++j) {
+      const int32_t id = p.src[j];
+      const int w = (int)(std::upper_bound(p.win_base.begin(), p.win_base.end(), id) - p.win_base.begin()) - 1;
+      src[2 * (ns + j)] = w;
+      src[2 * (ns + j) + 1] = id - p.win_base[w];
+    }
+    no += (size_t)p.N + 1;
+    ns += p.src.size();
+  }
+  const size_t n_clips = rg.n_win.size();
+  for (size_t c = 0; c < n_clips; ++c) {
+    crow[c] = RaggedClipRow{(int32_t)rg.frame_off[c], (int32_t)rg.item_off[c], off0[rg.plan_of[c]], src0[rg.plan_of[c]]};
+    for (int32_t w = 0; w < rg.n_win[c]; ++w) {
+      const int64_t st = rg.win_start[(size_t)rg.item_off[c] + w];
+      // samples of the window backed by the clip's audio, in [0, full_len]: beyond them pad_truncate's zeros
+      const int64_t av = std::min(rg.full_len, std::max<int64_t>(0, rg.clip_len[c] - st));
+      // a window wholly past its clip reads nothing: its source stays inside the buffer
+      item[rg.item_off[c] + w] = ItemRow{clip_off[c] + (av > 0 ? st : 0), av};
+    }
+  }
+  crow[n_clips] = RaggedClipRow{(int32_t)rg.frame_off[n_clips], (int32_t)rg.item_off[n_clips], 0, 0};
+}
+
 }  // namespace sedx

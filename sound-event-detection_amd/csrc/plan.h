@@ -257,4 +257,51 @@ struct WinLayout {
 };
 WinLayout win_layout(const Model& m, const Tuning& t, int64_t n_clips, const WinGeom& wg);
 
+// ---- ragged windowed driver (predict.py's directory loop) ----------------------
+// Clips of different lengths in one call.  Every clip follows window_geometry
+// for its own length and duration (the predict driver: every window is
+// pad_truncate'd to full_len samples, so all items share one Geometry); the
+// windows of all clips form one item list, clip by clip in window order, and
+// one MergePlan per DISTINCT window count serves every clip with that count.
+struct RaggedGeom {
+  int64_t full_len = 0;              // samples of a window
+  Geometry g{};                      // of every item
+  std::vector<int64_t> clip_len;     // [n_clips]
+  std::vector<int32_t> n_win;        // [n_clips]
+  std::vector<int32_t> plan_of;      // [n_clips] index into plans
+  std::vector<int64_t> item_off;     // [n_clips + 1] first item of clip c
+  std::vector<int64_t> frame_off;    // [n_clips + 1] first merged frame of clip c
+  std::vector<int64_t> win_start;    // [items] sample offset of the item inside its clip
+  std::vector<MergePlan> plans;
+  char reject[192] = {};
+};
+// nullptr, or why the call is refused (SEDX_EINVAL; a refused clip is named by index).  dur: nullptr or
+// [n_clips] loop bounds in seconds (<= 0: the clip's own length)
+const char* ragged_geometry(const Model& m, const int64_t* clip_len, int64_t n_clips, const sedx_window_spec* spec,
+                            const double* dur, RaggedGeom* rg);
+
+// the item table row of the log-mel frontend (FrontendParams::item_tab): where the item's samples start in the
+// audio buffer and how many of them are backed by audio (beyond: pad_truncate zeros; <= 0: none)
+struct ItemRow {
+  int64_t src, avail;
+};
+// a clip's row of the ragged merge: merged frames [frame0, next row's frame0), items from item0, and where its
+// plan's tables start in the concatenated off / src tables (div is laid out like off)
+struct RaggedClipRow {
+  int32_t frame0, item0, off0, src0;
+};
+// the device area: the model workspace of one forward of `chunk` items, every item's framewise output, the
+// chunk's clipwise outputs, then the tables, 256-B aligned, built on the host and uploaded once
+struct RaggedLayout {
+  int64_t items = 0, chunk = 0;          // items per forward (the last forward runs the rest)
+  size_t model_bytes = 0;
+  size_t fw = 0, clipwise = 0;           // floats from the area start
+  size_t tables = 0, table_bytes = 0, total_bytes = 0;   // tables: floats from the area start
+  size_t t_item = 0, t_clip = 0, t_off = 0, t_src = 0, t_div = 0;   // byte offsets in the tables
+  size_t n_off = 0, n_src = 0;           // entries of the concatenated off (= div) and src tables
+};
+RaggedLayout ragged_layout(const Model& m, const Tuning& t, const RaggedGeom& rg, int64_t items_per_forward);
+// the tables' image (table_bytes).  clip_off [n_clips + 1]: the clips' sample offsets in the audio buffer
+void ragged_tables(const RaggedGeom& rg, const RaggedLayout& l, const int64_t* clip_off, std::vector<char>* blob);
+
 }  // namespace sedx

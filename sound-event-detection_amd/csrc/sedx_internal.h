@@ -59,6 +59,10 @@ struct FrontendParams {
   const float* bn_mean;     // [64]
   const float* bn_bias;     // [64]
   float* out;               // X0 [items][T][64]
+  // per-item source table (the ragged windowed driver; device, [n_clips * n_win]): item i reads its samples at
+  // audio + item_tab[i].src, item_tab[i].avail of them backed by audio, instead of clip * clip_stride +
+  // win_start[w] and clip_len - win_start[w].  nullptr: the launches without a table, unchanged
+  const ItemRow* item_tab;
 };
 void launch_logmel(const FrontendParams& p, int n_fft, hipStream_t s);
 
@@ -447,6 +451,21 @@ struct MergeArgs {
   float* merged;          // [n_clips][N][C]
 };
 void launch_merge_plan(const MergeArgs& a, hipStream_t s);
+// The ragged driver's merge: clips of different window counts, one plan per distinct count (plan.h RaggedGeom).
+// Item i's framewise output is at fw + i * item_floats; merged row r belongs to the clip whose rows [frame0,
+// next frame0) hold it (crow has n_clips + 1 rows, the last one's frame0 = rows); per clip the fold and the
+// divisor are merge_plan_kernel's.
+struct RaggedMergeArgs {
+  const float* fw;
+  int64_t item_floats;          // out_frames * C
+  const RaggedClipRow* crow;    // [n_clips + 1]
+  const int32_t* off;           // the plans' off tables, concatenated
+  const int2* src;              // (window, frame), concatenated
+  const int32_t* div;           // laid out like off
+  int32_t n_clips, rows, C;
+  float* merged;                // [rows][C]
+};
+void launch_merge_ragged(const RaggedMergeArgs& a, hipStream_t s);
 
 // ---- events (events.hip) --------------------------------------------------
 struct EventArgs {
@@ -469,6 +488,9 @@ int64_t events_slot_cap(int64_t T);
 int64_t events_max_frames();
 size_t events_workspace_bytes(int64_t n_series, int64_t T, int64_t C);
 void launch_events(const EventArgs& a, int mode, hipStream_t s);
+// mode 0 over clips of different lengths: x [frame_off[N]][C], clip n's rows at frame_off[n] (device, [N + 1]);
+// a.T = the longest clip's frames (sizes the bitmaps and the slots)
+void launch_events_ragged(const EventArgs& a, const int64_t* frame_off, hipStream_t s);
 
 // ---- threshold calibration: segment-based tp / fp / fn counts (calib.hip) ----
 struct CalibArgs {

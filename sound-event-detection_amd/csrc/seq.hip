@@ -579,4 +579,45 @@ void launch_merge_plan(const MergeArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(merge_plan_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);
 }
 
+// ---------------------------------------------------------------------------
+// The ragged driver's merge: clips of different window counts, one host plan
+// per distinct count.  One thread per (merged row, class): the row's clip is
+// the last one whose first row is <= it (binary search of the clip table,
+// L2-resident), then merge_plan_kernel's fold of that clip's windows in the
+// plan's order and its divisor, so a clip merges to the same bits as alone.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void merge_ragged_kernel(RaggedMergeArgs a) {
+  const int64_t total = (int64_t)a.rows * a.C;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int k = (int)(i % a.C);
+    const int r = (int)(i / a.C);
+    int lo = 0, hi = a.n_clips;                  // crow[lo].frame0 <= r < crow[hi].frame0 (crow[n_clips].frame0 = rows)
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (a.crow[mid].frame0 <= r) lo = mid;
+      else hi = mid;
+    }
+    const RaggedClipRow c = a.crow[lo];
+    const int f = r - c.frame0;
+    const float* fw = a.fw + (int64_t)c.item0 * a.item_floats + k;
+    float s = 0.f;
+    const int j0 = a.off[c.off0 + f], j1 = a.off[c.off0 + f + 1];
+    for (int j = j0; j < j1; ++j) {
+      const int2 e = a.src[c.src0 + j];
+      const float v = fw[(int64_t)e.x * a.item_floats + (int64_t)e.y * a.C];
+      s = j == j0 ? v : s + v;                   // prev_overlap + curr_overlap, window order
+    }
+    const int d = a.div[c.off0 + f];
+    a.merged[i] = d > 1 ? s / (float)d : s;      // float32 /= int (utilities.py:435)
+  }
+}
+
+void launch_merge_ragged(const RaggedMergeArgs& a, hipStream_t s) {
+  const int64_t total = (int64_t)a.rows * a.C;
+  if (total <= 0 || a.n_clips <= 0) return;
+  int64_t blocks = (total + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(merge_ragged_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);
+}
+
 }  // namespace sedx

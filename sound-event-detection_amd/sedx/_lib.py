@@ -27,7 +27,9 @@ EXPORTS = ['sedx_create', 'sedx_destroy', 'sedx_last_error', 'sedx_version', 'se
            'sedx_set_tuning', 'sedx_set_capture', 'sedx_window_starts', 'sedx_merge_host', 'sedx_check_error',
            'sedx_abi_version', 'sedx_conv_launch_plan', 'sedx_gemm_launch_plan',
            'sedx_average_precision', 'sedx_average_precision_workspace_size', 'sedx_average_precision_device',
-           'sedx_rank_tile', 'sedx_gamma_workspace_layout']
+           'sedx_rank_tile', 'sedx_gamma_workspace_layout',
+           'sedx_ragged_window_geometry', 'sedx_ragged_window_workspace_size', 'sedx_forward_windows_ragged',
+           'sedx_events_ragged_workspace_size', 'sedx_events_device_ragged']
 TUNE_GRU_KERNEL, TUNE_GRU_HANDOFF, TUNE_WINO_BLOCK1, TUNE_MEL_MFMA, TUNE_GRU_SPIN, TUNE_WINO_ORDER = 0, 1, 2, 3, 4, 5
 TUNE_GAMMA_SPEC = 6
 TUNE_WINO_F43 = 7
@@ -156,6 +158,11 @@ def lib():
         'sedx_events_workspace_size': ([I64, I64, I64, PSZ], I32),
         'sedx_events_device': ([P, I64, I64, I64, P, P, I32, P, P, I32, F64, I32, P, I64, P, P, SZ, P],
                                I32),
+        'sedx_ragged_window_geometry': ([P, P, I64, PSPEC, P, P, P, PI64, PI64], I32),
+        'sedx_ragged_window_workspace_size': ([P, P, I64, PSPEC, P, I64, PSZ], I32),
+        'sedx_forward_windows_ragged': ([P, P, P, I64, PSPEC, P, I64, P, P, SZ, P], I32),
+        'sedx_events_ragged_workspace_size': ([P, I64, I64, PSZ], I32),
+        'sedx_events_device_ragged': ([P, P, I64, I64, P, P, I32, P, P, P, I64, P, P, SZ, P], I32),
         'sedx_segment_counts': ([P, I64, I64, I64, P, I64, I64, P, P, P, P, P], I32),
         'sedx_segment_counts_workspace_size': ([I64, I64, I64, I64, PSZ], I32),
         'sedx_segment_counts_device': ([P, I64, I64, I64, P, I64, I64, P, P, P, P, P, P, SZ, P], I32),

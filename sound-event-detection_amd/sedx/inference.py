@@ -9,6 +9,12 @@ extraction.  All compute goes through libsedx.
                      of every clip in ONE native batch, GPU merge at
                      int(100 * overlap_value) frames + the avg_merge divisor
                      schedule (utils/utilities.py:405-446).
+ - predict_windows_ragged / predict_files   predict.py's loop over the files
+                     of a directory (pytorch/predict.py:264-407): recordings
+                     of DIFFERENT lengths, the windows of all of them through
+                     the model together, every recording merged and
+                     thresholded on its own (bit-identical to one
+                     predict_windows call per recording).
  - window_starts / merge_host   the same loop control and merge on the host
                      (no GPU), for checks and host-side callers.
  - predict_windows_vote   inference_prob_vote (pytorch/main_strong.py:1058-1097):
@@ -168,6 +174,113 @@ def predict_windows_vote(model, audio, sample_duration, overlap_value, bin_thres
     return _windows(model, audio, spec, bin_threshold)
 
 
+DEFAULT_WINDOWS_PER_FORWARD = 256   # the ragged driver's chunk (DESIGN.md §4 "Ragged windowed driver")
+
+
+def _i64(values):
+    return np.ascontiguousarray(np.asarray(values, dtype=np.int64).reshape(-1))
+
+
+def _durations(audio_durations, n_clips):
+    if audio_durations is None:
+        return None, None
+    d = np.ascontiguousarray([0.0 if v is None else float(v) for v in audio_durations], dtype=np.float64)
+    if d.shape[0] != n_clips:
+        raise ValueError('audio_durations: one entry per clip (%d), got %d' % (n_clips, d.shape[0]))
+    return d, d.ctypes.data_as(ctypes.c_void_p)
+
+
+def ragged_window_geometry(model, lengths, sample_duration=5, overlap_value=1.0, overlap=True,
+                           audio_durations=None):
+    """(windows per clip [n_clips], frame_off [n_clips + 1], samples per window)
+    of one predict_windows_ragged call over clips of ``lengths`` samples
+    (sedx_ragged_window_geometry): clip c's merged rows are
+    frame_off[c] .. frame_off[c + 1].  Raises, naming the clip's index, when
+    a clip cannot run (shorter than one window, ...)."""
+    nat = model.native(torch.device('cuda', torch.cuda.current_device()))
+    spec = _lib.window_spec(sample_duration, overlap_value, 'predict', overlap, None)
+    lens = _i64(lengths)
+    n = lens.shape[0]
+    _, dptr = _durations(audio_durations, n)
+    nw = np.zeros(max(n, 1), np.int64)
+    foff = np.zeros(n + 1, np.int64)
+    wsamp, total = ctypes.c_int64(), ctypes.c_int64()
+    _lib.check(_lib.lib().sedx_ragged_window_geometry(
+        nat.h, lens.ctypes.data_as(ctypes.c_void_p), n, ctypes.byref(spec), dptr,
+        nw.ctypes.data_as(ctypes.c_void_p), foff.ctypes.data_as(ctypes.c_void_p), ctypes.byref(wsamp),
+        ctypes.byref(total)), nat.h, 'ragged_window_geometry')
+    return nw[:n].tolist(), foff.tolist(), wsamp.value
+
+
+def _ragged_input(clips):
+    """(concatenated float32 HIP tensor, lengths) of a list of 1-D HIP tensors or a (concatenated, lengths) pair."""
+    if isinstance(clips, tuple) and len(clips) == 2 and isinstance(clips[0], torch.Tensor) and clips[0].dim() == 1 \
+            and not isinstance(clips[1], torch.Tensor):
+        cat, lengths = clips[0], [int(v) for v in clips[1]]
+    else:
+        clips = list(clips)
+        if not clips:
+            raise ValueError('predict_windows_ragged: no clips')
+        if any(c.dim() != 1 for c in clips):
+            raise ValueError('predict_windows_ragged: every clip is a 1-D tensor')
+        lengths = [int(c.shape[0]) for c in clips]
+        cat = torch.cat([c.to(torch.float32) for c in clips]) if len(clips) > 1 else clips[0]
+    if cat.device.type != 'cuda':
+        raise RuntimeError('windowed inference needs a HIP tensor (no CPU fallback)')
+    cat = cat.to(torch.float32).contiguous()
+    if cat.data_ptr() % 8:
+        cat = cat.clone()   # a view at an odd sample of a larger buffer: the frontend's 8-byte loads want the base aligned
+    if sum(lengths) != cat.shape[0] or min(lengths) < 0:
+        raise ValueError('predict_windows_ragged: the lengths do not add up to the concatenated samples')
+    return cat, lengths
+
+
+def predict_windows_ragged(model, clips, sample_duration=5, overlap_value=1.0, overlap=True, audio_durations=None,
+                           max_windows_per_forward=None):
+    """predict.py's windowed inference (pytorch/predict.py:297-349) of
+    recordings of DIFFERENT lengths in one native call
+    (sedx_forward_windows_ragged).  ``clips``: a list of 1-D HIP tensors, or
+    (concatenated 1-D HIP tensor, lengths).  The windows of all clips run
+    through the model together, at most ``max_windows_per_forward`` per
+    forward (None: all at once); every clip is merged and averaged on its
+    own.  Returns a list of [N_i, classes] views of one buffer: clip i's
+    merged framewise predictions, bit for bit predict_windows(clip i)[0].
+
+    audio_durations   per-clip loop bounds in seconds (librosa.get_duration
+                      of each file); default: each clip's length / sample_rate.
+    A clip shorter than one window is refused (RuntimeError naming its index)."""
+    if model.training:
+        raise RuntimeError('call model.eval() first')
+    x, lengths = _ragged_input(clips)
+    n = len(lengths)
+    nat = model.native(x.device)
+    L = _lib.lib()
+    spec = _lib.window_spec(sample_duration, overlap_value, 'predict', overlap, None)
+    lens = _i64(lengths)
+    off = np.zeros(n + 1, np.int64)
+    np.cumsum(lens, out=off[1:])
+    _, dptr = _durations(audio_durations, n)
+    foff = np.zeros(n + 1, np.int64)
+    lens_p, off_p = lens.ctypes.data_as(ctypes.c_void_p), off.ctypes.data_as(ctypes.c_void_p)
+    _lib.check(L.sedx_ragged_window_geometry(nat.h, lens_p, n, ctypes.byref(spec), dptr, None,
+                                             foff.ctypes.data_as(ctypes.c_void_p), None, None),
+               nat.h, 'ragged_window_geometry')
+    per = int(max_windows_per_forward) if max_windows_per_forward else 0
+    wsz = ctypes.c_size_t()
+    _lib.check(L.sedx_ragged_window_workspace_size(nat.h, lens_p, n, ctypes.byref(spec), dptr, per,
+                                                   ctypes.byref(wsz)), nat.h, 'ragged_window_workspace_size')
+    ws = torch.empty(wsz.value, dtype=torch.uint8, device=x.device)
+    merged = torch.empty((int(foff[n]), model.classes_num), dtype=torch.float32, device=x.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    _lib.check(L.sedx_forward_windows_ragged(nat.h, _ptr(x), off_p, n, ctypes.byref(spec), dptr, per, _ptr(merged),
+                                             _ptr(ws), wsz.value, stream), nat.h, 'forward_windows_ragged')
+    # as _windows: the batch is complete once the stream is, and a GRU hand-off
+    # that timed out inside it raises here
+    torch.cuda.current_stream(x.device).synchronize()
+    model.check_error()
+    return [merged[int(foff[c]):int(foff[c + 1])] for c in range(n)]
+
+
 def gamma_features(model, audio):
     """audio [B, L] HIP tensor (pad_truncated to 10 s) -> [B, 64, T] model input."""
     if model.feature_type != 'gamma':
@@ -207,11 +320,70 @@ def _event_params(params, C):
     return hi, lo, use_lo, ns, nsalt
 
 
+def _ragged_framewise(x):
+    """(rows [sum N_i, C] HIP tensor, frame_off) when x is predict_windows_ragged's list of [N_i, C] tensors or
+    a (rows, frame_off) pair; else None."""
+    if isinstance(x, tuple) and len(x) == 2 and isinstance(x[0], torch.Tensor) and x[0].dim() == 2:
+        return x[0], [int(v) for v in x[1]]
+    if isinstance(x, list) and x and all(isinstance(v, torch.Tensor) and v.dim() == 2 for v in x):
+        foff = np.concatenate([[0], np.cumsum([int(v.shape[0]) for v in x])]).tolist()
+        return torch.cat(x), foff   # (one device copy of the rows, a few MB)
+    return None
+
+
+def _event_pairs_ragged(rows, frame_off, params):
+    """sedx_events_device_ragged: (clip, class, bgn, fin), frames relative to the clip."""
+    if rows.device.type != 'cuda':
+        raise RuntimeError('ragged event extraction needs a HIP tensor')
+    rows = rows.to(torch.float32).contiguous()
+    C = rows.shape[1]
+    foff = _i64(frame_off)
+    n = foff.shape[0] - 1
+    if n < 0 or foff[0] != 0 or foff[-1] != rows.shape[0]:
+        raise ValueError('frame_off must run from 0 to the number of rows')
+    hi, lo, use_lo, ns, nsalt = _event_params(params, C)
+    L = _lib.lib()
+    wsz = ctypes.c_size_t()
+    foff_p = foff.ctypes.data_as(ctypes.c_void_p)
+    _lib.check(L.sedx_events_ragged_workspace_size(foff_p, n, C, ctypes.byref(wsz)), None,
+               'events_ragged_workspace_size')
+    dev = rows.device
+    ws = torch.empty(max(wsz.value, 1), dtype=torch.uint8, device=dev)
+    info = torch.zeros(2, dtype=torch.int64, device=dev)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    cap = max(64, n * C * 4)
+    with torch.cuda.device(dev):
+        while True:
+            ev = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+            st = L.sedx_events_device_ragged(_ptr(rows), foff_p, n, C, hi.ctypes.data_as(ctypes.c_void_p),
+                                             lo.ctypes.data_as(ctypes.c_void_p), int(use_lo),
+                                             ns.ctypes.data_as(ctypes.c_void_p),
+                                             nsalt.ctypes.data_as(ctypes.c_void_p), _ptr(ev), cap, _ptr(info),
+                                             _ptr(ws), wsz.value, stream)
+            _lib.check(st, None, 'events_device_ragged')
+            total, bad = (int(v) for v in info.cpu().tolist())
+            if bad:
+                raise RuntimeError('sedx_events_device_ragged: a run begins at the last frame after the '
+                                   'find_bgn_fin_pairs quirk (the reference raises IndexError there)')
+            if total <= cap:
+                return ev[:total].cpu().numpy()
+            cap = total
+
+
 def event_pairs_device(x, params, mode=0, overlap_value=1, sample_duration=5):
     """Thresholding on the GPU (sedx_events_device): x [N, T, C] HIP tensor of
     framewise probabilities (mode 0, activity_detection) or window vote counts
     (mode 1, activity_detection_binary).  Returns int32 [n_events, 4] =
-    (clip, class, bgn, fin) in the reference's (clip, class, time) order."""
+    (clip, class, bgn, fin) in the reference's (clip, class, time) order.
+
+    x may also be predict_windows_ragged's list of [N_i, C] tensors, or
+    (rows [sum N_i, C], frame_off): clips of different lengths, mode 0 only
+    (sedx_events_device_ragged), frames relative to each clip."""
+    rag = _ragged_framewise(x)
+    if rag is not None:
+        if mode != 0:
+            raise ValueError('clips of different lengths: mode 0 (activity_detection) only')
+        return _event_pairs_ragged(rag[0], rag[1], params)
     if x.device.type != 'cuda':
         raise RuntimeError('event_pairs_device needs a HIP tensor')
     x = x.to(torch.float32).contiguous()
@@ -247,8 +419,10 @@ def event_pairs_device(x, params, mode=0, overlap_value=1, sample_duration=5):
 def event_pairs(framewise, params):
     """activity_detection over every (clip, class): on the GPU for a HIP tensor
     (sedx_events_device), else the host C++ path (sedx_events).  framewise
-    [N, T, C].  Returns int32 array [n_events, 4] = (clip, class, bgn, fin)."""
-    if isinstance(framewise, torch.Tensor) and framewise.device.type == 'cuda':
+    [N, T, C], or clips of different lengths as event_pairs_device takes them
+    (HIP tensors only).  Returns int32 array [n_events, 4] = (clip, class, bgn, fin)."""
+    if (isinstance(framewise, torch.Tensor) and framewise.device.type == 'cuda') or \
+            _ragged_framewise(framewise) is not None:
         return event_pairs_device(framewise, params, mode=0)
     fw = framewise.detach().cpu().numpy() if isinstance(framewise, torch.Tensor) else np.asarray(framewise)
     fw = np.ascontiguousarray(fw, dtype=np.float32)
@@ -289,7 +463,9 @@ def events_from_framewise(framewise, params, audio_name='test', frames_per_secon
                           labels=LABELS, sort=True):
     """List of {'filename','onset','offset','event_label'} exactly like
     frame_prediction_to_event_prediction_v2 (+ the stable onset sort of
-    predict.py:353; main_strong.py:834 does not sort: sort=False)."""
+    predict.py:353; main_strong.py:834 does not sort: sort=False).  For clips
+    of different lengths (predict_windows_ragged's list, or (rows,
+    frame_off)) ``audio_name`` is a list with one name per clip."""
     return _to_events(event_pairs(framewise, params), audio_name, frames_per_second, labels, sort)
 
 
@@ -385,6 +561,75 @@ def inference_prob(model, waveforms, batch_size=32, device=None):
             outs['framewise_output'].append(o['framewise_output'].cpu().numpy())
             model.check_error()     # the batch is complete: an asynchronous failure surfaces here
     return {k: np.concatenate(v, axis=0) for k, v in outs.items()}
+
+
+def predict_files(model, paths, params=DEFAULT_PREDICT_PARAMS, sample_duration=5, overlap=True, overlap_value=1.0,
+                  out_dir=None, max_windows_per_forward=DEFAULT_WINDOWS_PER_FORWARD):
+    """predict.py's directory loop (pytorch/predict.py:264-407) over WAV files
+    of any duration: every file is loaded with ``audio.load(path,
+    sr=model.sample_rate)``, the windows of ALL files run through the model in
+    one predict_windows_ragged call (loop bounds from the decoded lengths), one
+    ragged events call thresholds them, and with ``out_dir`` one
+    ``<name>.xml`` per file is written through write_xml (:406).
+
+    Returns {path: event list, sorted by onset as predict.py:353} (a
+    PredictedFiles dict); its ``skipped`` attribute lists the files that
+    yield no complete window.  Deviation from the reference: such files (fewer
+    samples than one window of sample_duration s, an empty or unreadable
+    file) are reported in ``skipped`` and do not abort the batch.  The
+    reference raises on an empty file and stops; a file shorter than one
+    window it runs as a single zero-padded window, which the ragged driver
+    refuses: run such a file through predict_windows on its own."""
+    import os
+    from . import audio
+    dev = next(model.parameters()).device
+    sr = model.sample_rate
+    need = int(sample_duration) * sr
+    out = PredictedFiles()
+    kept, clips = [], []
+    for p in paths:
+        try:
+            y, _ = audio.load(p, sr=sr, device=dev)
+        except RuntimeError:
+            y = None   # not a WAV file the loader reads
+        if y is None or y.shape[0] < need:
+            out.skipped.append(p)
+            continue
+        kept.append(p)
+        clips.append(y)
+    if not kept:
+        return out
+    with torch.no_grad():
+        merged = predict_windows_ragged(model, clips, sample_duration, overlap_value, overlap, None,
+                                        max_windows_per_forward)
+    pairs = event_pairs_device(merged, params, mode=0)
+    per_clip = [[] for _ in kept]
+    for row in pairs.tolist():
+        per_clip[row[0]].append(row)
+    stride = 1 if overlap else int(sample_duration)
+    n_windows = ragged_window_geometry(model, [int(y.shape[0]) for y in clips], sample_duration, overlap_value,
+                                       overlap)[0]
+    for c, p in enumerate(kept):
+        ev = _to_events(np.asarray(per_clip[c], dtype=np.int64).reshape(-1, 4), [p] * len(kept), FRAMES_PER_SECOND,
+                        LABELS, True)
+        out[p] = ev
+        if out_dir is not None:
+            # the loop's start after the last window and predict.py:355-358's end (the "Others" segment)
+            duration = clips[c].shape[0] / float(sr)
+            start = n_windows[c] * stride
+            end = duration if duration < start + sample_duration else start + sample_duration
+            name = p.split('/')[-1].split('.wav')[0]
+            with open(os.path.join(out_dir, name + '.xml'), 'w') as f:
+                f.write(write_xml(p, ev, start, end))
+    return out
+
+
+class PredictedFiles(dict):
+    """predict_files' result: {path: events}; ``skipped``: the files that yield no window."""
+
+    def __init__(self):
+        super().__init__()
+        self.skipped = []
 
 
 def write_xml(audio_name, events, start=0, end=0):
