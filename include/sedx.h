@@ -395,6 +395,28 @@ typedef struct {
 } sedx_gamma_layout;
 sedx_status sedx_gamma_workspace_layout(const sedx_handle* h, int64_t B, int64_t L, sedx_gamma_layout* out);
 
+/* One call from audio, whatever the model's features.  On a log-mel handle
+ * this is sedx_forward.  On a gamma handle the gammatone frontend runs inside
+ * the forward: d_audio [B, L] (pad_truncate'd clips, L >= nfft) -> float64
+ * spectrum, ERB product and dB as in sedx_gamma_features, then a quantiser
+ * that writes the conv input directly (the int16 quantisation followed by bn0;
+ * no [B, 64, T] feature tensor), then the model.  The three outputs equal
+ * sedx_gamma_features + sedx_forward_features on the same clips bit for bit.
+ * The frontend is timed stage 0 and runs ahead of sedx_set_pipelined's wait,
+ * so on a pipelined handle batch i + 1's features overlap batch i's conv
+ * stack.  B <= 65535 on a gamma handle.
+ *   sedx_audio_geometry        T frames, out_frames, seq_len of L samples
+ *                              (any of the three may be NULL)
+ *   sedx_audio_workspace_size  the model workspace plus, on a gamma handle,
+ *                              the frontend's mag / db / mm for B items
+ * Both queries reject exactly what the forward rejects. */
+sedx_status sedx_forward_audio(sedx_handle* h, const float* d_audio, int64_t B, int64_t L,
+                               float* d_framewise, float* d_clipwise, float* d_embedding,
+                               void* d_workspace, size_t workspace_bytes, void* stream);
+sedx_status sedx_audio_geometry(const sedx_handle* h, int64_t L, int64_t* T, int64_t* out_frames,
+                                int64_t* seq_len);
+sedx_status sedx_audio_workspace_size(const sedx_handle* h, int64_t B, int64_t L, size_t* bytes);
+
 /* Windowed drivers: pytorch/predict.py:297-349 (`predict`) and
  * pytorch/main_strong.py:786-835 (`inference_prob_overlap`) / :1052-1100
  * (`inference_prob_vote`).  The reference's loops take three independent
@@ -415,7 +437,16 @@ sedx_status sedx_gamma_workspace_layout(const sedx_handle* h, int64_t B, int64_t
  * main_strong pad_truncate's the whole clip to 10 s (:790) and feeds each
  * window as sliced, so a window that runs past 10 s is SHORTER (its own
  * forward, fewer frames; the merge then follows numpy's slicing and
- * broadcasting exactly, raising SEDX_EINVAL where numpy raises). */
+ * broadcasting exactly, raising SEDX_EINVAL where numpy raises).
+ *
+ * On a gamma handle (the reference's predict.py raises on one; its features
+ * are made per clip when the HDF5 files are packed, utils/features.py:356-370)
+ * every driver below treats a window as that packing treats a clip: the
+ * window's samples, zero-padded to its length where the clip ends, go through
+ * fft_gtgram (T = 1 + (len - nfft) / hop un-centred frames), power_to_db
+ * (top_db 80) and the int16 quantisation by the WINDOW's own max |dB|, inside
+ * the forward (sedx_forward_audio's frontend, one item per window).  A window
+ * shorter than nfft samples is refused. */
 typedef enum { SEDX_DRIVER_PREDICT = 0, SEDX_DRIVER_MAIN_STRONG = 1 } sedx_window_driver;
 typedef struct {
   int32_t driver;           /* sedx_window_driver */

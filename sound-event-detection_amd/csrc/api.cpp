@@ -268,6 +268,42 @@ void run_logmel(sedx_handle* h, const ForwardPlan& p, float* ws, const float* au
   launch_logmel(f, h->cfg.window_size, s);
 }
 
+// the gammatone frontend of plan p's items into its X0 (launch_gamma_items): items of sig_len samples, mapped
+// onto the clips' audio as run_logmel's are; fe: the frontend's regions (gamma_layout for p.B items).
+// even_bases: the host knows every item's first sample to be at an even offset
+sedx_status run_gamma_items(sedx_handle* h, const ForwardPlan& p, float* ws, char* fe, const float* audio,
+                            int64_t clip_stride, int n_win, const int64_t* win_start, int64_t clip_len,
+                            int64_t sig_len, bool even_bases, hipStream_t s, const ItemRow* item_tab = nullptr) {
+  if (p.B > 65535) return fail(h, SEDX_EINVAL, "forward too large: %lld items (the gammatone frontend runs at most 65535)",
+                               (long long)p.B);
+  const GammaLayout lay = gamma_layout(p.B, sig_len, h->g_nfft, h->g_hop);
+  if (lay.T != p.g.T) return fail(h, SEDX_ESTATE, "the gammatone frontend's frames (%lld) are not the plan's (%lld)",
+                                  (long long)lay.T, (long long)p.g.T);
+  GammaItemParams g{};
+  g.audio = audio;
+  g.L = sig_len;
+  g.B = (int32_t)p.B;
+  g.T = (int32_t)lay.T;
+  g.T_fill = (int32_t)lay.T_fill;
+  g.hop = h->g_hop;
+  g.nfft = h->g_nfft;
+  g.kp = lay.kp;
+  g.twiddle = reinterpret_cast<const double2*>(h->w.g_twiddle);
+  g.window = h->w.g_window;
+  g.weightsT = h->w.g_weightsT;
+  g.mag = reinterpret_cast<double*>(fe + lay.mag_off);
+  g.db = reinterpret_cast<double*>(fe + lay.db_off);
+  g.mm = reinterpret_cast<unsigned long long*>(fe + lay.mm_off);
+  g.out = nullptr;
+  g.item_tab = item_tab;
+  g.win_start = win_start;
+  g.clip_stride = clip_stride;
+  g.clip_len = clip_len;
+  g.n_win = n_win;
+  launch_gamma_items(g, even_bases, h->tune.gamma_spec, h->w.bn0_scale, h->w.bn0_mean, h->w.bn0_bias, ws + p.x0.off, s);
+  return SEDX_OK;
+}
+
 // CNN + head on X0 [B][T][64] already in the workspace: every kernel choice
 // and every pointer comes from the plan
 sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_fw, float* d_clip, float* d_emb,
@@ -945,6 +981,63 @@ sedx_status sedx_gamma_workspace_layout(const sedx_handle* h, int64_t B, int64_t
   return SEDX_OK;
 }
 
+// ---- one call from audio, whatever the model's features -------------------------
+// the geometry of B clips of L samples through the model's own frontend (what sedx_forward_audio runs)
+static sedx_status audio_query(const sedx_handle* h, int64_t L, Geometry* g) {
+  char buf[96];
+  if (const char* why = audio_refusal(*h, L, buf, sizeof(buf))) return fail(h, SEDX_EINVAL, "%s", why);
+  *g = geometry_from_T(*h, audio_T(*h, L));
+  if (const char* why = shape_refusal(*h, g->T, buf, sizeof(buf))) return fail(h, SEDX_EINVAL, "%s", why);
+  return SEDX_OK;
+}
+
+sedx_status sedx_audio_geometry(const sedx_handle* h, int64_t L, int64_t* T, int64_t* out_frames, int64_t* seq_len) {
+  if (!h) return SEDX_EINVAL;
+  Geometry g;
+  if (sedx_status st = audio_query(h, L, &g)) return st;
+  if (T) *T = g.T;
+  if (out_frames) *out_frames = g.out_frames;
+  if (seq_len) *seq_len = g.Ts;
+  return SEDX_OK;
+}
+
+sedx_status sedx_audio_workspace_size(const sedx_handle* h, int64_t B, int64_t L, size_t* bytes) {
+  if (!h) return SEDX_EINVAL;
+  if (!bytes || B <= 0) return fail(h, SEDX_EINVAL, "null size pointer or empty batch");
+  Geometry g;
+  if (sedx_status st = audio_query(h, L, &g)) return st;
+  if (h->cfg.feature_type == SEDX_FEATURE_GAMMA && B > 65535)
+    return fail(h, SEDX_EINVAL, "forward too large: %lld items (the gammatone frontend runs at most 65535)", (long long)B);
+  *bytes = audio_layout(*h, h->tune, B, L).total_bytes;
+  return SEDX_OK;
+}
+
+sedx_status sedx_forward_audio(sedx_handle* h, const float* d_audio, int64_t B, int64_t L, float* d_framewise,
+                               float* d_clipwise, float* d_embedding, void* d_workspace, size_t workspace_bytes,
+                               void* stream) {
+  if (!h) return SEDX_EINVAL;
+  if (h->cfg.feature_type != SEDX_FEATURE_GAMMA)
+    return sedx_forward(h, d_audio, B, L, d_framewise, d_clipwise, d_embedding, d_workspace, workspace_bytes, stream);
+  if (sedx_status e = preflight(h)) return e;
+  if (!d_audio || !d_framewise || !d_clipwise || B <= 0) return fail(h, SEDX_EINVAL, "null pointer or empty batch");
+  Geometry g;
+  if (sedx_status st = audio_query(h, L, &g)) return st;
+  if (B > 65535 || B * g.T > INT32_MAX / 64) return fail(h, SEDX_EINVAL, "batch too large");
+  DeviceGuard dg(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const AudioLayout al = audio_layout(*h, h->tune, B, L);
+  ForwardPlan p;
+  if (const char* why = plan_forward(*h, h->tune, B, g.T, &p)) return fail(h, SEDX_EINVAL, "%s", why);
+  float* ws = nullptr;
+  if (sedx_status st = get_ws(h, al.total_bytes, d_workspace, workspace_bytes, &ws)) return st;
+  mark(h, 0, s);
+  // B items of one window each: clip b's L samples at b * L (all backed); every base is even when L is
+  if (sedx_status st = run_gamma_items(h, p, ws, reinterpret_cast<char*>(ws) + al.fe, d_audio, L, 1, nullptr, L, L,
+                                       L % 2 == 0, s))
+    return st;
+  return run_body(h, p, ws, d_framewise, d_clipwise, d_embedding, s);
+}
+
 // host-side failures of the window entry points (plan vectors) become
 // status codes instead of exceptions crossing the C ABI
 #define SEDX_HOST_TRY(h, body)                                                              \
@@ -977,8 +1070,7 @@ static sedx_status forward_windows_impl(sedx_handle* h, const float* d_audio, in
                                         const sedx_window_spec* spec, const double* h_vote_thres, float* d_merged,
                                         void* d_workspace, size_t workspace_bytes, void* stream) {
   if (sedx_status e = preflight(h)) return e;
-  if (h->cfg.feature_type != SEDX_FEATURE_LOGMEL)
-    return fail(h, SEDX_EINVAL, "windowed inference needs a logmel model");
+  const bool gamma = h->cfg.feature_type == SEDX_FEATURE_GAMMA;   // its windows go through the gammatone frontend
   if (!d_audio || !d_merged || n_clips <= 0) return fail(h, SEDX_EINVAL, "null pointer or empty batch");
   if (spec && spec->vote != 0 && h_vote_thres == nullptr)
     return fail(h, SEDX_EINVAL, "spec.vote = 1: call sedx_forward_windows_vote");
@@ -1032,7 +1124,15 @@ static sedx_status forward_windows_impl(sedx_handle* h, const float* d_audio, in
     const WinGroup& g = wg.groups[gi];
     ForwardPlan p;
     if (const char* why = plan_forward(*h, h->tune, n_clips * g.nw, g.g.T, &p)) return fail(h, SEDX_EINVAL, "%s", why);
-    run_logmel(h, p, ws, d_audio, nullptr, L_clip, n_clips, g.nw, d_start + g.w0, wg.clip_len, g.len, s);
+    if (gamma) {
+      // the one-wave spectrum kernel's 8-byte loads: clip c's window i starts at c * L_clip + start[i]
+      bool even = L_clip % 2 == 0;
+      for (int i = 0; i < g.nw; ++i) even = even && wg.loop.start[g.w0 + i] % 2 == 0;
+      if (sedx_status st = run_gamma_items(h, p, ws, reinterpret_cast<char*>(ws) + wl.fe, d_audio, L_clip, g.nw,
+                                           d_start + g.w0, wg.clip_len, g.len, even, s))
+        return st;
+    } else
+      run_logmel(h, p, ws, d_audio, nullptr, L_clip, n_clips, g.nw, d_start + g.w0, wg.clip_len, g.len, s);
     if (sedx_status st = run_body(h, p, ws, ws + wl.fw_off[gi], ws + wl.clip_off[gi], nullptr, s)) return st;
   }
   MergeArgs a{};
@@ -1149,8 +1249,7 @@ static sedx_status forward_windows_ragged_impl(sedx_handle* h, const float* d_au
                                                float* d_merged, void* d_workspace, size_t workspace_bytes,
                                                void* stream) {
   if (sedx_status e = preflight(h)) return e;
-  if (h->cfg.feature_type != SEDX_FEATURE_LOGMEL)
-    return fail(h, SEDX_EINVAL, "windowed inference needs a logmel model");
+  const bool gamma = h->cfg.feature_type == SEDX_FEATURE_GAMMA;   // its windows go through the gammatone frontend
   if (!d_audio || !d_merged || !h_clip_off || n_clips <= 0)
     return fail(h, SEDX_EINVAL, "null pointer or empty batch");
   std::vector<int64_t> len((size_t)n_clips);
@@ -1179,13 +1278,25 @@ static sedx_status forward_windows_ragged_impl(sedx_handle* h, const float* d_au
   HIP_TRY(h, hipMemcpyAsync(d_tables, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
   const ItemRow* d_item = reinterpret_cast<const ItemRow*>(d_tables + rl.t_item);
   const int64_t item_floats = rg.g.out_frames * C;
+  // (gamma) the one-wave spectrum kernel's 8-byte loads want every item's first sample at an even offset:
+  // clips of odd lengths put the clips after them at odd ones, and those calls keep the Stockham kernel
+  bool even_bases = true;
+  if (gamma) {
+    const ItemRow* rows = reinterpret_cast<const ItemRow*>(blob.data() + rl.t_item);
+    for (int64_t i = 0; i < rl.items; ++i) even_bases = even_bases && rows[i].src % 2 == 0;
+  }
   mark(h, 0, s);
   for (int64_t i0 = 0; i0 < rl.items; i0 += rl.chunk) {
     const int64_t n = std::min(rl.chunk, rl.items - i0);
     ForwardPlan p;
     if (const char* why = plan_forward(*h, h->tune, n, rg.g.T, &p)) return fail(h, SEDX_EINVAL, "%s", why);
     // n items of one window each, their sources from the item table at i0
-    run_logmel(h, p, ws, d_audio, nullptr, 0, n, 1, nullptr, rg.full_len, rg.full_len, s, d_item + i0);
+    if (gamma) {
+      if (sedx_status st = run_gamma_items(h, p, ws, reinterpret_cast<char*>(ws) + rl.fe, d_audio, 0, 1, nullptr,
+                                           rg.full_len, rg.full_len, even_bases, s, d_item + i0))
+        return st;
+    } else
+      run_logmel(h, p, ws, d_audio, nullptr, 0, n, 1, nullptr, rg.full_len, rg.full_len, s, d_item + i0);
     if (sedx_status st = run_body(h, p, ws, ws + rl.fw + i0 * item_floats, ws + rl.clipwise, nullptr, s)) return st;
   }
   RaggedMergeArgs a{};

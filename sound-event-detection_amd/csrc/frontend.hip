@@ -712,6 +712,10 @@ void launch_features_bn0(const float* feat, int B, int T, const float* bn_scale,
 // Stockham FFT in LDS, |X| rows to HBM), gamma_erb_kernel (the dense
 // 64 x (nfft/2+1) ERB product as a float64 GEMM over 64-frame tiles, dB and
 // the per-clip max / min in its epilogue), gamma_quant_kernel.
+// From raw audio inside a forward (launch_gamma_items: sedx_forward_audio, the
+// windowed drivers on a gamma handle) the same stages run over ITEMS (clip,
+// window) read in place through GammaItemParams' map, and
+// gamma_quant_x0_kernel writes the conv input X0 (quantiser + bn0) directly.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ double2 zmul(double2 a, double2 b) {
   return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
@@ -810,6 +814,27 @@ __device__ __forceinline__ double2 zreal_bin(const double2* Z, double2 twk, int 
 
 constexpr int GAMMA_SPEC_THREADS = 256;
 
+// ITEMS: the frames of item b come from the clips' audio through the item map (GammaItemParams); the kernels
+// without it are the ones sedx_gamma_features launches, unchanged
+template <bool ITEMS>
+using GammaArgs = std::conditional_t<ITEMS, GammaItemParams, GammaParams>;
+// where item b's samples start (samples from p.audio) and how many of its p.L samples are backed by audio
+__device__ __forceinline__ void gamma_item_source(const GammaItemParams& p, int64_t b, int64_t* src, int* valid) {
+  int64_t off, av;
+  if (p.item_tab) {
+    const ItemRow row = p.item_tab[b];
+    off = row.src;
+    av = row.avail;
+  } else {
+    const int64_t clip = b / p.n_win;
+    const int64_t wstart = p.win_start ? p.win_start[b - clip * p.n_win] : 0;
+    off = clip * p.clip_stride + wstart;
+    av = p.clip_len - wstart;
+  }
+  *src = off;
+  *valid = av > p.L ? (int)p.L : av > 0 ? (int)av : 0;   // (the host checks L < 2^31)
+}
+
 template <int NFFT>
 constexpr size_t gamma_spec_lds() {   // the two FFT buffers
   return (size_t)NFFT * sizeof(double2);
@@ -821,8 +846,8 @@ constexpr size_t gamma_spec_lds() {   // the two FFT buffers
 // the whole launch (LDS holds only the FFT buffers: several workgroups per
 // CU), and the next frame's samples are loaded while the current frame is
 // transformed.
-template <int NFFT>
-__global__ __launch_bounds__(GAMMA_SPEC_THREADS) void gamma_spec_kernel(GammaParams p) {
+template <int NFFT, bool ITEMS = false>
+__global__ __launch_bounds__(GAMMA_SPEC_THREADS) void gamma_spec_kernel(GammaArgs<ITEMS> p) {
   constexpr int N2 = NFFT / 2;
   constexpr int NB = N2 + 1;
   constexpr int P = GAMMA_SPEC_THREADS;
@@ -858,11 +883,32 @@ __global__ __launch_bounds__(GAMMA_SPEC_THREADS) void gamma_spec_kernel(GammaPar
       for (int i = 0; i < PER; ++i) v[i] = make_float2(0.f, 0.f);
       return;
     }
+    if constexpr (ITEMS) {
+      int64_t off;
+      int valid;
+      gamma_item_source(p, b, &off, &valid);
+      const int pos = t * p.hop;                       // < L
+      const float* src = p.audio + off + pos;
+      if (pos + NFFT > valid) {                        // the frame runs into pad_truncate's zeros
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+          const int j = pos + 2 * (tid + P * i);
+          v[i] = make_float2(j < valid ? src[j - pos] : 0.f, j + 1 < valid ? src[j + 1 - pos] : 0.f);
+        }
+        return;
+      }
+#pragma unroll
+      for (int i = 0; i < PER; ++i) {
+        const int m = tid + P * i;
+        v[i] = make_float2(src[2 * m], src[2 * m + 1]);
+      }
+    } else {
     const float* src = p.audio + b * p.L + (int64_t)t * p.hop;
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
       const int m = tid + P * i;
       v[i] = make_float2(src[2 * m], src[2 * m + 1]);
+    }
     }
   };
   float2 v[PER];
@@ -971,7 +1017,8 @@ __device__ __forceinline__ void zdft16(double2 (&v)[16], const double2 (&w16)[10
 
 constexpr int GSW_WAVES = 4;                 // waves (frames in flight) per workgroup
 constexpr int GSW_LD = 1024 + 64 + 16;       // complex per wave buffer (padded layouts below)
-__global__ __launch_bounds__(64 * GSW_WAVES, 1) void gamma_spec_wave_kernel(GammaParams p) {
+template <bool ITEMS = false>
+__global__ __launch_bounds__(64 * GSW_WAVES, 1) void gamma_spec_wave_kernel(GammaArgs<ITEMS> p) {
   extern __shared__ double2 s_gsw[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   double2* buf = s_gsw + wave * GSW_LD;
@@ -999,9 +1046,28 @@ __global__ __launch_bounds__(64 * GSW_WAVES, 1) void gamma_spec_wave_kernel(Gamm
       for (int j = 0; j < 16; ++j) v[j] = make_float2(0.f, 0.f);
       return;
     }
+    if constexpr (ITEMS) {
+      int64_t off;
+      int valid;
+      gamma_item_source(p, b, &off, &valid);
+      const int pos = t * p.hop;
+      const float* sp = p.audio + off + pos;           // even offset: the launcher's even_bases, hop even
+      if (pos + 2048 > valid) {                        // the frame runs into pad_truncate's zeros
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          const int q = pos + 2 * (lane + 64 * j);
+          v[j] = make_float2(q < valid ? sp[q - pos] : 0.f, q + 1 < valid ? sp[q + 1 - pos] : 0.f);
+        }
+        return;
+      }
+      const float2* src = reinterpret_cast<const float2*>(sp);
+#pragma unroll
+      for (int j = 0; j < 16; ++j) v[j] = src[lane + 64 * j];
+    } else {
     const float2* src = reinterpret_cast<const float2*>(p.audio + b * p.L + (int64_t)t * p.hop);
 #pragma unroll
     for (int j = 0; j < 16; ++j) v[j] = src[lane + 64 * j];
+    }
   };
   float2 xs[16];
   int64_t fr = (int64_t)blockIdx.x * GSW_WAVES + wave;
@@ -1232,38 +1298,93 @@ __global__ __launch_bounds__(256) void gamma_quant_kernel(GammaParams p) {
   }
 }
 
-template <int NFFT>
-static void launch_gamma_spec(const GammaParams& p, hipStream_t s) {
-  const void* k = reinterpret_cast<const void*>(gamma_spec_kernel<NFFT>);
+// the quantiser with bn0 as its epilogue (the item path): gamma_quant_kernel's arithmetic on a tile of 64
+// channels x 64 frames of item b, then features_bn0_kernel's, through the same LDS transpose, so db's frame-major
+// reads and X0's channel-major rows are both coalesced.  x0 [B][T][64]
+__global__ __launch_bounds__(256) void gamma_quant_x0_kernel(GammaParams p, const float* sc, const float* mu,
+                                                             const float* bi, float* x0) {
+  __shared__ float tile[64][65];
+  const int64_t b = blockIdx.y;
+  const int t0 = blockIdx.x * 64;
+  const double mx = ord2d(p.mm[2 * b]);
+  const double mn = ord2d(p.mm[2 * b + 1]);
+  const double floor_db = mx - 80.0;                 // log_spec.max() - top_db
+  const double lo = fmax(mn, floor_db);
+  const double maxabs = fmax(fabs(mx), fabs(lo));    // np.max(np.abs(x)) after the clamp
+  for (int i = threadIdx.x; i < 64 * 64; i += 256) {
+    const int m = i >> 6, tt = i & 63;
+    const int t = t0 + tt;
+    float v = 0.0f;
+    if (t < p.T) {
+      double x = fmax(p.db[(b * 64 + m) * p.T + t], floor_db);
+      if (maxabs > 1.0) x = x / maxabs;
+      const double q = trunc(x * 32767.0) + 0.0;     // (gamma_quant_kernel: no negative zero)
+      v = (float)(q / 32767.0);
+    }
+    tile[m][tt] = v;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 64 * 64; i += 256) {
+    const int tt = i >> 6, m = i & 63;
+    const int t = t0 + tt;
+    if (t < p.T) x0[(b * p.T + t) * 64 + m] = (tile[m][tt] - mu[m]) * sc[m] + bi[m];
+  }
+}
+
+template <int NFFT, bool ITEMS = false>
+static void launch_gamma_spec(const GammaArgs<ITEMS>& p, hipStream_t s) {
+  const void* k = reinterpret_cast<const void*>(gamma_spec_kernel<NFFT, ITEMS>);
   const LaunchInfo li = launch_info(k, GAMMA_SPEC_THREADS, gamma_spec_lds<NFFT>());
   if (!li.ok) return;
   const int64_t total = (int64_t)p.B * p.T;
   int64_t blocks = std::min<int64_t>(total, (int64_t)li.ncu * li.per_cu * 4);
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(gamma_spec_kernel<NFFT>, dim3((unsigned)blocks), dim3(GAMMA_SPEC_THREADS), li.dyn, s, p);
+  hipLaunchKernelGGL((gamma_spec_kernel<NFFT, ITEMS>), dim3((unsigned)blocks), dim3(GAMMA_SPEC_THREADS), li.dyn, s, p);
+}
+
+// the spectrum launch of either form; wave: the one-wave kernel may run (nfft 2048, float2 sample loads)
+template <bool ITEMS>
+static bool launch_gamma_spectrum(const GammaArgs<ITEMS>& p, bool wave, hipStream_t s) {
+  if (p.nfft == 2048 && wave) {
+    const void* k = reinterpret_cast<const void*>(gamma_spec_wave_kernel<ITEMS>);
+    const size_t lds = (size_t)GSW_WAVES * GSW_LD * sizeof(double2);
+    const LaunchInfo li = launch_info(k, 64 * GSW_WAVES, lds);
+    if (!li.ok) return false;
+    const int64_t frames = (int64_t)p.B * p.T;
+    int64_t blocks = std::min<int64_t>((frames + GSW_WAVES - 1) / GSW_WAVES, (int64_t)li.ncu * li.per_cu);
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(gamma_spec_wave_kernel<ITEMS>, dim3((unsigned)blocks), dim3(64 * GSW_WAVES), li.dyn, s, p);
+  } else if (p.nfft == 2048)
+    launch_gamma_spec<2048, ITEMS>(p, s);
+  else if (p.nfft == 1024)
+    launch_gamma_spec<1024, ITEMS>(p, s);
+  else if (p.nfft == 512)
+    launch_gamma_spec<512, ITEMS>(p, s);
+  else {
+    note_launch_error(hipErrorInvalidValue);
+    return false;
+  }
+  return true;
 }
 
 void launch_gamma(const GammaParams& p, hipStream_t s, int spec_variant) {
   hipLaunchKernelGGL(gamma_init_kernel, dim3((p.B + 255) / 256), dim3(256), 0, s, p.mm, p.B);
-  if (p.nfft == 2048 && spec_variant == 1 && p.L % 2 == 0 && p.hop % 2 == 0) {   // float2 sample loads
-    const void* k = reinterpret_cast<const void*>(gamma_spec_wave_kernel);
-    const size_t lds = (size_t)GSW_WAVES * GSW_LD * sizeof(double2);
-    const LaunchInfo li = launch_info(k, 64 * GSW_WAVES, lds);
-    if (!li.ok) return;
-    const int64_t frames = (int64_t)p.B * p.T;
-    int64_t blocks = std::min<int64_t>((frames + GSW_WAVES - 1) / GSW_WAVES, (int64_t)li.ncu * li.per_cu);
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(gamma_spec_wave_kernel, dim3((unsigned)blocks), dim3(64 * GSW_WAVES), li.dyn, s, p);
-  } else if (p.nfft == 2048)
-    launch_gamma_spec<2048>(p, s);
-  else if (p.nfft == 1024)
-    launch_gamma_spec<1024>(p, s);
-  else if (p.nfft == 512)
-    launch_gamma_spec<512>(p, s);
-  else
-    return note_launch_error(hipErrorInvalidValue);
+  if (!launch_gamma_spectrum<false>(p, spec_variant == 1 && p.L % 2 == 0 && p.hop % 2 == 0, s)) return;   // float2 sample loads
   hipLaunchKernelGGL(gamma_erb_kernel, dim3((p.T + ERB_TF - 1) / ERB_TF, p.B), dim3(256), 0, s, p);
   hipLaunchKernelGGL(gamma_quant_kernel, dim3(2048), dim3(256), 0, s, p);
+}
+
+void launch_gamma_items(const GammaItemParams& p, bool even_bases, int spec_variant, const float* bn_scale,
+                        const float* bn_mean, const float* bn_bias, float* x0, hipStream_t s) {
+  if (p.B < 1 || p.B > 65535 || p.L >= (int64_t)1 << 31 || p.n_win < 1) return note_launch_error(hipErrorInvalidValue);
+  hipLaunchKernelGGL(gamma_init_kernel, dim3((p.B + 255) / 256), dim3(256), 0, s, p.mm, p.B);
+  // a base at an odd sample (ragged clips of odd lengths) keeps the Stockham kernel's 4-byte loads
+  const bool wave = spec_variant == 1 && even_bases && p.hop % 2 == 0 && (reinterpret_cast<uintptr_t>(p.audio) & 7) == 0;
+  if (!launch_gamma_spectrum<true>(p, wave, s)) return;
+  const GammaParams& g = p;   // mag / db / mm are per item: the ERB product as it is
+  hipLaunchKernelGGL(gamma_erb_kernel, dim3((p.T + ERB_TF - 1) / ERB_TF, p.B), dim3(256), 0, s, g);
+  hipLaunchKernelGGL(gamma_quant_x0_kernel, dim3((p.T + 63) / 64, p.B), dim3(256), 0, s, g, bn_scale, bn_mean, bn_bias,
+                     x0);
 }
 
 }  // namespace sedx

@@ -54,6 +54,52 @@ namespace {
 Region take(size_t& end, size_t floats) { return Region{carve(end, floats * 4) / 4, floats}; }
 }  // namespace
 
+// ---- a gamma model's own frontend ---------------------------------------------
+int64_t audio_T(const Model& m, int64_t L) {
+  if (m.cfg.feature_type != SEDX_FEATURE_GAMMA) return conv_T(m, L);
+  GammaGeom gg;
+  gamma_geometry(m.cfg.sample_rate, m.cfg.window_size, m.cfg.hop_size, &gg);
+  return L < gg.nfft || gg.hop < 1 ? 0 : 1 + (L - gg.nfft) / gg.hop;
+}
+
+const char* audio_refusal(const Model& m, int64_t L, char* buf, size_t n) {
+  if (m.cfg.feature_type == SEDX_FEATURE_GAMMA) {
+    GammaGeom gg;
+    gamma_geometry(m.cfg.sample_rate, m.cfg.window_size, m.cfg.hop_size, &gg);
+    if (L >= gg.nfft) return nullptr;
+    snprintf(buf, n, "input of %lld samples is shorter than the gammatone FFT (%d)", (long long)L, gg.nfft);
+    return buf;
+  }
+  // STFT reflect padding needs more than n_fft / 2 samples (stft.py:237)
+  if (L > m.cfg.window_size / 2) return nullptr;
+  snprintf(buf, n, "input of %lld samples is too short for reflect padding of %d", (long long)L, m.cfg.window_size / 2);
+  return buf;
+}
+
+size_t frontend_bytes(const Model& m, int64_t items, int64_t L) {
+  if (m.cfg.feature_type != SEDX_FEATURE_GAMMA) return 0;
+  GammaGeom gg;
+  gamma_geometry(m.cfg.sample_rate, m.cfg.window_size, m.cfg.hop_size, &gg);
+  if (items < 1 || L < gg.nfft || gg.hop < 1) return 0;
+  return gamma_layout(items, L, gg.nfft, gg.hop).total_bytes;
+}
+
+AudioLayout audio_layout(const Model& m, const Tuning& t, int64_t B, int64_t L) {
+  AudioLayout l;
+  ForwardPlan fp;
+  plan_forward(m, t, B, audio_T(m, L), &fp);
+  l.model_bytes = fp.total_bytes;
+  l.fe_bytes = frontend_bytes(m, B, L);
+  if (!l.fe_bytes) {   // a log-mel model: the forward's own workspace
+    l.total_bytes = l.model_bytes;
+    return l;
+  }
+  size_t end = align256(l.model_bytes);
+  l.fe = carve(end, l.fe_bytes);
+  l.total_bytes = end;
+  return l;
+}
+
 const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, ForwardPlan* p) {
   const Geometry g = geometry_from_T(m, T);
   p->g = g;
@@ -415,11 +461,19 @@ const char* window_geometry(const Model& m, int64_t L_clip, const sedx_window_sp
   wg->clip_len = spec->driver == SEDX_DRIVER_MAIN_STRONG ? std::min<int64_t>(L_clip, (int64_t)sr * 10) : L_clip;
   wg->groups.clear();
   std::vector<int64_t> frames(wg->n_win);
+  const bool gamma = m.cfg.feature_type == SEDX_FEATURE_GAMMA;
   for (int w = 0; w < wg->n_win; ++w) {
     const int64_t len = wg->loop.len[w];
+    // a gamma model's window goes through fft_gtgram like a clip (utils/features.py:356-370): un-centred frames,
+    // so it needs one whole FFT of samples
+    if (gamma && audio_T(m, len) < 1) {
+      snprintf(wg->reject, sizeof(wg->reject), "window %d has %lld samples: shorter than the gammatone FFT", w,
+               (long long)len);
+      return wg->reject;
+    }
     // the model raises on these windows: STFT reflect padding needs more
     // than n_fft/2 samples (stft.py:237); then what every forward refuses
-    if (len <= m.cfg.window_size / 2) {
+    if (!gamma && len <= m.cfg.window_size / 2) {
       snprintf(wg->reject, sizeof(wg->reject), "window %d has %lld samples: too short for the STFT's reflect padding",
                w, (long long)len);
       return wg->reject;
@@ -428,7 +482,7 @@ const char* window_geometry(const Model& m, int64_t L_clip, const sedx_window_sp
       WinGroup g;
       g.w0 = w;
       g.len = len;
-      g.g = geometry_from_T(m, conv_T(m, len));
+      g.g = geometry_from_T(m, audio_T(m, len));   // the frontend's own frame count (gamma: 1 + (len - nfft) / hop)
       char why[96];
       if (shape_refusal(m, g.g.T, why, sizeof(why))) {
         snprintf(wg->reject, sizeof(wg->reject), "window %d: %s", w, why);
@@ -454,6 +508,9 @@ WinLayout win_layout(const Model& m, const Tuning& t, int64_t n_clips, const Win
   for (const auto& g : wg.groups) l.fw_off.push_back(take(end, (size_t)n_clips * g.nw * g.g.out_frames * C).off);
   for (const auto& g : wg.groups) l.clip_off.push_back(take(end, (size_t)n_clips * g.nw * C).off);
   l.vthr = take(end, 2 * C).off;   // [C] f64
+  // a gamma model: the frontend's mag / db / mm, shared by the groups' forwards (one runs at a time)
+  for (const auto& g : wg.groups) l.fe_bytes = std::max(l.fe_bytes, frontend_bytes(m, n_clips * g.nw, g.len));
+  l.fe = carve(end, l.fe_bytes);
   l.tables = end / 4;
   size_t b = 0;
   l.t_start = carve(b, 8 * (size_t)wg.n_win);
@@ -548,6 +605,8 @@ RaggedLayout ragged_layout(const Model& m, const Tuning& t, const RaggedGeom& rg
   size_t end = l.model_bytes;
   l.fw = take(end, (size_t)l.items * rg.g.out_frames * C).off;
   l.clipwise = take(end, (size_t)l.chunk * C).off;
+  l.fe_bytes = frontend_bytes(m, l.chunk, rg.full_len);   // a gamma model: mag / db / mm of one forward's items
+  l.fe = carve(end, l.fe_bytes);
   l.tables = end / 4;
   for (const MergePlan& p : rg.plans) {
     l.n_off += (size_t)p.N + 1;

@@ -44,6 +44,11 @@ struct Geometry {
   int rep = 8;
 };
 inline int64_t conv_T(const Model& m, int64_t L) { return L / m.cfg.hop_size + 1; }
+// the frames the model's own frontend makes of L samples: conv_T (log-mel), or fft_gtgram's un-centred
+// 1 + (L - nfft) / hop on a gamma model (<= 0: L is shorter than the gammatone FFT)
+int64_t audio_T(const Model& m, int64_t L);
+// nullptr, or why no frontend runs L samples ("input of ... samples is too short for ..."; into buf)
+const char* audio_refusal(const Model& m, int64_t L, char* buf, size_t n);
 // the model's frame rule (Model::frames, weights.h) applied to T frames; it answers for shapes no forward runs too
 Geometry geometry_from_T(const Model& m, int64_t T);
 // The one rule of which shapes a model refuses, by its frame rule: nullptr, or why no forward runs T frames
@@ -155,6 +160,15 @@ struct ForwardPlan {
 // shapes no forward runs); returns why a forward rejects the shape, else nullptr.
 const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, ForwardPlan* p);
 
+// a forward from audio (sedx_forward_audio): the model workspace of B items of audio_T(L) frames, then, on a
+// gamma model, the frontend's regions (gamma_layout's mag / db / mm for B items of L samples) at fe.  A log-mel
+// model has no such regions (fe_bytes 0).  frontend_bytes: those regions' size for `items` items (0: log-mel)
+struct AudioLayout {
+  size_t model_bytes = 0, fe = 0, fe_bytes = 0, total_bytes = 0;   // fe: bytes from the workspace start
+};
+size_t frontend_bytes(const Model& m, int64_t items, int64_t L);
+AudioLayout audio_layout(const Model& m, const Tuning& t, int64_t B, int64_t L);
+
 // ---- one Winograd conv launch -----------------------------------------------
 // What launch_conv3x3_wino, launch_block1_wino and launch_conv3x3_wino43
 // launch for a layer: the item shape, the persistent grid, the item order and
@@ -253,6 +267,9 @@ struct WinLayout {
   size_t model_bytes = 0;                 // max over the groups' plans
   std::vector<size_t> fw_off, clip_off;   // per group, floats from the area start
   size_t vthr = 0, tables = 0, table_bytes = 0, total_bytes = 0;
+  // a gamma model's frontend regions (gamma_layout for the largest group's items), bytes from the area start,
+  // between the vote thresholds and the tables; a log-mel model has none (fe_bytes 0: the layout as it was)
+  size_t fe = 0, fe_bytes = 0;
   size_t t_start = 0, t_wb = 0, t_wcs = 0, t_off = 0, t_src = 0, t_div = 0;   // byte offsets in the tables
 };
 WinLayout win_layout(const Model& m, const Tuning& t, int64_t n_clips, const WinGeom& wg);
@@ -296,6 +313,7 @@ struct RaggedLayout {
   int64_t items = 0, chunk = 0;          // items per forward (the last forward runs the rest)
   size_t model_bytes = 0;
   size_t fw = 0, clipwise = 0;           // floats from the area start
+  size_t fe = 0, fe_bytes = 0;           // a gamma model's frontend regions for `chunk` items (bytes; WinLayout::fe)
   size_t tables = 0, table_bytes = 0, total_bytes = 0;   // tables: floats from the area start
   size_t t_item = 0, t_clip = 0, t_off = 0, t_src = 0, t_div = 0;   // byte offsets in the tables
   size_t n_off = 0, n_src = 0;           // entries of the concatenated off (= div) and src tables

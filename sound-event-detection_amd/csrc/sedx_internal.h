@@ -92,6 +92,26 @@ struct GammaParams {
 // spec_variant (nfft 2048): 0 the workgroup Stockham spectrum, 1 one wave per frame
 void launch_gamma(const GammaParams& p, hipStream_t s, int spec_variant = 0);
 
+// The same frontend over ITEMS (clip c, window i) read in place from the clips' audio, straight into the conv
+// input (sedx_forward_audio and the windowed drivers on a gamma handle).  B = items, L = samples of an item;
+// item b's samples start at audio + (item_tab ? item_tab[b].src : (b / n_win) * clip_stride + win_start[b % n_win])
+// and min(L, item_tab ? item_tab[b].avail : clip_len - win_start[b % n_win]) of them are backed by audio: the
+// rest up to L are pad_truncate's zeros.  mag / db / mm are per item; out is unused.
+struct GammaItemParams : GammaParams {
+  const ItemRow* item_tab;   // device [B], or nullptr: the window table below
+  const int64_t* win_start;  // device [n_win], or nullptr: every item starts at its clip's first sample
+  int64_t clip_stride;       // samples between clips
+  int64_t clip_len;          // samples backing each clip
+  int32_t n_win;             // windows per clip
+};
+// gamma_init, the spectrum (items), gamma_erb_kernel as it is, then the quantiser with bn0 as its epilogue:
+// gamma_quant_kernel's value, then launch_features_bn0's (v - mean) * scale + bias, stored as X0 [B][T][64]
+// (bit for bit launch_gamma + launch_features_bn0 on the pad_truncate'd items).  even_bases: every item's first
+// sample is at an even offset from an 8-byte aligned audio pointer (the one-wave spectrum kernel's float2
+// loads; else the Stockham kernel runs whatever spec_variant says).  B <= 65535 (the ERB grid's y).
+void launch_gamma_items(const GammaItemParams& p, bool even_bases, int spec_variant, const float* bn_scale,
+                        const float* bn_mean, const float* bn_bias, float* x0, hipStream_t s);
+
 // ---- conv stack -----------------------------------------------------------
 // bn0 output X0 [B][T][64] -> zero-bordered [B][T+2][66] (block1_pad_floats)
 void launch_pad_x0(const float* x0, int B, int T, float* xpad, hipStream_t s);

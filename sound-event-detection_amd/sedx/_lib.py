@@ -29,7 +29,8 @@ EXPORTS = ['sedx_create', 'sedx_destroy', 'sedx_last_error', 'sedx_version', 'se
            'sedx_average_precision', 'sedx_average_precision_workspace_size', 'sedx_average_precision_device',
            'sedx_rank_tile', 'sedx_gamma_workspace_layout',
            'sedx_ragged_window_geometry', 'sedx_ragged_window_workspace_size', 'sedx_forward_windows_ragged',
-           'sedx_events_ragged_workspace_size', 'sedx_events_device_ragged']
+           'sedx_events_ragged_workspace_size', 'sedx_events_device_ragged',
+           'sedx_forward_audio', 'sedx_audio_geometry', 'sedx_audio_workspace_size']
 TUNE_GRU_KERNEL, TUNE_GRU_HANDOFF, TUNE_WINO_BLOCK1, TUNE_MEL_MFMA, TUNE_GRU_SPIN, TUNE_WINO_ORDER = 0, 1, 2, 3, 4, 5
 TUNE_GAMMA_SPEC = 6
 TUNE_WINO_F43 = 7
@@ -142,6 +143,9 @@ def lib():
         'sedx_forward': ([P, P, I64, I64, P, P, P, P, SZ, P], I32),
         'sedx_forward_features': ([P, P, I64, I64, P, P, P, P, SZ, P], I32),
         'sedx_forward_i16': ([P, P, I64, I64, P, P, P, P, SZ, P], I32),
+        'sedx_forward_audio': ([P, P, I64, I64, P, P, P, P, SZ, P], I32),
+        'sedx_audio_geometry': ([P, I64, PI64, PI64, PI64], I32),
+        'sedx_audio_workspace_size': ([P, I64, I64, PSZ], I32),
         'sedx_gamma_features': ([P, P, I64, I64, P, PI64, P, SZ, P], I32),
         'sedx_gamma_workspace_size': ([P, I64, I64, PSZ], I32),
         'sedx_gamma_workspace_layout': ([P, I64, I64, ctypes.POINTER(SedxGammaLayout)], I32),

@@ -550,13 +550,15 @@ class GraphedForward:
 
 def inference_prob(model, waveforms, batch_size=32, device=None):
     """pytorch_utils.forward (pytorch/pytorch_utils.py:25-78): batched clip
-    inference; returns numpy {'clipwise_output', 'framewise_output'}."""
+    inference; returns numpy {'clipwise_output', 'framewise_output'}.  On a
+    gamma model a 2-D batch is waveforms (model.forward_audio), a 3-D one the
+    precomputed features the reference's loader hands its model."""
     device = device or torch.device('cuda', torch.cuda.current_device())
     outs = {'clipwise_output': [], 'framewise_output': []}
     with torch.no_grad():
         for i in range(0, len(waveforms), batch_size):
             x = torch.as_tensor(waveforms[i:i + batch_size], dtype=torch.float32).to(device)
-            o = model(x)
+            o = model.forward_audio(x) if getattr(model, 'feature_type', None) == 'gamma' and x.dim() == 2 else model(x)
             outs['clipwise_output'].append(o['clipwise_output'].cpu().numpy())
             outs['framewise_output'].append(o['framewise_output'].cpu().numpy())
             model.check_error()     # the batch is complete: an asynchronous failure surfaces here

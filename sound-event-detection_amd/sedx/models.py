@@ -620,6 +620,43 @@ class _SedModel(nn.Module):
             return {'framewise_output': fw, 'clipwise_output': clip}
         return {'framewise_output': fw, 'clipwise_output': clip, 'embedding': emb}
 
+    def forward_audio(self, wave):
+        """The forward from a (batch_size, data_length) float waveform,
+        whatever the model's features (sedx_forward_audio): ``forward(wave)``
+        on a log-mel model; on a gamma model the gammatone frontend runs
+        inside the forward (clips already pad_truncate'd, as for
+        ``inference.gamma_features``) and the outputs equal
+        ``forward(gamma_features(model, wave))`` bit for bit.  Eval mode only."""
+        self._check_eval(None, False)
+        if not isinstance(wave, torch.Tensor) or wave.device.type != 'cuda':
+            raise RuntimeError('sedx forward needs a tensor on a HIP device (no CPU fallback)')
+        if self.feature_type != 'gamma':
+            return self.forward(wave)
+        x = wave.to(torch.float32).contiguous()
+        if x.dim() != 2:
+            raise ValueError('input must be (batch_size, data_length)')
+        nat = self.native(x.device)
+        L = _lib.lib()
+        B, length = x.shape
+        fr, sl = ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(L.sedx_audio_geometry(nat.h, length, None, ctypes.byref(fr), ctypes.byref(sl)),
+                   nat.h, 'audio_geometry')
+        C = self.classes_num
+        dev = x.device
+        fw = torch.empty((B, fr.value, C), dtype=torch.float32, device=dev)
+        clip = torch.empty((B, C), dtype=torch.float32, device=dev)
+        emb_shape = (B, C, sl.value) if self._embedding_cla else (B, self._embedding_width, sl.value)
+        emb = torch.empty(emb_shape, dtype=torch.float32, device=dev) if self._has_embedding else None
+        wsz = ctypes.c_size_t()
+        _lib.check(L.sedx_audio_workspace_size(nat.h, B, length, ctypes.byref(wsz)), nat.h, 'audio_workspace_size')
+        ws = torch.empty(wsz.value, dtype=torch.uint8, device=dev)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(L.sedx_forward_audio(nat.h, _ptr(x), B, length, _ptr(fw), _ptr(clip), _ptr(emb), _ptr(ws),
+                                        wsz.value, stream), nat.h, 'forward_audio')
+        if emb is None:
+            return {'framewise_output': fw, 'clipwise_output': clip}
+        return {'framewise_output': fw, 'clipwise_output': clip, 'embedding': emb}
+
 
 class Cnn_9layers_Gru_FrameAtt(_SedModel):
     """pytorch/models.py:564-688."""
