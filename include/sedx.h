@@ -280,14 +280,15 @@ sedx_status sedx_workspace_size(const sedx_handle* h, int64_t B, int64_t L_or_T,
  * current precision and tuning, as the launchers decide them (read-only; no
  * launch, no output depends on any of it).  One row per launch: a batch whose
  * input passes the kernels' 32-bit offsets runs a stage as several launches of
- * whole clips.  Rows of the exact and x3 launchers carry the layer only (the
- * fields from `clips` on are 0). */
+ * whole clips.  Rows of the exact, x3 and f16 launchers carry the layer only
+ * (the fields from `clips` on are 0). */
 typedef enum sedx_conv_family {
   SEDX_CONV_EXACT = 0,
   SEDX_CONV_X3 = 1,
   SEDX_CONV_F23 = 2,         /* Winograd F(2x2,3x3) */
   SEDX_CONV_F23_BLOCK1 = 3,  /* block 1 in one F(2x2,3x3) launch (conv1 inside) */
-  SEDX_CONV_F43 = 4          /* Winograd F(4x4,3x3) */
+  SEDX_CONV_F43 = 4,         /* Winograd F(4x4,3x3) */
+  SEDX_CONV_F16 = 5          /* the fp16 matrix-pipe launcher (SEDX_PRECISION_F16); rows as the x3 launcher's */
 } sedx_conv_family;
 typedef struct sedx_conv_launch {
   int32_t stage, family;              /* 2..8 (sedx_stage_times' numbering), sedx_conv_family */
@@ -579,9 +580,37 @@ sedx_status sedx_forward_windows_ragged(sedx_handle* h, const float* d_audio, co
  *  SEDX_PRECISION_X3    opt-in: bf16 MFMA with a 3-term hi/lo operand split
  *                       (hi*hi + hi*lo + lo*hi, fp32 accumulate): operands
  *                       carry 16 significant bits, products err ~2^-16 rel.
+ *  SEDX_PRECISION_F16   opt-in, reduced precision: the conv layers that X3 runs
+ *                       on the bf16 pipe (block 1's conv2 and blocks 2-4 of the
+ *                       9-layer trunk; on the 14-layer trunk block 1's conv2
+ *                       to block 4's conv1) run on the f16 matrix pipe, one
+ *                       v_mfma_f32_32x32x16_f16 per product.  Per layer both
+ *                       operands v (the BN-folded weight after its one rounding
+ *                       to fp32, and the fp32 input activation) become q(v):
+ *                       clamped to +-65504, rounded to the nearest-even fp16
+ *                       with gradual underflow in the rounding itself, then
+ *                       every result with |q| < 2^-14 set to +0 (so the
+ *                       result does not depend on how the matrix pipe treats
+ *                       fp16 subnormals).  Products are accumulated in fp32;
+ *                       the folded-BN bias (fp32), ReLU, the 2x2 average pool
+ *                       and block 4's frequency mean are fp32.  Activations
+ *                       stay fp32 in memory, in the exact mode's layout, and
+ *                       the workspace is the exact mode's.  Everything else
+ *                       runs as in EXACT: block 1's conv1, the 14-layer
+ *                       trunk's deep layers, the VGGish trunk, the Conformer
+ *                       encoder, every sequence layer and head.  One output's
+ *                       summation order depends on neither the batch, the
+ *                       tile claim order nor the stream.  Outputs move by
+ *                       ~5e-5 against EXACT on synthetic weights (DESIGN.md
+ *                       §4, "fp16 conv stack").
  * The frontend (FFT, mel, dB), the gates, softmax and the head's
  * element-wise work are fp32 in every mode; the gammatone frontend float64. */
-typedef enum { SEDX_PRECISION_EXACT = 0, SEDX_PRECISION_X3 = 1, SEDX_PRECISION_WINOGRAD = 2 } sedx_precision;
+typedef enum {
+  SEDX_PRECISION_EXACT = 0,
+  SEDX_PRECISION_X3 = 1,
+  SEDX_PRECISION_WINOGRAD = 2,
+  SEDX_PRECISION_F16 = 3
+} sedx_precision;
 sedx_status sedx_set_precision(sedx_handle* h, int32_t mode);
 
 /* Implementation choices that leave the arithmetic's meaning unchanged (A/B

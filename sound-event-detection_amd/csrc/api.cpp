@@ -39,6 +39,7 @@ struct sedx_handle : sedx::Model {
   bool finalized = false;
   void* blob = nullptr;      // single device allocation for all packed weights
   DevWeights w;
+  F16Weights wf16;           // SEDX_PRECISION_F16's conv packs, in the same allocation
   int g_nfft = 0, g_hop = 0;   // gammatone FFT size and hop (prepare_weights)
   void* ws = nullptr;        // cached workspace
   size_t ws_bytes = 0;
@@ -332,7 +333,8 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
       case B1_CONV1_F23:
       case B1_CONV1_F43: launch_conv1_nhwc(X0, iB, (int)g.T, w.c1_w, w.c1_b, A, s); break;
       case B1_PAD_EXACT:
-      case B1_PAD_X3: launch_pad_x0(X0, iB, (int)g.T, A, s); break;
+      case B1_PAD_X3:
+      case B1_PAD_F16: launch_pad_x0(X0, iB, (int)g.T, A, s); break;
       case B1_F23_FUSED: break;   // conv1 inside the stage-2 launch
       case B1_VGG: launch_vgg_conv1(X0, iB, (int)g.T, w.c1_w, w.c1_b, A, s); break;   // conv1 + ReLU + max pool
     }
@@ -391,10 +393,14 @@ sedx_status run_body(sedx_handle* h, const ForwardPlan& p, float* ws, float* d_f
                             p.c4, 0, claim, i == 0 && p.b1_planar);
     else if (i == 0 && p.block1 == B1_PAD_X3)
       launch_block1_fused_x3(nullptr, iB, c.T, in, w.c1_wt, w.c1_b, w.wx3[k], w.cb[k], out, claim, s);
+    else if (i == 0 && p.block1 == B1_PAD_F16)
+      launch_block1_fused_f16(iB, c.T, in, w.c1_wt, w.c1_b, h->wf16.w[k], w.cb[k], out, claim, s);
     else if (i == 0)   // B1_PAD_EXACT
       launch_block1_exact(in, iB, c.T, w.c1_w, w.c1_b, w.wp[k], w.cb[k], out, w.zero, s);
     else if (p.family == CONV_X3)
       launch_conv3x3_x3(in, iB, c.T, c.F, c.cin, c.cout, w.wx3[k], w.cb[k], out, c.epi, claim, s);
+    else if (p.family == CONV_F16)
+      launch_conv3x3_f16(in, iB, c.T, c.F, c.cin, c.cout, h->wf16.w[k], w.cb[k], out, c.epi, claim, s);
     else
       launch_conv3x3(in, iB, c.T, c.F, c.cin, c.cout, w.wp[k], w.cb[k], out, c.epi, w.zero, s);
     if (h->token && i == 6) {
@@ -539,14 +545,15 @@ extern "C" {
 
 const char* sedx_version(void) {
   return "sedx 0.6 (abi 6; gfx950: fp32 MFMA exact direct conv | fp32 Winograd F(4x4,3x3) + F(2x2,3x3) | "
-         "3xbf16-split MFMA)";
+         "3xbf16-split MFMA | fp16 MFMA conv stack)";
 }
 
 int32_t sedx_abi_version(void) { return SEDX_ABI_VERSION; }
 
 sedx_status sedx_set_precision(sedx_handle* h, int32_t mode) {
   if (!h) return SEDX_EINVAL;
-  if (mode != SEDX_PRECISION_EXACT && mode != SEDX_PRECISION_X3 && mode != SEDX_PRECISION_WINOGRAD)
+  if (mode != SEDX_PRECISION_EXACT && mode != SEDX_PRECISION_X3 && mode != SEDX_PRECISION_WINOGRAD &&
+      mode != SEDX_PRECISION_F16)
     return fail(h, SEDX_EINVAL, "unknown precision mode %d", mode);
   h->tune.precision = mode;
   return SEDX_OK;
@@ -676,17 +683,20 @@ sedx_status sedx_finalize_weights(sedx_handle* h) {
   DevWeights w;
   WeightBlob blob;
   GammaGeom gg;
-  if (sedx_status st = prepare_weights(*h, h->params, &w, &blob, &gg, &h->err)) return st;
+  F16Weights wf16;
+  if (sedx_status st = prepare_weights(*h, h->params, &w, &blob, &gg, &h->err, &wf16)) return st;
   DeviceGuard dg(h->device);
   if (h->blob) {
     (void)hipFree(h->blob);
     h->blob = nullptr;
     h->w = DevWeights();
+    h->wf16 = F16Weights();
   }
   HIP_TRY(h, hipMalloc(&h->blob, blob.image.size()));
   HIP_TRY(h, hipMemcpy(h->blob, blob.image.data(), blob.image.size(), hipMemcpyHostToDevice));
-  blob.bind(h->blob);   // sets w's pointers
+  blob.bind(h->blob);   // sets w's and wf16's pointers
   h->w = w;
+  h->wf16 = wf16;
   h->g_nfft = gg.nfft;
   h->g_hop = gg.hop;
   if (!h->gru_err_host) {
@@ -796,7 +806,7 @@ sedx_status sedx_conv_launch_plan(const sedx_handle* h, int64_t B, int64_t L_or_
     const ConvLayer& c = p.layers[i];
     sedx_conv_launch r{};
     r.stage = 2 + i;
-    r.family = p.family == CONV_X3 ? SEDX_CONV_X3 : SEDX_CONV_EXACT;
+    r.family = p.family == CONV_X3 ? SEDX_CONV_X3 : p.family == CONV_F16 ? SEDX_CONV_F16 : SEDX_CONV_EXACT;
     r.T = c.T, r.F = c.F, r.cin = c.cin, r.cout = c.cout, r.epi = c.epi;
     WinoFamily wf;
     const bool wino = conv_launch_family(p, i, &wf);

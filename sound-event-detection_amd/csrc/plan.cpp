@@ -110,20 +110,23 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
   p->first_deep = m.vgg ? p->nlayers : deep ? 6 : 7;
   // ---- which kernels ----
   const bool wino = t.precision == SEDX_PRECISION_WINOGRAD, x3 = t.precision == SEDX_PRECISION_X3;
+  // fp16 conv stack: the packed layers on conv_f16.hip, everything else (sequence layer, head) as in exact
+  const bool f16 = t.precision == SEDX_PRECISION_F16;
   // Winograd block 1 (SEDX_TUNE_WINO_BLOCK1): 1 = conv1's activation
   // [B][T][64][64] into A by its own launch; 2 = conv1 inside the F(2x2,3x3)
   // launch.  F(4x4,3x3) block 1 (SEDX_TUNE_WINO_F43 2): conv1 by its own
   // launch in both (2: in the chunk-of-4 layout), then the F(4x4,3x3) conv2
   if (x3) p->block1 = B1_PAD_X3;
+  else if (f16) p->block1 = B1_PAD_F16;
   else if (!wino || t.wino_block1 == 0) p->block1 = B1_PAD_EXACT;
   else if (t.wino_f43 == 2) p->block1 = t.wino_block1 == 2 ? B1_CONV1C4_F43 : B1_CONV1_F43;
   else p->block1 = t.wino_block1 == 2 ? B1_F23_FUSED : B1_CONV1_F23;
-  p->family = x3 ? CONV_X3 : !wino ? CONV_EXACT : t.wino_f43 ? CONV_WINO43 : CONV_WINO;
+  p->family = x3 ? CONV_X3 : f16 ? CONV_F16 : !wino ? CONV_EXACT : t.wino_f43 ? CONV_WINO43 : CONV_WINO;
   p->c4 = wino && t.wino_f43 && t.wino_block1 == 2;
   // block 1's chunk-of-4 pair stays reachable for A/B: SEDX_TUNE_WINO_ORDER 3 (every launch's order as 1)
   p->b1_planar = p->block1 == B1_CONV1C4_F43 && t.wino_order != 3;
   const int wino_order = t.wino_order == 3 ? 1 : t.wino_order;
-  p->claims = x3 || (p->family == CONV_WINO43 && B >= 8);
+  p->claims = x3 || f16 || (p->family == CONV_WINO43 && B >= 8);
   // the VGGish trunk: launch_vgg_conv1, then launch_conv3x3 on every layer, in every precision mode
   if (m.vgg) p->block1 = B1_VGG, p->family = CONV_EXACT, p->c4 = false, p->b1_planar = false, p->claims = false;
   // AUTO: 16 slices (half the recurrence's serial product); on a pipelined
@@ -149,8 +152,9 @@ const char* plan_forward(const Model& m, const Tuning& t, int64_t B, int64_t T, 
   // conv stack: block 1's first launch into A, then the layers ping-pong P / A
   size_t a_conv = p->block1 == B1_VGG                                   ? (size_t)B * g.T1 * 32 * 64
                   : p->block1 == B1_F23_FUSED                           ? 0
-                  : p->block1 == B1_PAD_EXACT || p->block1 == B1_PAD_X3 ? block1_pad_floats((int)B, (int)T)
-                                                                         : (size_t)B * T * 64 * 64;
+                  : p->block1 == B1_PAD_EXACT || p->block1 == B1_PAD_X3 || p->block1 == B1_PAD_F16
+                      ? block1_pad_floats((int)B, (int)T)
+                      : (size_t)B * T * 64 * 64;
   size_t p_conv = 0;
   const int64_t Ts[4] = {g.T, g.T1, g.T2, g.T3};
   // 14-layer trunk: block 4's conv2 pools 2x2; block 5 at F = 4, block 6 at F = 2 (its conv2: the mean of 2 bins)
@@ -422,7 +426,7 @@ ConvLaunch plan_conv_launch(WinoFamily family, int ncu, int64_t B, int T, int F,
 
 bool conv_launch_family(const ForwardPlan& p, int i, WinoFamily* family) {
   if (p.block1 == B1_VGG) return false;   // launch_conv3x3 on every layer
-  const bool b1 = i == 0 && p.block1 != B1_PAD_EXACT && p.block1 != B1_PAD_X3;   // a Winograd stage 2
+  const bool b1 = i == 0 && p.block1 != B1_PAD_EXACT && p.block1 != B1_PAD_X3 && p.block1 != B1_PAD_F16;   // a Winograd stage 2
   if (b1) *family = p.block1 == B1_F23_FUSED ? WINO_F23_BLOCK1 : p.block1 == B1_CONV1_F23 ? WINO_F23 : WINO_F43;
   else *family = p.family == CONV_WINO ? WINO_F23 : WINO_F43;
   return b1 || (i > 0 && (p.family == CONV_WINO || p.family == CONV_WINO43));

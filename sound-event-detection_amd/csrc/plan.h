@@ -88,6 +88,7 @@ struct Region {
 enum Block1Form {
   B1_PAD_EXACT,     // launch_pad_x0 + launch_block1_exact (exact; Winograd with SEDX_TUNE_WINO_BLOCK1 0)
   B1_PAD_X3,        // launch_pad_x0 + launch_block1_fused_x3
+  B1_PAD_F16,       // launch_pad_x0 + launch_block1_fused_f16 (conv1 in fp32 inside conv2's halo staging)
   B1_F23_FUSED,     // launch_block1_wino: conv1 inside the F(2x2,3x3) launch
   B1_CONV1_F23,     // launch_conv1_nhwc + launch_conv3x3_wino
   B1_CONV1_F43,     // launch_conv1_nhwc + launch_conv3x3_wino43
@@ -96,7 +97,7 @@ enum Block1Form {
   B1_CONV1C4_F43,
   B1_VGG,           // launch_vgg_conv1 (conv 1 -> 64 + bias + ReLU + 2x2 max pool), then launch_conv3x3 on conv2
 };
-enum ConvFamily { CONV_EXACT, CONV_X3, CONV_WINO, CONV_WINO43 };   // layers 2-7
+enum ConvFamily { CONV_EXACT, CONV_X3, CONV_WINO, CONV_WINO43, CONV_F16 };   // layers 2-7
 constexpr int MAX_CONV_LAYERS = 11;   // conv launches after block 1's first: 7, or 11 on the 14-layer trunk
 struct ConvLayer {
   int T, F, cin, cout, epi;

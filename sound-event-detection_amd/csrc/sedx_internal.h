@@ -347,6 +347,16 @@ void launch_conv3x3_x3(const float* in, int B, int T, int F, int Cin, int Cout, 
 void launch_block1_fused_x3(const float* x0, int B, int T, float* xpad, const float* w1, const float* b1,
                             const void* wp, const float* bias, float* out, int* sched, hipStream_t s);
 
+// Same contract on the f16 matrix pipe (SEDX_PRECISION_F16; conv_f16.hip): both operands
+// rounded by q (f16_geom.h), fp32 accumulation and epilogue.  wp = pack_f16's image
+// [Cout/128][Cin/16][9][128][2 x 16 B]; F in {32, 16, 8}, Cin % 32 == 0, Cout % 128 == 0.
+void launch_conv3x3_f16(const float* in, int B, int T, int F, int Cin, int Cout, const void* wp,
+                        const float* bias, float* out, int epi, int* sched, hipStream_t s);
+// block 1 in one launch: xpad = launch_pad_x0's zero-bordered bn0 output; conv1 (fp32: conv_c1_kernel's
+// fma chain, bias, ReLU) is computed while conv2's halo is staged, rounded by q there (wp: pack_f16, BN 64)
+void launch_block1_fused_f16(int B, int T, const float* xpad, const float* w1, const float* b1, const void* wp,
+                             const float* bias, float* out, int* sched, hipStream_t s);
+
 // ---- sequence / head ------------------------------------------------------
 // C[M][N] = act(A[M][K] . W[N][K]^T + bias[N]);  act: 0 none, 1 relu
 void launch_linear(const float* A, int M, int K, const float* W, int N, const float* bias,

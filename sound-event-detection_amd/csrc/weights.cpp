@@ -224,15 +224,26 @@ std::map<std::string, std::vector<int64_t>> expected_params(const Model& m) {
 }
 
 // ---- the blob -----------------------------------------------------------------
-void WeightBlob::add_bytes(void** dst, const void* src, size_t bytes) {
+namespace {
+size_t append256(std::vector<char>& image, const void* src, size_t bytes) {
   const size_t off = image.size();
   image.resize(off + ((bytes + 255) & ~size_t(255)), 0);
   if (bytes) std::memcpy(image.data() + off, src, bytes);
-  regions.push_back({dst, off, bytes});
+  return off;
+}
+}  // namespace
+
+void WeightBlob::add_bytes(void** dst, const void* src, size_t bytes) {
+  regions.push_back({dst, append256(image, src, bytes), bytes});
+}
+
+void WeightBlob::add_aux(void** dst, const void* src, size_t bytes) {
+  aux.push_back({dst, append256(image, src, bytes), bytes});
 }
 
 void WeightBlob::bind(void* device_base) const {
   for (const Region& r : regions) *r.dst = static_cast<char*>(device_base) + r.off;
+  for (const Region& r : aux) *r.dst = static_cast<char*>(device_base) + r.off;
 }
 
 // ---- frontend tables ----------------------------------------------------------
@@ -388,6 +399,17 @@ std::vector<uint16_t> pack_x3(const float* w, int N, int K, int taps, int BN) {
   return px;
 }
 
+// fp16 pack (conv_f16.hip): w [N][K][taps] -> q(w) as fp16 bits in the kernel's
+// LDS image [N/BN][K/16][taps][BN][2 slots x 8] (f16_geom.h: f16_pack_index)
+std::vector<uint16_t> pack_f16(const float* w, int N, int K, int taps, int BN) {
+  std::vector<uint16_t> px((size_t)N * K * taps, 0);
+  for (int o = 0; o < N; ++o)
+    for (int i = 0; i < K; ++i)
+      for (int t = 0; t < taps; ++t)
+        px[f16_pack_index(K, taps, BN, o, i, t)] = f16_q_bits(w[((size_t)o * K + i) * taps + t]);
+  return px;
+}
+
 // Winograd F(2x2,3x3) (conv_wino.hip): U = G g G^T per (input channel, output
 // channel) in float64 from the BN-folded weights, rounded once to fp32, packed
 // [Cin/4][16 p][2 h][Cout][2 ks] with channel 4 chunk + 2 h + ks (one 8-byte
@@ -496,7 +518,7 @@ sedx_status fail(std::string* err, sedx_status st, const char* fmt, ...) {
 }  // namespace
 
 sedx_status prepare_weights(const Model& m, const Params& P, DevWeights* Wp, WeightBlob* blob, GammaGeom* gamma,
-                            std::string* err) {
+                            std::string* err, F16Weights* f16) {
   for (const auto& kv : expected_params(m))
     if (!P.count(kv.first)) return fail(err, SEDX_EKEY, "missing key in state_dict: %s", kv.first.c_str());
   auto get = [&](const std::string& k) -> const std::vector<float>& { return P.at(k).data; };
@@ -622,6 +644,10 @@ sedx_status prepare_weights(const Model& m, const Params& P, DevWeights* Wp, Wei
       blob->add(&W.cb[idx], bias.data(), bias.size());
       const std::vector<uint16_t> px = pack_x3(wff.data(), cout, cin, 9, cout == 64 ? 64 : 128);
       blob->add(&W.wx3[idx], px.data(), px.size());
+      if (f16) {
+        const std::vector<uint16_t> ph = pack_f16(wff.data(), cout, cin, 9, cout == 64 ? 64 : 128);
+        blob->add_aux(&f16->w[idx], ph.data(), ph.size() * sizeof(uint16_t));
+      }
       pk.assign((size_t)cin * cout * 16, 0.f);
       pack_conv_wino(wf.data(), cin, cout, pk.data());
       blob->add(&W.wu[idx], pk.data(), pk.size());

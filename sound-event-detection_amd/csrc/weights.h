@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/sedx.h"
+#include "f16_geom.h"
 
 namespace sedx {
 
@@ -202,6 +203,13 @@ struct DevWeights {
   double* g_weightsT = nullptr;  // [gamma_kp(nfft)][64] ERB weights (fft_weights)
 };
 
+// SEDX_PRECISION_F16's conv weights: pack_f16 of block k conv j at index 2(k-1)+(j-1), as DevWeights::wx3 (half
+// the exact pack's bytes).  They live in the same device allocation as every other pack; a caller of
+// prepare_weights that passes no F16Weights gets an image without them.
+struct F16Weights {
+  void* w[8] = {};
+};
+
 // The host image of the one device allocation that holds every packed weight.
 // add() copies its source at once, at the next 256-byte offset, and remembers
 // the pointer to set; bind() sets every such pointer once the image's device
@@ -213,11 +221,13 @@ struct WeightBlob {
   };
   std::vector<char> image;
   std::vector<Region> regions;
+  std::vector<Region> aux;   // regions whose pointers are not DevWeights members (F16Weights); bound with the others
   template <typename D, typename T>
   void add(D** dst, const T* src, size_t n) {
     add_bytes(reinterpret_cast<void**>(dst), src, n * sizeof(T));
   }
   void add_bytes(void** dst, const void* src, size_t bytes);
+  void add_aux(void** dst, const void* src, size_t bytes);
   void bind(void* device_base) const;
 };
 
@@ -239,6 +249,11 @@ inline size_t deep_pack_index(int Cin, int o, int i, int tap) {
 // w [N][K][taps] fp32 -> split-bf16 pack for conv_x3.hip (taps 9) and linear_x3.hip (taps 1):
 // x = hi + lo + (dropped), hi = bf16(x), lo = bf16(x - hi), both round-to-nearest-even
 std::vector<uint16_t> pack_x3(const float* w, int N, int K, int taps, int BN);
+// w [N][K][taps] fp32 (K % 16 == 0, N % BN == 0) -> the fp16 LDS image of conv_f16.hip, N * K * taps fp16 values
+// [N/BN][K/16][taps][BN][2 slots][8]: output channel o = BN nt + n, input channel i = 16 chunk + 8 c + j sits in
+// record n's slot c ^ ((n >> 3) & 1) at element j (f16_geom.h: f16_pack_index), as q(w): clamped to +-65504,
+// rounded to nearest even with gradual underflow, then everything below 2^-14 in magnitude set to +0 (f16_q_bits)
+std::vector<uint16_t> pack_f16(const float* w, int N, int K, int taps, int BN);
 
 void pack_head(const Model& m, const Params& P, std::vector<float>* wac, std::vector<float>* bac);   // [nac][hw], [nac]
 // Cnn_9layers_Conformer's tag token [512]: linear_emb on a tensor of ones, w[c][0] * 1 + b[c] in fp32 (one rounding)
@@ -275,7 +290,8 @@ GammaLayout gamma_layout(int64_t B, int64_t L, int nfft, int hop);
 // Everything sedx_finalize_weights uploads: checks that params holds every key
 // of expected_params(m), fills the image, records where every pointer of *W
 // goes (WeightBlob::bind sets them) and sets W's scalar fields.
+// f16: where the fp16 conv packs' pointers go (blob->aux); nullptr: they are not built.
 sedx_status prepare_weights(const Model& m, const Params& params, DevWeights* W, WeightBlob* blob,
-                            GammaGeom* gamma, std::string* err);
+                            GammaGeom* gamma, std::string* err, F16Weights* f16 = nullptr);
 
 }  // namespace sedx

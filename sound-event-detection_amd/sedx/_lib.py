@@ -35,7 +35,7 @@ TUNE_GRU_KERNEL, TUNE_GRU_HANDOFF, TUNE_WINO_BLOCK1, TUNE_MEL_MFMA, TUNE_GRU_SPI
 TUNE_GAMMA_SPEC = 6
 TUNE_WINO_F43 = 7
 TUNE_CF_ATTN = 8   # 0: four lanes per query, 1: the fp32 matrix pipe, 2 (default): per model (1 on Cnn_9layers_Conformer, 0 elsewhere)
-PRECISION = {'exact': 0, 'x3': 1, 'winograd': 2}
+PRECISION = {'exact': 0, 'x3': 1, 'winograd': 2, 'f16': 3}
 STAGES = ['frontend', 'b1c1', 'b1c2', 'b2c1', 'b2c2', 'b3c1', 'b3c2', 'b4c1', 'b4c2', 'seq', 'head', 'pipeline_wait']
 
 
@@ -79,7 +79,7 @@ class SedxConvLaunch(ctypes.Structure):
         'nitems', 'nwg', 'claim', 'order2d')] + [('clips_per_launch', ctypes.c_int64)]
 
 
-CONV_FAMILY = {'exact': 0, 'x3': 1, 'f23': 2, 'f23_block1': 3, 'f43': 4}
+CONV_FAMILY = {'exact': 0, 'x3': 1, 'f23': 2, 'f23_block1': 3, 'f43': 4, 'f16': 5}
 
 
 class SedxGemmLaunch(ctypes.Structure):

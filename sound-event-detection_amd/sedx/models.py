@@ -530,8 +530,12 @@ class _SedModel(nn.Module):
         F(4x4,3x3) — _lib.TUNE_WINO_F43 0 / 1 select F(2x2,3x3) in every layer
         / in block 1 only; error vs float64 max <= 2.5e-5, rms <= 1.7e-6 per
         layer), 'exact'
-        (fp32 direct convolution, the reference's operation order) or 'x3'
-        (opt-in; 3xbf16-split MFMA, fp32 accumulate, ~1e-6 from fp32)."""
+        (fp32 direct convolution, the reference's operation order), 'x3'
+        (opt-in; 3xbf16-split MFMA, fp32 accumulate, ~1e-6 from fp32) or 'f16'
+        (opt-in, reduced precision: the packed 3x3 conv layers with both
+        operands rounded to fp16 on the f16 matrix pipe, fp32 accumulation and
+        epilogue, everything else as 'exact'; outputs move by ~5e-5 on
+        synthetic weights — include/sedx.h, SEDX_PRECISION_F16)."""
         if mode not in _lib.PRECISION:
             raise ValueError('precision must be one of %s' % sorted(_lib.PRECISION))
         self.precision = mode
